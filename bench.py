@@ -174,6 +174,24 @@ def pmc_traffic_rings(model, n, dtype, steps_per_launch):
         return None, None
 
 
+DUMP_BYTES = 60000000  # --dump-outputs: at most this many bytes of arrays (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: host array [envs, width]} -> out_dir/<name>.npy.  Beyond DUMP_BYTES in all, every array keeps
+    the same fraction of its rows, drawn with a fixed seed (the same rows from run to run with the same arguments)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_BYTES:
+            keep = max(1, a.shape[0] * DUMP_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,7 +218,7 @@ def main():
                     help="library option for every handle of this run (tds_hip_default_option), e.g. loop_w2=0, shard_wait=1")
     ap.add_argument("--y-stride", default="auto", choices=["auto", "line", "packed"],
                     help="record stride of the y ring: padded to whole 128-byte lines, or output_dim; auto (default): lines where the "
-                         "padding is under 10 % of the record")
+                         "padding is under 10 %% of the record")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary measurements of the default N = 1 line (substep_fused, one_rank_with_exchange, auto_reset_rate)")
     ap.add_argument("--shard-graph", action="store_true",
@@ -245,7 +263,14 @@ def main():
                          "f32 = 4 B per scalar as SURVEY 8e sizes the exchange (default), same / f64 = as computed")
     ap.add_argument("--force-gather", action="store_true",
                     help="run the N > 1 step loop (pipelined record gather) even with one rank: exercises that code path on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records their LAST step handed to the caller (rank 0): DIR/y.npy "
+                         "[envs, output_dim] and DIR/obs.npy [envs, obs_dim + 2] ([obs | reward | done]; N > 1: the gathered "
+                         "records of every rank), in the record dtype; beyond %d MB in all, a sample of the environments "
+                         "drawn with a fixed seed" % (DUMP_BYTES // 1000000))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -602,6 +627,18 @@ def run(args, n, rank, local_rank, world, secondary, config5):
     while not ev1.query():  # (polled: the wake-up of a blocking wait costs 10 - 60 us, a fifth of a 20-step region)
         pass
     elapsed = ranks.close_region(t0, world, "cuda", torch.cuda.synchronize)  # (sync, barrier, sync; max over ranks)
+    # --dump-outputs: the records of the last timed step, read back before anything below steps the handle again
+    # (config 5: the `value` run's only)
+    if args.dump_outputs and secondary and rank == 0:
+        if multi:
+            gat = shard.gathered_step(0) if shard_form == "ring" else shard.gathered()[:, -1]
+            y_last, obs_last = sim.y, gat.reshape(-1, gat.shape[-1])
+        elif use_rings:
+            last = (state["i"] - 1) % RS  # (slot of step K - 1 of the timed call)
+            y_last, obs_last = y_ring[last][:, :m.output_dim], obs_ring[last]
+        else:
+            y_last, obs_last = sim.y, obs
+        dump_outputs(args.dump_outputs, {"y": y_last.cpu().numpy(), "obs": obs_last.cpu().numpy()})
 
     kernel_ms = None
     kernel_ms_isolated = None
