@@ -527,6 +527,38 @@ int tds_hip_forward_zero_host_end(tds_hip_sim_t *sim);
 int tds_hip_send_local(tds_hip_sim_t *sim, int n, const double *x_host);
 int tds_hip_forward_zero_fetch(tds_hip_sim_t *sim, int n, double *y_host);
 
+/* Step Jacobians (tiny-differentiable-simulator's CudaModel::sparse_jacobian, src/utils/cuda/cuda_model.hpp:14-25,
+   cuda_codegen.hpp:303-426).  J = d y / d x of forward_zero per environment, x [input_dim] the reference record,
+   y [output_dim], taken through the algorithm as executed: clamps, PGS projections, friction boxes and the activation
+   of contacts follow the branch the primal takes; quaternion entries of x are differentiated raw (no projection onto
+   the unit sphere).  Forward mode (dual numbers), a kernel of its own; f64 handles only.  In scope: one articulated
+   body, fixed or floating base, 1-DoF and fixed joints, PD or torque actuation, plane contacts with spheres, capsules
+   and boxes; spherical joints, worlds of several bodies and f32 / float-record handles give TDS_ERR_UNSUPPORTED with
+   a tds_hip_last_error() message.  An environment whose joint-space inertia is not positive definite gets NaN
+   outputs (device) or TDS_ERR_INVALID_ARG (host). */
+enum { TDS_JAC_ACCUMULATE_NONE = 0, TDS_JAC_ACCUMULATE_SUM = 1, TDS_JAC_ACCUMULATE_MEAN = 2 }; /* CudaAccumulationMethod */
+/* Directional derivatives: jv[n][k][output_dim] = J v for v [n][k][input_dim]; y [n][output_dim] (optional, may be
+   NULL) = forward_zero's output.  All device pointers, n environments (any n >= 1, independent of num_envs).
+   Enqueued on the handle's stream; the host waits for that stream only when the handle's work buffer has to grow.
+   Work buffer: one work object per lane (the step's state in dual form: 54 KB (cartpole, pendulum5, cube_floating),
+   76 KB (ant), 69 KB (laikago)) for min(n * ceil(k / K), 16384) lanes, K = tds_hip_jacobian_tangents; it is kept by
+   the handle for the next call and freed with it. */
+int tds_hip_jvp(tds_hip_sim_t *sim, int n, const void *x_dev, int k, const void *v_dev, void *y_dev, void *jv_dev);
+/* Jacobian rows x columns (set_jac_output_sparsity / set_jac_local_input_sparsity): rows_host [n_rows] indices into y,
+   cols_host [n_cols] into x, host arrays, NULL = dense (the count is then ignored).  accumulate NONE: jac_dev
+   [n][n_rows][n_cols]; SUM / MEAN: [n_rows][n_cols] summed / averaged over the n environments in environment order.
+   y_dev optional.  Enqueued on the handle's stream (work buffer as for tds_hip_jvp, with k = n_cols, plus
+   n * n_rows * n_cols doubles for SUM / MEAN); the host waits for that stream first where a row or column selection
+   is given (it is copied into the work buffer with a blocking copy) or the work buffer has to grow. */
+int tds_hip_jacobian(tds_hip_sim_t *sim, int n, const void *x_dev, int n_rows, const int *rows_host, int n_cols,
+                     const int *cols_host, int accumulate, void *y_dev, void *jac_dev);
+/* The same template on the CPU (checker and CPU fallback; needs no GPU): host arrays, y (optional) from the double
+   instantiation of the step, jac (optional) as tds_hip_jacobian lays it out. */
+int tds_hip_jacobian_host(const tds_model_t *model, int n, const double *x, int n_rows, const int *rows, int n_cols,
+                          const int *cols, int accumulate, double *y, double *jac);
+/* Tangents one device lane carries for this model (the K of TdsDual<K>); 0 if the model is refused. */
+int tds_hip_jacobian_tangents(const tds_model_t *model);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

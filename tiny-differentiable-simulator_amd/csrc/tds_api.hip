@@ -591,6 +591,8 @@ int tds_hip_destroy(tds_hip_sim_t *s) {
   if (s->h_stage) (void)hipHostFree(s->h_stage);
   if (s->d_stage_act) (void)hipFree(s->d_stage_act);
   if (s->d_stage_obs) (void)hipFree(s->d_stage_obs);
+  if (s->d_diff_model) (void)hipFree(s->d_diff_model);
+  if (s->d_diff_tmp) (void)hipFree(s->d_diff_tmp);
   delete s;
   return TDS_OK;
 }

@@ -50,6 +50,9 @@ struct tds_hip_sim {
   // pinned staging of the host-vector entry points (tds_hip_step_host / tds_hip_reset_host): actions up, records down
   void *h_stage = nullptr, *d_stage_act = nullptr, *d_stage_obs = nullptr;
   size_t h_stage_bytes = 0;
+  // step Jacobians (tds_jvp.hip): the model blob on the device, and the work buffer of tds_hip_jacobian
+  void *d_diff_model = nullptr, *d_diff_tmp = nullptr;
+  size_t diff_tmp_bytes = 0;
   bool stage_ready = false;        // the three staging buffers exist (set last by stage_alloc: all or nothing)
   const TdsPeerLaunch *peer_launch = nullptr;  // != NULL: the next ring launch is a peer-store exchange launch (see above)
   bool shard_ring_shaped = false;  // a shard layer has laid out its ring from this handle's options (tds_shard.hip: ring_alloc)

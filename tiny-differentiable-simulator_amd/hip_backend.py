@@ -110,6 +110,12 @@ def lib():
         L.tds_hip_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
         L.tds_hip_option_name.argtypes = [C.c_int]
         L.tds_hip_option_name.restype = C.c_char_p
+        L.tds_hip_jvp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tds_hip_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p]
+        L.tds_hip_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p]
+        L.tds_hip_jacobian_tangents.argtypes = [P]
         _lib = L
     return _lib
 
@@ -144,6 +150,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_shard_step", "tds_hip_shard_step_many", "tds_hip_shard_step_many_prepare", "tds_hip_shard_group_step", "tds_hip_shard_flush", "tds_hip_shard_gathered", "tds_hip_shard_gathered_step",
     "tds_hip_shard_ring_plan", "tds_hip_shard_gathered_offset", "tds_hip_shard_exchange_form", "tds_hip_shard_peer_count",
     "tds_hip_single_step_kernel",
+    "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step",
 ]
@@ -202,6 +209,57 @@ def _check(rc):
 
 def model_check(m: _model.Model) -> None:
     _check(lib().tds_hip_model_check(C.byref(m)))
+
+
+# step Jacobians: accumulation methods (the reference's CudaAccumulationMethod)
+JAC_ACCUMULATE = {None: 0, "none": 0, "sum": 1, "mean": 2}
+
+
+def _index_array(idx):
+    """None (dense) or a host int32 array of indices, kept alive by the caller"""
+    import numpy as np
+
+    if idx is None:
+        return None, 0, None
+    a = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1).astype(np.int32))
+    return a, a.shape[0], C.c_void_p(a.ctypes.data)
+
+
+def jacobian_host(m: _model.Model, x, rows=None, cols=None, accumulate=None, want_y: bool = False):
+    """The step Jacobian on the CPU (tds_hip_jacobian_host; the checker of the device path, needs no GPU).
+
+    x: [N, input_dim] float64.  Returns jac [N, n_rows, n_cols] (accumulate None) or [n_rows, n_cols] ("sum",
+    "mean"); with want_y also forward_zero's y [N, output_dim] from the double instantiation of the same template."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n = x.shape[0]
+    ra, nr, rp = _index_array(rows)
+    ca, nc, cp = _index_array(cols)
+    nr = nr if rows is not None else m.output_dim
+    nc = nc if cols is not None else m.input_dim
+    acc = JAC_ACCUMULATE[accumulate]
+    jac = np.zeros((n, nr, nc) if acc == 0 else (nr, nc), dtype=np.float64)
+    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
+    _check(lib().tds_hip_jacobian_host(C.byref(m), n, x.ctypes.data, nr, rp, nc, cp, acc,
+                                       y.ctypes.data if want_y else None, jac.ctypes.data))
+    return (jac, y) if want_y else jac
+
+
+def step_host(m: _model.Model, x):
+    """forward_zero through the double instantiation of the step Jacobians' template (CPU)"""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    y = np.zeros((x.shape[0], m.output_dim), dtype=np.float64)
+    _check(lib().tds_hip_jacobian_host(C.byref(m), x.shape[0], x.ctypes.data, 0, None, 0, None, 0, y.ctypes.data,
+                                       None))
+    return y
+
+
+def jacobian_tangents(m: _model.Model) -> int:
+    """tangents one device lane carries for this model (0: the model is refused)"""
+    return int(lib().tds_hip_jacobian_tangents(C.byref(m)))
 
 
 def wrap_device_pointer(ptr: int, shape, torch_dtype, device: int, owner=None):
@@ -467,6 +525,46 @@ class HipSim:
         assert y.is_cuda and y.dtype == self.torch_dtype and y.is_contiguous()
         _check(lib().tds_hip_forward_zero_device(self.h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())))
         return y
+
+    # -- step Jacobians (forward mode, a kernel of its own) ------------------------------------
+    def jvp(self, x, v, y=None):
+        """(y, jv): y = f(x) [N, output_dim] and the directional derivatives jv = J(x) v [N, K, output_dim] for
+        v [N, K, input_dim] (or [N, input_dim]: K = 1, jv [N, output_dim]).  Any N; f64 handles only (async)."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        squeeze = v.dim() == 2
+        v3 = v.unsqueeze(1) if squeeze else v
+        assert v3.is_cuda and v3.dtype == torch.float64 and tuple(v3.shape[::2]) == (x.shape[0], self.input_dim)
+        x, v3 = x.contiguous(), v3.contiguous()
+        n, k = x.shape[0], v3.shape[1]
+        if y is None:
+            y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
+        jv = torch.empty((n, k, self.output_dim), dtype=torch.float64, device=x.device)
+        _check(lib().tds_hip_jvp(self.h, n, C.c_void_p(x.data_ptr()), k, C.c_void_p(v3.data_ptr()),
+                                 C.c_void_p(y.data_ptr()), C.c_void_p(jv.data_ptr())))
+        return y, (jv[:, 0] if squeeze else jv)
+
+    def jacobian(self, x, rows=None, cols=None, accumulate=None, y=None):
+        """J = dy/dx at x [N, input_dim]: [N, n_rows, n_cols] (accumulate None) or [n_rows, n_cols] ("sum", "mean");
+        rows / cols: index lists into y / x (None: dense).  With y (a [N, output_dim] tensor) forward_zero's output is
+        written too.  Any N; f64 handles only."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        x = x.contiguous()
+        n = x.shape[0]
+        ra, nr, rp = _index_array(rows)
+        ca, nc, cp = _index_array(cols)
+        nr = nr if rows is not None else self.output_dim
+        nc = nc if cols is not None else self.input_dim
+        acc = JAC_ACCUMULATE[accumulate]
+        jac = torch.empty((n, nr, nc) if acc == 0 else (nr, nc), dtype=torch.float64, device=x.device)
+        if y is not None:
+            assert y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (n, self.output_dim)
+        _check(lib().tds_hip_jacobian(self.h, n, C.c_void_p(x.data_ptr()), nr, rp, nc, cp, acc,
+                                      C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(jac.data_ptr())))
+        return jac
 
     def step(self, actions=None, substeps: int = 1, obs=None):
         """Closed-loop step on the resident records (async): x[:, act] <- actions, y = f(x),
