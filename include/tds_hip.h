@@ -559,6 +559,27 @@ int tds_hip_jacobian_host(const tds_model_t *model, int n, const double *x, int 
 /* Tangents one device lane carries for this model (the K of TdsDual<K>); 0 if the model is refused. */
 int tds_hip_jacobian_tangents(const tds_model_t *model);
 
+/* Step VJPs: reverse mode of the same derivative (the branch of the primal, quaternions raw), one tape per
+   environment swept back once per cotangent.  wj[n][k][input_dim] = w^T J(x) for w [n][k][output_dim], per environment
+   and cotangent; y [n][output_dim] (optional, may be NULL) = forward_zero's output.  Entries of w past the step's
+   written outputs (q | qd | visuals | up . z) contribute nothing.  All device pointers, any n >= 1, f64 handles only;
+   scope and refusals as for tds_hip_jacobian.  An environment whose joint-space inertia is not positive definite gets
+   NaN outputs.  The tape of an environment holds at most a bound per model class (18 to 28 % above the longest tape
+   counted for the class's models): an environment that would exceed it gets NaN outputs and the call returns
+   TDS_ERR_UNSUPPORTED.  Enqueued on the handle's stream (a recording and a sweep kernel per 4096 environments); the call
+   waits for them (it reads back the overflow flag).
+   Work buffer (shared with tds_hip_jvp / tds_hip_jacobian, grown as needed and kept by the handle): for
+   min(ceil(n / 64) * 64, 4096) lanes, the lane's work object plus 32 B per tape entry of the bound (10.9 GB for Ant
+   x 4096). */
+int tds_hip_vjp(tds_hip_sim_t *sim, int n, const void *x_dev, int k, const void *w_dev, void *y_dev, void *wj_dev);
+/* The same on the CPU (host arrays, needs no GPU); a joint-space inertia that is not positive definite gives NaN
+   outputs and TDS_ERR_INVALID_ARG, an overflowing tape NaN outputs and TDS_ERR_UNSUPPORTED. */
+int tds_hip_vjp_host(const tds_model_t *model, int n, const double *x, int k, const double *w, double *y, double *wj);
+/* tds_hip_vjp_host with the tape capacity tape_cap (<= 0: the class's bound, as tds_hip_vjp_host) and, where
+   tape_len [n] is given, the number of entries each environment recorded (-1 where it overflowed). */
+int tds_hip_vjp_host_tape(const tds_model_t *model, int n, const double *x, int k, const double *w, double *y,
+                          double *wj, int tape_cap, int *tape_len);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

@@ -2,10 +2,13 @@
 
 The forward pass is the step kernels' forward_zero.  Where ``x.requires_grad``, it also computes the step Jacobian J
 [N, output_dim, input_dim] with the forward-mode kernel (HipSim.jacobian), and the backward pass returns J^T grad_y
-by bmm.  The derivative is that of the algorithm as executed (clamps, PGS projections and contact activation follow
-the branch the primal takes; quaternion entries differentiated raw): see DESIGN.md, "Step Jacobians"."""
+by bmm.  With ``step_fn(sim, mode="reverse")`` the forward pass keeps only x, and the backward pass returns
+grad_y^T J from the reverse-mode kernel (HipSim.vjp): no Jacobian is formed.  The derivative is that of the algorithm
+as executed (clamps, PGS projections and contact activation follow the branch the primal takes; quaternion entries
+differentiated raw): see DESIGN.md, "Step Jacobians"."""
 
 _StepFunction = None
+_StepFunctionReverse = None
 
 
 def _function():
@@ -33,9 +36,45 @@ def _function():
     return _StepFunction
 
 
-def step_fn(sim):
-    """x [num_envs, input_dim] (float64, on the sim's device) -> y = forward_zero(x), differentiable in x"""
-    fn = _function()
+def _function_reverse():
+    """the reverse-mode autograd.Function, built on first use"""
+    global _StepFunctionReverse
+    if _StepFunctionReverse is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class StepFunctionReverse(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, sim):
+                xd = x.detach().contiguous()
+                y = sim.forward_zero(xd)
+                ctx.sim = sim
+                if ctx.needs_input_grad[0]:
+                    ctx.save_for_backward(xd)
+                return y
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_y):
+                (xd,) = ctx.saved_tensors
+                _, grad_x = ctx.sim.vjp(xd, grad_y.to(xd.dtype).contiguous())
+                return grad_x, None
+
+        _StepFunctionReverse = StepFunctionReverse
+    return _StepFunctionReverse
+
+
+def step_fn(sim, mode: str = "forward"):
+    """x [num_envs, input_dim] (float64, on the sim's device) -> y = forward_zero(x), differentiable in x.
+
+    mode "forward": the forward pass computes the dense Jacobian where x requires grad, backward is J^T grad_y.
+    mode "reverse": the forward pass saves x, backward is one VJP per call (HipSim.vjp)."""
+    if mode == "forward":
+        fn = _function()
+    elif mode == "reverse":
+        fn = _function_reverse()
+    else:
+        raise ValueError(f"step_fn: mode must be 'forward' or 'reverse', not {mode!r}")
 
     def f(x):
         return fn.apply(x, sim)

@@ -13,18 +13,12 @@
 
 #include <vector>
 
-#include "tds_api_internal.h"
-#include "tds_diff_step.h"
+#include "tds_diff_classes.h"
 
 using namespace tds_internal;
 
 namespace {
 
-// model classes: the smallest bound a model fits is taken (tds_jvp_pick)
-// (links, dofs, contact points, visuals)
-using TdsBoundS = TdsDiffBounds<8, 8, 8, 8>;      // cartpole, pendulum5 (+ plane), cube_floating
-using TdsBoundA = TdsDiffBounds<14, 14, 17, 9>;   // ant, ant_floating, cartpole_plane (two boxes: 16 points)
-using TdsBoundL = TdsDiffBounds<22, 18, 4, 17>;   // laikago, laikago_soft, laikago_floating(_env)
 // tangents per lane of each class on the device (the lane's work object grows with K + 1)
 template <class B>
 struct TdsJvpK;
@@ -35,15 +29,6 @@ struct TdsJvpK<TdsBoundA> { static constexpr int K = 2; };
 template <>
 struct TdsJvpK<TdsBoundL> { static constexpr int K = 2; };
 constexpr int kHostK = 8;  // tangents per evaluation on the host
-
-// 0..2: class S, A, L; -1: refused (why set)
-int tds_jvp_pick(const tds_model_t *m, const char **why) {
-  if (!m) return *why = "NULL model", -1;
-  if (tds_diff_check<TdsBoundS>(m, why) == 0) return 0;
-  if (tds_diff_check<TdsBoundA>(m, why) == 0) return 1;
-  if (tds_diff_check<TdsBoundL>(m, why) == 0) return 2;
-  return -1;
-}
 
 // What a launch computes.  JVP: directions v[n][kdirs][input_dim], out = jv[n][kdirs][output_dim].  Jacobian: unit
 // directions e_cols[c] (cols NULL: e_c), out = jac[n][n_rows][n_cols] at rows[r] (rows NULL: r).
@@ -173,32 +158,6 @@ int tds_jvp_dispatch(tds_hip_sim *s, int cls, const TdsJvpArgs &a) {
   }
 }
 
-// the work buffer holds at least `need` bytes.  Launches on the handle's stream use it one after the other; only a
-// buffer that has to grow is replaced, after the host waits for the earlier calls on the stream.
-int tds_jvp_tmp(tds_hip_sim *s, size_t need) {
-  if (need > s->diff_tmp_bytes) {
-    TDS_HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->d_diff_tmp) TDS_HIP_TRY(hipFree(s->d_diff_tmp));
-    s->d_diff_tmp = nullptr, s->diff_tmp_bytes = 0;
-    TDS_HIP_TRY(hipMalloc(&s->d_diff_tmp, need));
-    s->diff_tmp_bytes = need;
-  }
-  return TDS_OK;
-}
-
-// the handle's checks and its device copy of the model blob
-int tds_jvp_prepare(tds_hip_sim *s, int *cls) {
-  if (s->dtype != TDS_DTYPE_F64) return fail(TDS_ERR_UNSUPPORTED, "step Jacobians: f64 handles only%s");
-  const char *why = "";
-  *cls = tds_jvp_pick(&s->model, &why);
-  if (*cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
-  if (!s->d_diff_model) {
-    TDS_HIP_TRY(hipMalloc(&s->d_diff_model, sizeof(tds_model_t)));
-    TDS_HIP_TRY(hipMemcpy(s->d_diff_model, &s->model, sizeof(tds_model_t), hipMemcpyHostToDevice));
-  }
-  return TDS_OK;
-}
-
 int tds_jac_check_sel(const tds_model_t *m, int n_rows, const int *rows, int n_cols, const int *cols) {
   for (int r = 0; rows && r < n_rows; ++r)
     if (rows[r] < 0 || rows[r] >= m->output_dim) return fail(TDS_ERR_INVALID_ARG, "step Jacobians: row index out of range%s");
@@ -240,6 +199,36 @@ int tds_jac_host_impl(const tds_model_t *m, int n, const double *x, int n_rows, 
 }
 
 }  // namespace
+
+namespace tds_internal {
+
+// the work buffer holds at least `need` bytes.  Launches on the handle's stream use it one after the other; only a
+// buffer that has to grow is replaced, after the host waits for the earlier calls on the stream.
+int tds_jvp_tmp(tds_hip_sim *s, size_t need) {
+  if (need > s->diff_tmp_bytes) {
+    TDS_HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->d_diff_tmp) TDS_HIP_TRY(hipFree(s->d_diff_tmp));
+    s->d_diff_tmp = nullptr, s->diff_tmp_bytes = 0;
+    TDS_HIP_TRY(hipMalloc(&s->d_diff_tmp, need));
+    s->diff_tmp_bytes = need;
+  }
+  return TDS_OK;
+}
+
+// the handle's checks and its device copy of the model blob
+int tds_jvp_prepare(tds_hip_sim *s, int *cls) {
+  if (s->dtype != TDS_DTYPE_F64) return fail(TDS_ERR_UNSUPPORTED, "step Jacobians: f64 handles only%s");
+  const char *why = "";
+  *cls = tds_jvp_pick(&s->model, &why);
+  if (*cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
+  if (!s->d_diff_model) {
+    TDS_HIP_TRY(hipMalloc(&s->d_diff_model, sizeof(tds_model_t)));
+    TDS_HIP_TRY(hipMemcpy(s->d_diff_model, &s->model, sizeof(tds_model_t), hipMemcpyHostToDevice));
+  }
+  return TDS_OK;
+}
+
+}  // namespace tds_internal
 
 extern "C" {
 

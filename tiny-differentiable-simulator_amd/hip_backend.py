@@ -116,6 +116,10 @@ def lib():
         L.tds_hip_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p]
         L.tds_hip_jacobian_tangents.argtypes = [P]
+        L.tds_hip_vjp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tds_hip_vjp_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tds_hip_vjp_host_tape.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -151,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_shard_ring_plan", "tds_hip_shard_gathered_offset", "tds_hip_shard_exchange_form", "tds_hip_shard_peer_count",
     "tds_hip_single_step_kernel",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
+    "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step",
 ]
@@ -255,6 +260,37 @@ def step_host(m: _model.Model, x):
     _check(lib().tds_hip_jacobian_host(C.byref(m), x.shape[0], x.ctypes.data, 0, None, 0, None, 0, y.ctypes.data,
                                        None))
     return y
+
+
+def vjp_host(m: _model.Model, x, w, want_y: bool = False, tape_cap: int = 0, tape_len: bool = False):
+    """The step VJP on the CPU (tds_hip_vjp_host: reverse mode, the checker of the device path, needs no GPU).
+
+    x: [N, input_dim], w: [N, K, output_dim] or [N, output_dim] (K = 1) float64.  Returns wj = w^T J [N, K, input_dim]
+    (or [N, input_dim]); with want_y also forward_zero's y [N, output_dim].  tape_cap > 0 replaces the model class's
+    tape capacity, and tape_len adds the entries each environment recorded (-1: overflowed) to what is returned
+    (tds_hip_vjp_host_tape)."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n = x.shape[0]
+    w = np.asarray(w, dtype=np.float64)
+    squeeze = w.ndim == 2
+    w3 = np.ascontiguousarray(w[:, None] if squeeze else w)
+    if w3.ndim != 3 or w3.shape[0] != n or w3.shape[2] != m.output_dim:
+        raise ValueError(f"w: expected [{n}, K, {m.output_dim}] or [{n}, {m.output_dim}], got {tuple(w.shape)}")
+    k = w3.shape[1]
+    wj = np.zeros((n, k, m.input_dim), dtype=np.float64)
+    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
+    lens = np.zeros(n, dtype=np.int32) if tape_len else None
+    _check(lib().tds_hip_vjp_host_tape(C.byref(m), n, x.ctypes.data, k, w3.ctypes.data,
+                                       y.ctypes.data if want_y else None, wj.ctypes.data, int(tape_cap),
+                                       lens.ctypes.data if tape_len else None))
+    out = (wj[:, 0] if squeeze else wj,)
+    if want_y:
+        out += (y,)
+    if tape_len:
+        out += (lens,)
+    return out if len(out) > 1 else out[0]
 
 
 def jacobian_tangents(m: _model.Model) -> int:
@@ -565,6 +601,27 @@ class HipSim:
         _check(lib().tds_hip_jacobian(self.h, n, C.c_void_p(x.data_ptr()), nr, rp, nc, cp, acc,
                                       C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(jac.data_ptr())))
         return jac
+
+    def vjp(self, x, w, y=None):
+        """(y, wj): y = f(x) [N, output_dim] and the vector-Jacobian products wj = w^T J(x) [N, K, input_dim] for
+        cotangents w [N, K, output_dim] (or [N, output_dim]: K = 1, wj [N, input_dim]).  Reverse mode: one tape per
+        environment, swept back once per cotangent.  Any N; f64 handles only.  The call waits for its kernels."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        squeeze = w.dim() == 2
+        w3 = w.unsqueeze(1) if squeeze else w
+        assert w3.is_cuda and w3.dtype == torch.float64 and w3.dim() == 3
+        assert tuple(w3.shape[::2]) == (x.shape[0], self.output_dim)
+        x, w3 = x.contiguous(), w3.contiguous()
+        n, k = x.shape[0], w3.shape[1]
+        if y is None:
+            y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
+        assert y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (n, self.output_dim)
+        wj = torch.empty((n, k, self.input_dim), dtype=torch.float64, device=x.device)
+        _check(lib().tds_hip_vjp(self.h, n, C.c_void_p(x.data_ptr()), k, C.c_void_p(w3.data_ptr()),
+                                 C.c_void_p(y.data_ptr()), C.c_void_p(wj.data_ptr())))
+        return y, (wj[:, 0] if squeeze else wj)
 
     def step(self, actions=None, substeps: int = 1, obs=None):
         """Closed-loop step on the resident records (async): x[:, act] <- actions, y = f(x),
