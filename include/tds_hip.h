@@ -580,6 +580,49 @@ int tds_hip_vjp_host(const tds_model_t *model, int n, const double *x, int k, co
 int tds_hip_vjp_host_tape(const tds_model_t *model, int n, const double *x, int k, const double *w, double *y,
                           double *wj, int tape_cap, int *tape_len);
 
+/* Parameter derivatives: the step derivatives above taken in [x | theta], theta [n][p] f64 per environment, the model
+   scalars a selection params[p] names, in that order (system identification: examples/pendulum_sys_id.cpp).  The step
+   reads theta_i in place of the blob's values for environment i; every other scalar comes from the blob.  Derivative,
+   scope, refusals and error handling as for tds_hip_jacobian / tds_hip_vjp.  A selection with an unknown kind, a link
+   or comp out of range, a duplicate entry or a base kind on a fixed base gives TDS_ERR_INVALID_ARG.  dt, cfm, erp,
+   geometry and visuals are not selectable. */
+enum {
+  TDS_PARAM_LINK_MASS = 0,       /* links[link].mass */
+  TDS_PARAM_LINK_COM = 1,        /* links[link].com[comp], comp 0..2 */
+  TDS_PARAM_LINK_INERTIA = 2,    /* links[link].inertia, comp 0..5 = xx, yy, zz, xy, xz, yz (an off-diagonal comp sets
+                                    both mirror entries) */
+  TDS_PARAM_LINK_XT_TRANS = 3,   /* links[link].X_T_trans[comp], comp 0..2 */
+  TDS_PARAM_LINK_STIFFNESS = 4,  /* links[link].stiffness */
+  TDS_PARAM_LINK_DAMPING = 5,    /* links[link].damping */
+  TDS_PARAM_BASE_MASS = 6,       /* base_mass (floating base only; link 0) */
+  TDS_PARAM_BASE_COM = 7,        /* base_com[comp] (floating base only) */
+  TDS_PARAM_BASE_INERTIA = 8,    /* base_inertia, comp as for links (floating base only) */
+  TDS_PARAM_GRAVITY = 9,         /* gravity[comp] (link 0) */
+  TDS_PARAM_FRICTION = 10,       /* friction (link 0, comp 0) */
+  TDS_PARAM_RESTITUTION = 11     /* restitution (link 0, comp 0) */
+};
+typedef struct tds_param {
+  int32_t kind, link, comp, pad_; /* TDS_PARAM_*; link 0 and comp 0 where the kind has none */
+} tds_param_t;
+/* theta [p] = the blob's values of the selection (host arrays); checks the selection. */
+int tds_hip_params_get(const tds_model_t *model, int p, const tds_param_t *params, double *theta);
+/* Forward mode in [x | theta]: jv[n][k][output_dim] = J v for v [n][k][input_dim + p]; k = 0 computes y only (v, jv
+   may then be NULL).  x_dev [n][input_dim], theta_dev [n][p], y_dev (optional) [n][output_dim]: device pointers;
+   params_host: host array.  Enqueued on the handle's stream (the selection is copied into the work buffer with a
+   blocking copy).  Work buffer as for tds_hip_jvp, each lane's work object holding the overlay of parameters. */
+int tds_hip_jvp_params(tds_hip_sim_t *sim, int n, const void *x_dev, int p, const tds_param_t *params_host,
+                       const void *theta_dev, int k, const void *v_dev, void *y_dev, void *jv_dev);
+/* Reverse mode in [x | theta]: wj[n][k][input_dim + p] = w^T J for w [n][k][output_dim], the x part first.  As
+   tds_hip_vjp (tape bound per class for parameter mode; the call waits for its kernels). */
+int tds_hip_vjp_params(tds_hip_sim_t *sim, int n, const void *x_dev, int p, const tds_param_t *params_host,
+                       const void *theta_dev, int k, const void *w_dev, void *y_dev, void *wj_dev);
+/* The same templates on the CPU (host arrays, needs no GPU); jv / wj as above, y optional. */
+int tds_hip_jvp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
+                            const double *theta, int k, const double *v, double *y, double *jv);
+int tds_hip_vjp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
+                            const double *theta, int k, const double *w, double *y, double *wj, int tape_cap,
+                            int *tape_len);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

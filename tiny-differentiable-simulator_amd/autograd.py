@@ -5,10 +5,14 @@ The forward pass is the step kernels' forward_zero.  Where ``x.requires_grad``, 
 by bmm.  With ``step_fn(sim, mode="reverse")`` the forward pass keeps only x, and the backward pass returns
 grad_y^T J from the reverse-mode kernel (HipSim.vjp): no Jacobian is formed.  The derivative is that of the algorithm
 as executed (clamps, PGS projections and contact activation follow the branch the primal takes; quaternion entries
-differentiated raw): see DESIGN.md, "Step Jacobians"."""
+differentiated raw): see DESIGN.md, "Step Jacobians".
+
+``param_step_fn(sim, params)(x, theta)`` is the step at the model parameters theta (the selection ``params``,
+hip_backend.param_spec), differentiable in x and theta: see DESIGN.md, "Parameter derivatives"."""
 
 _StepFunction = None
 _StepFunctionReverse = None
+_ParamStepFunction = None
 
 
 def _function():
@@ -78,5 +82,71 @@ def step_fn(sim, mode: str = "forward"):
 
     def f(x):
         return fn.apply(x, sim)
+
+    return f
+
+
+def _param_function():
+    """the autograd.Function of param_step_fn, built on first use"""
+    global _ParamStepFunction
+    if _ParamStepFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class ParamStepFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, theta, sim, params, mode):
+                xd, th = x.detach().contiguous(), theta.detach().contiguous()
+                n, nin, p = xd.shape[0], sim.input_dim, len(params)
+                ctx.sim, ctx.params, ctx.mode, ctx.shared = sim, params, mode, th.dim() == 1
+                if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+                    return sim.jvp_params(xd, th, params)
+                if mode == "forward":  # J^T [N, input_dim + p, output_dim] from one unit direction per input
+                    eye = torch.eye(nin + p, dtype=torch.float64, device=xd.device)
+                    y, jt = sim.jvp_params(xd, th, params, eye.expand(n, nin + p, nin + p).contiguous())
+                    ctx.save_for_backward(jt)
+                else:
+                    y = sim.jvp_params(xd, th, params)
+                    ctx.save_for_backward(xd, th)
+                return y
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_y):
+                nin = ctx.sim.input_dim
+                if ctx.mode == "forward":
+                    (jt,) = ctx.saved_tensors
+                    g = torch.bmm(jt, grad_y.to(jt.dtype).unsqueeze(2)).squeeze(2)
+                    gx, gth = g[:, :nin], g[:, nin:]
+                else:
+                    xd, th = ctx.saved_tensors
+                    _, gx, gth = ctx.sim.vjp_params(xd, th, ctx.params, grad_y.to(xd.dtype).contiguous())
+                if ctx.shared:  # one theta for every environment: its gradient sums over them
+                    gth = gth.sum(0)
+                return gx, gth, None, None, None
+
+        _ParamStepFunction = ParamStepFunction
+    return _ParamStepFunction
+
+
+def param_step_fn(sim, params, mode: str = "reverse"):
+    """(x, theta) -> y: the step of x [num_envs, input_dim] at the model parameters theta, differentiable in both.
+
+    params: the selection (tuples such as ("mass", 3), ("com", 3, 2), ("xt_trans", 1, 2), ("friction",), or
+    tds_param_t; hip_backend.param_spec).  theta: [p], shared by every environment (its gradient is summed over
+    them), or [N, p].  The forward pass computes y at theta with the parameter kernel (HipSim.jvp_params).
+    mode "reverse": backward is one VJP per call (HipSim.vjp_params).  mode "forward": where an input requires grad,
+    the forward pass forms J over [x | theta] (input_dim + p directions) and backward is J^T grad_y."""
+    from . import hip_backend
+
+    if mode not in ("forward", "reverse"):
+        raise ValueError(f"param_step_fn: mode must be 'forward' or 'reverse', not {mode!r}")
+    sel = hip_backend.param_spec(params)
+    p = len(params)
+    fn = _param_function()
+    spec = [sel[j] for j in range(p)]  # checked tds_param_t entries (param_spec passes them through)
+
+    def f(x, theta):
+        return fn.apply(x, theta, sim, spec, mode)
 
     return f

@@ -1,5 +1,6 @@
-// tds_diff_classes.h — what the two step-derivative translation units share (tds_jvp.hip: forward mode, tds_vjp.hip:
-// reverse mode): the model classes and their bounds, the class of a model, the handle's checks and its work buffer.
+// tds_diff_classes.h — what the step-derivative translation units share (tds_jvp.hip: forward mode, tds_vjp.hip:
+// reverse mode, tds_dparam.hip: both in [x | theta]): the model classes and their bounds, the class of a model, the
+// forward-mode tangents and lanes per launch, the handle's checks and its work buffer.
 #pragma once
 #include "tds_api_internal.h"
 #include "tds_diff_step.h"
@@ -19,6 +20,29 @@ inline int tds_jvp_pick(const tds_model_t *m, const char **why) {
   if (tds_diff_check<TdsBoundA>(m, why) == 0) return 1;
   if (tds_diff_check<TdsBoundL>(m, why) == 0) return 2;
   return -1;
+}
+
+// tangents per lane of each class on the device (the lane's work object grows with K + 1)
+template <class B>
+struct TdsJvpK;
+template <>
+struct TdsJvpK<TdsBoundS> { static constexpr int K = 4; };
+template <>
+struct TdsJvpK<TdsBoundA> { static constexpr int K = 2; };
+template <>
+struct TdsJvpK<TdsBoundL> { static constexpr int K = 2; };
+
+// lanes of one launch: each walks the (environment, direction block) items with the grid's stride.  The cap bounds the
+// work buffer (kJvpLanes work objects: 0.9 - 1.2 GB); it also leaves three of four SIMDs without a wave at the kernel's
+// occupancy of one
+constexpr long long kJvpLanes = 16384;
+
+// lanes of a launch over n environments x kdirs directions: one per item, at most kJvpLanes
+template <class B>
+long long tds_jvp_lanes(int n, int kdirs) {
+  constexpr int K = TdsJvpK<B>::K;
+  const long long items = (long long)n * ((kdirs + K - 1) / K);
+  return items < kJvpLanes ? items : kJvpLanes;
 }
 
 // the handle's checks (f64, a supported model) and its device copy of the model blob

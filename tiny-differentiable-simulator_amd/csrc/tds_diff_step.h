@@ -1,6 +1,8 @@
 // tds_diff_step.h — one single-source, scalar-templated statement of the per-environment step (forward_zero) for the
-// step Jacobians.  Instantiated over double (host: the checker against the reference) and over TdsDual<K>
-// (tds_dual.h; host and device: K directional derivatives per evaluation, tds_jvp.hip).
+// step Jacobians.  Instantiated over double (host: the checker against the reference), over TdsDual<K>
+// (tds_dual.h; host and device: K directional derivatives per evaluation, tds_jvp.hip) and over TdsRev (tds_rev.h,
+// tds_vjp.hip).  The model's selectable parameters are read through a view (TdsBlobView: the blob's values;
+// TdsOverlayView: T-typed copies with active theta, the parameter derivatives of tds_dparam.hip).
 //
 // WHAT THE DERIVATIVE IS.  J = dy/dx of forward_zero per environment, x = the reference record [input_dim] (q, qd,
 // actions, and kp, kd, max_force where the record carries them), y = [output_dim].  It is the derivative of the
@@ -343,10 +345,169 @@ TDS_HD inline void tds_d_abi_inv_mul(const TdsDAbi<T> &A, const TdsDSv<T> &f, Td
   for (int k = 0; k < 3; ++k) o.l[k] = a[k] - b[k];
 }
 
+// ---------------------------------------------------------------- parameter views
+// Every read of a selectable model parameter (tds_param_t, include/tds_hip.h: masses, COMs, inertias, X_T
+// translations, springs, gravity, friction, restitution) goes through a view P, passed by value.  TdsBlobView reads
+// the blob as double constants: the code of the plain instantiations, tds_diff_step(m, w, x, y).  TdsOverlayView reads
+// a TdsParamOverlay<T, B>: T-typed copies seeded from the blob (tds_param_seed), the selected entries replaced by
+// active theta (tds_param_set); the overlay lives in the lane's work object (tds_dparam.hip).
+struct TdsBlobView {  // no state: passed by value, it adds nothing to the plain instantiations' code
+  TDS_HD const double *xt(const tds_model_t *m, int i) const { return m->links[i].X_T_trans; }
+  template <typename T>
+  TDS_HD void link_rbi(const tds_model_t *m, int i, TdsDAbi<T> &o) const {
+    const tds_link_t &l = m->links[i];
+    tds_d_abi_rbi(l.mass, l.com, l.inertia, o);
+  }
+  template <typename T>
+  TDS_HD void base_rbi(const tds_model_t *m, TdsDAbi<T> &o) const {
+    tds_d_abi_rbi(m->base_mass, m->base_com, m->base_inertia, o);
+  }
+  TDS_HD const double *base_inertia(const tds_model_t *m) const { return m->base_inertia; }
+  TDS_HD double stiffness(const tds_model_t *m, int i) const { return m->links[i].stiffness; }
+  TDS_HD double damping(const tds_model_t *m, int i) const { return m->links[i].damping; }
+  TDS_HD const double *gravity(const tds_model_t *m) const { return m->gravity; }
+  template <typename T>
+  TDS_HD T neg_gravity(const tds_model_t *m, int k) const { return T(-m->gravity[k]); }
+  TDS_HD double friction(const tds_model_t *m) const { return m->friction; }
+  TDS_HD double restitution(const tds_model_t *m) const { return m->restitution; }
+};
+
+// the rigid-body ABI of inertia.hpp:121-130 with T-typed mass, COM and inertia (tds_d_abi_rbi's expression order)
+template <typename T>
+TDS_HD inline void tds_d_abi_rbi_t(const T &mass, const T *com, const T *inertia, TdsDAbi<T> &o) {
+  const T z = T(0.0);
+  const T H[9] = {z, -com[2], com[1], com[2], z, -com[0], -com[1], com[0], z};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const T hh = H[3 * i] * H[3 * j] + H[3 * i + 1] * H[3 * j + 1] + H[3 * i + 2] * H[3 * j + 2];
+      o.I[3 * i + j] = inertia[3 * i + j] + hh * mass;
+      o.H[3 * i + j] = H[3 * i + j] * mass;
+      o.M[3 * i + j] = i == j ? mass : z;
+    }
+}
+
+template <typename T, class B>
+struct TdsParamOverlay {
+  T lxt[B::NL][3], lmass[B::NL], lcom[B::NL][3], linertia[B::NL][9], lstiff[B::NL], ldamp[B::NL];
+  T bmass, bcom[3], binertia[9], grav[3], fric, rest;
+};
+
+// the view of an overlay (a pointer to it, passed by value); the model argument is not read
+template <typename T, class B>
+struct TdsOverlayView {
+  const TdsParamOverlay<T, B> *o;
+  TDS_HD const T *xt(const tds_model_t *, int i) const { return o->lxt[i]; }
+  TDS_HD void link_rbi(const tds_model_t *, int i, TdsDAbi<T> &r) const {
+    tds_d_abi_rbi_t(o->lmass[i], o->lcom[i], o->linertia[i], r);
+  }
+  TDS_HD void base_rbi(const tds_model_t *, TdsDAbi<T> &r) const { tds_d_abi_rbi_t(o->bmass, o->bcom, o->binertia, r); }
+  TDS_HD const T *base_inertia(const tds_model_t *) const { return o->binertia; }
+  TDS_HD const T &stiffness(const tds_model_t *, int i) const { return o->lstiff[i]; }
+  TDS_HD const T &damping(const tds_model_t *, int i) const { return o->ldamp[i]; }
+  TDS_HD const T *gravity(const tds_model_t *) const { return o->grav; }
+  template <typename U>
+  TDS_HD U neg_gravity(const tds_model_t *, int k) const { return -o->grav[k]; }
+  TDS_HD const T &friction(const tds_model_t *) const { return o->fric; }
+  TDS_HD const T &restitution(const tds_model_t *) const { return o->rest; }
+};
+
+// the overlay holds the blob's values, all constant
+template <typename T, class B>
+TDS_HD inline void tds_param_seed(const tds_model_t *m, TdsParamOverlay<T, B> &o) {
+  for (int i = 0; i < m->num_links; ++i) {
+    const tds_link_t &l = m->links[i];
+    for (int k = 0; k < 3; ++k) o.lxt[i][k] = T(l.X_T_trans[k]), o.lcom[i][k] = T(l.com[k]);
+    for (int k = 0; k < 9; ++k) o.linertia[i][k] = T(l.inertia[k]);
+    o.lmass[i] = T(l.mass), o.lstiff[i] = T(l.stiffness), o.ldamp[i] = T(l.damping);
+  }
+  o.bmass = T(m->base_mass);
+  for (int k = 0; k < 3; ++k) o.bcom[k] = T(m->base_com[k]), o.grav[k] = T(m->gravity[k]);
+  for (int k = 0; k < 9; ++k) o.binertia[k] = T(m->base_inertia[k]);
+  o.fric = T(m->friction), o.rest = T(m->restitution);
+}
+
+// inertia entry `comp` (0..5 = xx, yy, zz, xy, xz, yz) of a row-major 3x3: its index and its mirror's
+TDS_HD inline int tds_param_inertia_index(int comp, int mirror) {
+  if (comp < 3) return 4 * comp;
+  const int r = comp == 5 ? 1 : 0, c = comp == 3 ? 1 : 2;
+  return mirror ? 3 * c + r : 3 * r + c;
+}
+
+// the overlay's entry (entries: an inertia entry and its mirror) of a selection; NULL for a kind it does not know
+template <typename T, class B>
+TDS_HD inline T *tds_param_slot(TdsParamOverlay<T, B> &o, const tds_param_t &q, int mirror) {
+  switch (q.kind) {
+    case TDS_PARAM_LINK_MASS: return &o.lmass[q.link];
+    case TDS_PARAM_LINK_COM: return &o.lcom[q.link][q.comp];
+    case TDS_PARAM_LINK_INERTIA: return &o.linertia[q.link][tds_param_inertia_index(q.comp, mirror)];
+    case TDS_PARAM_LINK_XT_TRANS: return &o.lxt[q.link][q.comp];
+    case TDS_PARAM_LINK_STIFFNESS: return &o.lstiff[q.link];
+    case TDS_PARAM_LINK_DAMPING: return &o.ldamp[q.link];
+    case TDS_PARAM_BASE_MASS: return &o.bmass;
+    case TDS_PARAM_BASE_COM: return &o.bcom[q.comp];
+    case TDS_PARAM_BASE_INERTIA: return &o.binertia[tds_param_inertia_index(q.comp, mirror)];
+    case TDS_PARAM_GRAVITY: return &o.grav[q.comp];
+    case TDS_PARAM_FRICTION: return &o.fric;
+    case TDS_PARAM_RESTITUTION: return &o.rest;
+    default: return nullptr;
+  }
+}
+
+// selected entry q := t (both mirror entries of an off-diagonal inertia entry: the inertia stays symmetric)
+template <typename T, class B>
+TDS_HD inline void tds_param_set(TdsParamOverlay<T, B> &o, const tds_param_t &q, const T &t) {
+  *tds_param_slot(o, q, 0) = t;
+  *tds_param_slot(o, q, 1) = t;
+}
+
+// the blob's value of a (checked) selection
+inline double tds_param_value(const tds_model_t *m, const tds_param_t &q) {
+  const tds_link_t &l = m->links[q.kind <= TDS_PARAM_LINK_DAMPING ? q.link : 0];
+  switch (q.kind) {
+    case TDS_PARAM_LINK_MASS: return l.mass;
+    case TDS_PARAM_LINK_COM: return l.com[q.comp];
+    case TDS_PARAM_LINK_INERTIA: return l.inertia[tds_param_inertia_index(q.comp, 0)];
+    case TDS_PARAM_LINK_XT_TRANS: return l.X_T_trans[q.comp];
+    case TDS_PARAM_LINK_STIFFNESS: return l.stiffness;
+    case TDS_PARAM_LINK_DAMPING: return l.damping;
+    case TDS_PARAM_BASE_MASS: return m->base_mass;
+    case TDS_PARAM_BASE_COM: return m->base_com[q.comp];
+    case TDS_PARAM_BASE_INERTIA: return m->base_inertia[tds_param_inertia_index(q.comp, 0)];
+    case TDS_PARAM_GRAVITY: return m->gravity[q.comp];
+    case TDS_PARAM_FRICTION: return m->friction;
+    default: return m->restitution;
+  }
+}
+
+// 0: the selection names p distinct scalars of the model; else why is set
+inline int tds_param_check(const tds_model_t *m, int p, const tds_param_t *params, const char **why) {
+  if (p < 0 || (p > 0 && !params)) return *why = "parameter derivatives: NULL or negative parameter selection", 1;
+  for (int j = 0; j < p; ++j) {
+    const tds_param_t &q = params[j];
+    if (q.kind < TDS_PARAM_LINK_MASS || q.kind > TDS_PARAM_RESTITUTION)
+      return *why = "parameter derivatives: unknown parameter kind", 1;
+    const bool on_link = q.kind <= TDS_PARAM_LINK_DAMPING;
+    const int ncomp = q.kind == TDS_PARAM_LINK_INERTIA || q.kind == TDS_PARAM_BASE_INERTIA ? 6
+                      : q.kind == TDS_PARAM_LINK_COM || q.kind == TDS_PARAM_LINK_XT_TRANS || q.kind == TDS_PARAM_BASE_COM ||
+                                q.kind == TDS_PARAM_GRAVITY
+                          ? 3
+                          : 1;
+    if (on_link ? (q.link < 0 || q.link >= m->num_links) : q.link != 0)
+      return *why = "parameter derivatives: link index out of range", 1;
+    if (q.comp < 0 || q.comp >= ncomp) return *why = "parameter derivatives: component index out of range", 1;
+    if (q.kind >= TDS_PARAM_BASE_MASS && q.kind <= TDS_PARAM_BASE_INERTIA && !m->is_floating)
+      return *why = "parameter derivatives: base parameters need a floating base", 1;
+    for (int i = 0; i < j; ++i)
+      if (params[i].kind == q.kind && params[i].link == q.link && params[i].comp == q.comp)
+        return *why = "parameter derivatives: duplicate parameter", 1;
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------- the step
 // ref: link.hpp:229-287 (X_J, X_parent) for a 1-DoF or fixed joint
-template <typename T>
-TDS_HD inline void tds_d_jcalc(const tds_link_t &l, const T &q, TdsDXf<T> &Xp) {
+template <typename T, typename X>
+TDS_HD inline void tds_d_jcalc(const tds_link_t &l, const X *xt, const T &q, TdsDXf<T> &Xp) {
   T R[9], tj[3] = {T(0.0), T(0.0), T(0.0)};
   for (int k = 0; k < 9; ++k) R[k] = T(k % 4 == 0 ? 1.0 : 0.0);
   switch (l.joint_type) {
@@ -381,13 +542,13 @@ TDS_HD inline void tds_d_jcalc(const tds_link_t &l, const T &q, TdsDXf<T> &Xp) {
   }
   // X_parent = X_T X_J (link.hpp:283)
   for (int k = 0; k < 3; ++k)
-    Xp.t[k] = l.X_T_trans[k] + (l.X_T_rot[3 * k] * tj[0] + l.X_T_rot[3 * k + 1] * tj[1] + l.X_T_rot[3 * k + 2] * tj[2]);
+    Xp.t[k] = xt[k] + (l.X_T_rot[3 * k] * tj[0] + l.X_T_rot[3 * k + 1] * tj[1] + l.X_T_rot[3 * k + 2] * tj[2]);
   tds_d_mul(l.X_T_rot, R, Xp.r);
 }
 
 // ref: dynamics/kinematics.hpp:18-148 (fixed and floating base); have_qd = 0: the mass matrix's call (v = 0)
-template <typename T, class B>
-TDS_HD inline void tds_d_kinematics(const tds_model_t *m, TdsDiffWork<T, B> &w, int have_qd) {
+template <typename T, class B, class P>
+TDS_HD inline void tds_d_kinematics(const tds_model_t *m, P p, TdsDiffWork<T, B> &w, int have_qd) {
   if (m->is_floating) {  // :35-62
     tds_d_quat_to_matrix(w.q, w.base.r);
     for (int k = 0; k < 3; ++k) {
@@ -395,10 +556,10 @@ TDS_HD inline void tds_d_kinematics(const tds_model_t *m, TdsDiffWork<T, B> &w, 
       w.base_v.a[k] = have_qd ? w.qd[k] : T(0.0);
       w.base_v.l[k] = have_qd ? w.qd[3 + k] : T(0.0);
     }
-    tds_d_abi_rbi(m->base_mass, m->base_com, m->base_inertia, w.base_abi);  // :50
+    p.base_rbi(m, w.base_abi);  // :50
     // :52-59 gyroscopic force with the world inertia R I R^T and the base angular velocity (frames as the reference has them)
     T RI[9], Iw[9], Iwv[3];
-    tds_d_mul(w.base.r, m->base_inertia, RI);
+    tds_d_mul(w.base.r, p.base_inertia(m), RI);
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) Iw[3 * i + j] = RI[3 * i] * w.base.r[3 * j] + RI[3 * i + 1] * w.base.r[3 * j + 1] + RI[3 * i + 2] * w.base.r[3 * j + 2];
     tds_d_mulv(Iw, w.base_v.a, Iwv);
@@ -412,7 +573,7 @@ TDS_HD inline void tds_d_kinematics(const tds_model_t *m, TdsDiffWork<T, B> &w, 
     const tds_link_t &l = m->links[i];
     const T q = l.q_index >= 0 ? w.q[l.q_index] : T(0.0);  // multi_body.hpp:490-500
     const T qd = (have_qd && l.qd_index >= 0) ? w.qd[l.qd_index] : T(0.0);
-    tds_d_jcalc(l, q, w.Xp[i]);
+    tds_d_jcalc(l, p.xt(m, i), q, w.Xp[i]);
     TdsDSv<T> vJ;  // link.hpp:289-329: S qd
     for (int k = 0; k < 3; ++k) vJ.a[k] = l.S[k] * qd, vJ.l[k] = l.S[3 + k] * qd;
     const TdsDXf<T> &Xpar = l.parent >= 0 ? w.Xw[l.parent] : w.base;
@@ -425,7 +586,7 @@ TDS_HD inline void tds_d_kinematics(const tds_model_t *m, TdsDiffWork<T, B> &w, 
       w.v[i] = vJ;
     }
     tds_d_cross_mm(w.v[i], vJ, w.c[i]);  // :96-97
-    tds_d_abi_rbi(l.mass, l.com, l.inertia, w.abi[i]);  // :99
+    p.link_rbi(m, i, w.abi[i]);  // :99
     TdsDSv<T> Iv;
     tds_d_abi_mul(w.abi[i], w.v[i], Iv);
     tds_d_cross_mf(w.v[i], Iv, w.pA[i]);  // :132
@@ -433,17 +594,17 @@ TDS_HD inline void tds_d_kinematics(const tds_model_t *m, TdsDiffWork<T, B> &w, 
 }
 
 // ref: dynamics/forward_dynamics.hpp:11-326 (ABA)
-template <typename T, class B>
-TDS_HD inline void tds_d_forward_dynamics(const tds_model_t *m, TdsDiffWork<T, B> &w) {
-  tds_d_kinematics(m, w, 1);
+template <typename T, class B, class P>
+TDS_HD inline void tds_d_forward_dynamics(const tds_model_t *m, P p, TdsDiffWork<T, B> &w) {
+  tds_d_kinematics(m, p, w, 1);
   for (int i = m->num_links - 1; i >= 0; --i) {
     const tds_link_t &l = m->links[i];
     tds_d_abi_mulc(w.abi[i], l.S, w.U[i]);  // :111
     w.D[i] = tds_d_dot6c(l.S, w.U[i]);      // :115
     T tau = l.joint_type != TDS_JOINT_FIXED ? w.tau[l.qd_index] : T(0.0);  // multi_body.hpp:557-570
     const T qv = l.q_index >= 0 ? w.q[l.q_index] : T(0.0), qdv = l.qd_index >= 0 ? w.qd[l.qd_index] : T(0.0);
-    tau = tau - l.stiffness * qv;  // :122
-    tau = tau - l.damping * qdv;   // :123
+    tau = tau - p.stiffness(m, i) * qv;  // :122
+    tau = tau - p.damping(m, i) * qdv;   // :123
     w.u[i] = tau - tds_d_dot6c(l.S, w.pA[i]);  // :129
     const T invD = l.joint_type == TDS_JOINT_FIXED ? T(0.0) : 1.0 / w.D[i];  // :153
     if (l.parent < 0 && !m->is_floating) continue;
@@ -474,7 +635,7 @@ TDS_HD inline void tds_d_forward_dynamics(const tds_model_t *m, TdsDiffWork<T, B
     tds_d_abi_inv_mul(w.base_abi, w.base_bias, r);
     for (int k = 0; k < 3; ++k) a_base.a[k] = -r.a[k], a_base.l[k] = -r.l[k];
   } else {  // :242  -spatial gravity
-    for (int k = 0; k < 3; ++k) a_base.a[k] = T(0.0), a_base.l[k] = T(-m->gravity[k]);
+    for (int k = 0; k < 3; ++k) a_base.a[k] = T(0.0), a_base.l[k] = p.template neg_gravity<T>(m, k);
   }
   for (int i = 0; i < m->num_links; ++i) {  // :245-302 (a_i into v_i: the velocities are not read any more)
     const tds_link_t &l = m->links[i];
@@ -489,16 +650,16 @@ TDS_HD inline void tds_d_forward_dynamics(const tds_model_t *m, TdsDiffWork<T, B
     }
   }
   if (m->is_floating)  // :315-319  gravity (world components) added to the base-frame acceleration
-    for (int k = 0; k < 3; ++k) w.qdd[k] = a_base.a[k], w.qdd[3 + k] = a_base.l[k] + m->gravity[k];
+    for (int k = 0; k < 3; ++k) w.qdd[k] = a_base.a[k], w.qdd[3 + k] = a_base.l[k] + p.gravity(m)[k];
 }
 
 // ref: dynamics/mass_matrix.hpp:13-127 (CRBA) followed by the Cholesky factor of tiny_matrix_x.h:240-345 into w.L.
 // Returns 0, or -1 where M is not positive definite (the reference's inverse fails: mb_constraint_solver.hpp:245-246)
-template <typename T, class B>
-TDS_HD inline int tds_d_mass_matrix(const tds_model_t *m, TdsDiffWork<T, B> &w) {
+template <typename T, class B, class P>
+TDS_HD inline int tds_d_mass_matrix(const tds_model_t *m, P p, TdsDiffWork<T, B> &w) {
   const int nd = m->dof_qd;
   T *M = w.L;  // assembled in place, then factored
-  tds_d_kinematics(m, w, 0);  // :37
+  tds_d_kinematics(m, p, w, 0);  // :37
   for (int k = 0; k < nd * nd; ++k) M[k] = T(0.0);
   for (int i = m->num_links - 1; i >= 0; --i) {
     const tds_link_t &l = m->links[i];
@@ -630,11 +791,11 @@ static inline TDS_HD void tds_d_plane_space(const double *n, double *p, double *
 }
 
 // ref: mb_constraint_solver.hpp:191-498 (mb_a = plane, mb_b = robot, keep_all_points_), PGS :101-142
-template <typename T, class B>
-TDS_HD inline int tds_d_resolve(const tds_model_t *m, TdsDiffWork<T, B> &w) {
+template <typename T, class B, class P>
+TDS_HD inline int tds_d_resolve(const tds_model_t *m, P p, TdsDiffWork<T, B> &w) {
   const int nc = w.n_c, nd = m->dof_qd, nr = 3 * nc;
   if (nc == 0 || nd == 0) return 0;
-  if (tds_d_mass_matrix(m, w)) return -1;  // :232-246
+  if (tds_d_mass_matrix(m, p, w)) return -1;  // :232-246
   double nrm[3] = {-m->plane_normal[0], -m->plane_normal[1], -m->plane_normal[2]}, f1[3], f2[3];
   tds_d_plane_space(nrm, f1, f2);  // :361
   for (int i = 0; i < nc; ++i) {
@@ -648,7 +809,7 @@ TDS_HD inline int tds_d_resolve(const tds_model_t *m, TdsDiffWork<T, B> &w) {
     }
     // rel_vel = -vel (:315); b rows (:321-325, :365-370), J rows (:300-307, :378-384); inactive contacts: zero rows
     const T nrv = -(nrm[0] * vel[0] + nrm[1] * vel[1] + nrm[2] * vel[2]);
-    w.b[i] = hit ? (-(1.0 + m->restitution) * nrv - m->erp * w.cp_dist[i] / m->dt) : T(0.0);
+    w.b[i] = hit ? (-(1.0 + p.restitution(m)) * nrv - m->erp * w.cp_dist[i] / m->dt) : T(0.0);
     w.b[nc + i] = hit ? (f1[0] * vel[0] + f1[1] * vel[1] + f1[2] * vel[2]) : T(0.0);
     w.b[2 * nc + i] = hit ? (f2[0] * vel[0] + f2[1] * vel[1] + f2[2] * vel[2]) : T(0.0);
     for (int d = 0; d < nd; ++d) {
@@ -685,7 +846,7 @@ TDS_HD inline int tds_d_resolve(const tds_model_t *m, TdsDiffWork<T, B> &w) {
         x = tds_clamp(x, T(0.0), T(100000.0));
       } else {  // friction: +-mu max(p_normal, 0)
         const T pn = w.p[r % nc], sc = pn < 0.0 ? T(0.0) : pn;
-        const T lo = -m->friction * sc, hi = m->friction * sc;
+        const T lo = -p.friction(m) * sc, hi = p.friction(m) * sc;
         if (x < lo) x = lo;  // Algebra::max
         if (x > hi) x = hi;  // Algebra::min
       }
@@ -706,8 +867,9 @@ TDS_HD inline int tds_d_resolve(const tds_model_t *m, TdsDiffWork<T, B> &w) {
 // output_dim - tds_diff_ny(m) entries are zero and left to the caller.  ref: examples/environments/
 // locomotion_contact_simulation.h:151-304 (LOCOMOTION) and cartpole_environment.h:71-117 (TAU), world.hpp:293-366.
 // Returns 0, or -1 where the mass matrix is not positive definite.
-template <typename T, class B>
-TDS_HD inline int tds_diff_step(const tds_model_t *m, TdsDiffWork<T, B> &w, const T *x, T *y) {
+// The model's selectable parameters are read through the view p (TdsBlobView: the blob's values).
+template <typename T, class B, class P>
+TDS_HD inline int tds_diff_step_view(const tds_model_t *m, P p, TdsDiffWork<T, B> &w, const T *x, T *y) {
   const int nq = m->dof_q, nd = m->dof_qd;
   for (int i = 0; i < nq; ++i) w.q[i] = x[i];  // :154-159
   for (int i = 0; i < nd; ++i) w.qd[i] = x[nq + i], w.qdd[i] = T(0.0), w.tau[i] = T(0.0);
@@ -731,7 +893,7 @@ TDS_HD inline int tds_diff_step(const tds_model_t *m, TdsDiffWork<T, B> &w, cons
     const int off = m->is_floating ? 6 : 0;
     for (int i = 0; i < nd - off; ++i) w.tau[off + i] = x[nq + nd + i];
   }
-  tds_d_forward_dynamics(m, w);  // :261
+  tds_d_forward_dynamics(m, p, w);  // :261
   if (m->is_floating)  // integrate_euler_qdd (integrator.hpp:141-182)
     for (int k = 0; k < 6; ++k) w.qd[k] = w.qd[k] + w.qdd[k] * m->dt;
   for (int i = 0; i < m->num_links; ++i)
@@ -756,7 +918,7 @@ TDS_HD inline int tds_diff_step(const tds_model_t *m, TdsDiffWork<T, B> &w, cons
   }
   if (m->has_plane) {  // world.step (world.hpp:293-366)
     tds_d_contacts(m, w);
-    if (tds_d_resolve(m, w)) return -1;
+    if (tds_d_resolve(m, p, w)) return -1;
   }
   if (m->is_floating) {  // integrate_euler (integrator.hpp:23-89): quaternion += quat_velocity(q, omega, dt), normalised
     T *b = w.q;
@@ -780,4 +942,10 @@ TDS_HD inline int tds_diff_step(const tds_model_t *m, TdsDiffWork<T, B> &w, cons
   for (int i = 0; i < nd; ++i) y[nq + i] = w.qd[i];
   if (m->pack_visuals) y[j] = w.base.r[8];  // up . z (:301-303)
   return 0;
+}
+
+// the step with the blob's parameters (the plain instantiations: double, TdsDual<K>, TdsRev)
+template <typename T, class B>
+TDS_HD inline int tds_diff_step(const tds_model_t *m, TdsDiffWork<T, B> &w, const T *x, T *y) {
+  return tds_diff_step_view(m, TdsBlobView{}, w, x, y);
 }

@@ -1,0 +1,353 @@
+// tds_dparam.hip — parameter derivatives: the step derivatives in [x | theta] on gfx950, theta the model scalars a
+// selection tds_param_t[p] names (include/tds_hip.h), per environment.  C ABI tds_hip_params_get,
+// tds_hip_jvp_params, tds_hip_vjp_params and their host checkers.
+//
+// The step (tds_diff_step_view) reads the selectable parameters through a TdsParamOverlay: T-typed copies of the
+// blob's values, the selected entries replaced by active theta.  The overlay is part of the lane's work object, in the
+// handle's work buffer (a private-segment work object aborted on its first launch: DESIGN 7a).
+//   forward mode: one work item per (environment, block of K directions over [x | theta]), as tds_jvp.hip's kernel;
+//   reverse mode: the recording and sweep kernels of tds_vjp_kernels.h over TdsVjpParamLane: theta is variables
+//                 input_dim .. input_dim + p - 1, the tape starts after them.
+// With p = 0 the device entry points call the plain paths (tds_hip_jvp, tds_hip_vjp); k = 0 in forward mode computes
+// y at theta only, with the double step over an overlay of doubles (tds_param_y_kernel).
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "tds_vjp_kernels.h"
+
+namespace {
+
+// tape entries a lane may record in parameter mode, per class: the longest tape counted with every selectable
+// parameter of the model selected, over each model's tests/golden records and with every contact point active
+// (pendulum5_plane 14 248, ant 73 107, laikago_soft 70 352), plus 29 %, 18 % and 16 %
+template <class B>
+struct TdsVjpParamCap;
+template <>
+struct TdsVjpParamCap<TdsBoundS> { static constexpr int N = 18432; };
+template <>
+struct TdsVjpParamCap<TdsBoundA> { static constexpr int N = 86016; };
+template <>
+struct TdsVjpParamCap<TdsBoundL> { static constexpr int N = 81920; };
+
+constexpr int kHostK = 8;  // tangents per evaluation on the host
+
+// ---------------------------------------------------------------- forward mode
+// directions v[n][kdirs][input_dim + p] -> jv[n][kdirs][output_dim]; kdirs = 0: y only
+struct TdsJvpParamArgs {
+  const tds_model_t *m;
+  int n, kdirs, p;
+  const double *x, *theta, *v;
+  const tds_param_t *params;
+  double *y, *out;
+};
+
+template <class B, int K>
+struct TdsJvpParamLane {
+  TdsDual<K> x[B::NX], y[B::NY];
+  TdsParamOverlay<TdsDual<K>, B> P;
+  TdsDiffWork<TdsDual<K>, B> w;
+};
+
+// evaluate environment env with directions d0 .. d0 + K - 1 (those below kdirs); 0 or the step's -1
+template <class B, int K>
+TDS_HD inline int tds_jvp_param_eval(const TdsJvpParamArgs &a, TdsJvpParamLane<B, K> &L, int env, int d0) {
+  using D = TdsDual<K>;
+  const tds_model_t *m = a.m;
+  const int nin = m->input_dim, nall = nin + a.p;
+  const double *xe = a.x + (size_t)env * nin, *th = a.theta + (size_t)env * a.p;
+  for (int i = 0; i < nin; ++i) L.x[i] = D(xe[i]);
+  tds_param_seed(m, L.P);
+  for (int j = 0; j < a.p; ++j) tds_param_set(L.P, a.params[j], D(th[j]));
+  for (int k = 0; k < K && d0 + k < a.kdirs; ++k) {
+    const double *ve = a.v + ((size_t)env * a.kdirs + d0 + k) * nall;
+    for (int i = 0; i < nin; ++i) L.x[i].d[k] = ve[i];
+    for (int j = 0; j < a.p; ++j) {
+      tds_param_slot(L.P, a.params[j], 0)->d[k] = ve[nin + j];
+      tds_param_slot(L.P, a.params[j], 1)->d[k] = ve[nin + j];
+    }
+  }
+  return tds_diff_step_view(m, TdsOverlayView<D, B>{&L.P}, L.w, L.x, L.y);
+}
+
+// jv of the directions d0 .. of environment env; `bad`: NaN
+template <class B, int K>
+TDS_HD inline void tds_jvp_param_store(const TdsJvpParamArgs &a, const TdsJvpParamLane<B, K> &L, int env, int d0,
+                                       double bad) {
+  const int nout = a.m->output_dim, ny = tds_diff_ny(a.m);
+  for (int k = 0; k < K && d0 + k < a.kdirs; ++k) {
+    double *o = a.out + ((size_t)env * a.kdirs + d0 + k) * nout;
+    for (int i = 0; i < nout; ++i) o[i] = (i < ny ? L.y[i].d[k] : 0.0) + bad;
+  }
+}
+
+template <class B, int K>
+__global__ void __launch_bounds__(64) tds_jvp_param_kernel(TdsJvpParamArgs a, TdsJvpParamLane<B, K> *lanes,
+                                                           long long n_lanes) {
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n_lanes) return;
+  const int blocks = a.kdirs > 0 ? (a.kdirs + K - 1) / K : 1;
+  const long long items = (long long)a.n * blocks;
+  TdsJvpParamLane<B, K> &L = lanes[lane];
+  for (long long it = lane; it < items; it += n_lanes) {
+    const int env = (int)(it % a.n), blk = (int)(it / a.n);  // neighbouring lanes: neighbouring environments
+    const int rc = tds_jvp_param_eval<B, K>(a, L, env, blk * K);
+    const double bad = rc ? __builtin_nan("") : 0.0;  // M not positive definite: the environment's outputs are NaN
+    if (a.y && blk == 0) {
+      const int nout = a.m->output_dim, ny = tds_diff_ny(a.m);
+      double *ye = a.y + (size_t)env * nout;
+      for (int i = 0; i < nout; ++i) ye[i] = (i < ny ? L.y[i].v : 0.0) + bad;
+    }
+    tds_jvp_param_store<B, K>(a, L, env, blk * K, bad);
+  }
+}
+
+// bytes of the lanes' work objects of a launch over n environments x kdirs directions (kdirs = 0: one block)
+template <class B>
+size_t tds_jvp_param_ws_bytes(int n, int kdirs) {
+  return ((size_t)tds_jvp_lanes<B>(n, kdirs > 0 ? kdirs : 1) * sizeof(TdsJvpParamLane<B, TdsJvpK<B>::K>) + 255) &
+         ~(size_t)255;
+}
+
+template <class B>
+int tds_jvp_param_launch(tds_hip_sim *s, const TdsJvpParamArgs &a, void *ws) {
+  constexpr int K = TdsJvpK<B>::K;
+  const long long n_lanes = tds_jvp_lanes<B>(a.n, a.kdirs > 0 ? a.kdirs : 1);
+  const int threads = 64;
+  const unsigned blocks = (unsigned)((n_lanes + threads - 1) / threads);
+  hipLaunchKernelGGL((tds_jvp_param_kernel<B, K>), dim3(blocks), dim3(threads), 0, s->stream, a,
+                     (TdsJvpParamLane<B, K> *)ws, n_lanes);
+  TDS_HIP_TRY(hipGetLastError());
+  return TDS_OK;
+}
+
+// y only (k = 0): the double step over an overlay of doubles, a lane's work object (no tangents: about a third of the
+// dual lane's bytes)
+template <class B>
+struct TdsParamYLane {
+  double y[B::NY];
+  TdsParamOverlay<double, B> P;
+  TdsDiffWork<double, B> w;
+};
+
+// y of environment env into ye (NaN where M is not positive definite); 0 or the step's -1
+template <class B>
+TDS_HD inline int tds_param_y_eval(const TdsJvpParamArgs &a, TdsParamYLane<B> &L, int env, double *ye) {
+  const tds_model_t *m = a.m;
+  const int nout = m->output_dim, ny = tds_diff_ny(m);
+  tds_param_seed(m, L.P);
+  for (int j = 0; j < a.p; ++j) tds_param_set(L.P, a.params[j], a.theta[(size_t)env * a.p + j]);
+  const int rc = tds_diff_step_view(m, TdsOverlayView<double, B>{&L.P}, L.w, a.x + (size_t)env * m->input_dim, L.y);
+  const double bad = rc ? __builtin_nan("") : 0.0;
+  for (int i = 0; i < nout; ++i) ye[i] = (i < ny ? L.y[i] : 0.0) + bad;
+  return rc;
+}
+
+// one lane per environment, at most kJvpLanes lanes walking the environments with the grid's stride
+template <class B>
+__global__ void __launch_bounds__(64) tds_param_y_kernel(TdsJvpParamArgs a, TdsParamYLane<B> *lanes, long long n_lanes) {
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n_lanes) return;
+  for (long long env = lane; env < a.n; env += n_lanes)
+    tds_param_y_eval<B>(a, lanes[lane], (int)env, a.y + (size_t)env * a.m->output_dim);
+}
+
+long long tds_param_y_lanes(int n) { return n < kJvpLanes ? n : kJvpLanes; }
+
+template <class B>
+size_t tds_param_y_ws_bytes(int n) {
+  return ((size_t)tds_param_y_lanes(n) * sizeof(TdsParamYLane<B>) + 255) & ~(size_t)255;
+}
+
+template <class B>
+int tds_param_y_launch(tds_hip_sim *s, const TdsJvpParamArgs &a, void *ws) {
+  const long long n_lanes = tds_param_y_lanes(a.n);
+  const unsigned blocks = (unsigned)((n_lanes + 63) / 64);
+  hipLaunchKernelGGL((tds_param_y_kernel<B>), dim3(blocks), dim3(64), 0, s->stream, a, (TdsParamYLane<B> *)ws, n_lanes);
+  TDS_HIP_TRY(hipGetLastError());
+  return TDS_OK;
+}
+
+// the host instantiation: y from the double step over an overlay of doubles, jv from TdsDual<kHostK>
+template <class B>
+int tds_jvp_param_host_impl(const TdsJvpParamArgs &a) {
+  const int nout = a.m->output_dim;
+  std::vector<TdsJvpParamLane<B, kHostK>> L(1);
+  std::vector<TdsParamYLane<B>> Ly(1);
+  int bad = 0;
+  for (int e = 0; e < a.n; ++e) {
+    if (a.y) bad |= tds_param_y_eval<B>(a, Ly[0], e, a.y + (size_t)e * nout) != 0;
+    for (int d0 = 0; d0 < a.kdirs; d0 += kHostK) {
+      const int rc = tds_jvp_param_eval<B, kHostK>(a, L[0], e, d0);
+      bad |= rc != 0;
+      tds_jvp_param_store<B, kHostK>(a, L[0], e, d0, rc ? __builtin_nan("") : 0.0);
+    }
+  }
+  return bad ? fail(TDS_ERR_INVALID_ARG, "step Jacobians: joint-space inertia not positive definite%s") : TDS_OK;
+}
+
+// ---------------------------------------------------------------- reverse mode
+struct TdsVjpParamArgs : TdsVjpArgs {
+  int p;
+  const tds_param_t *params;
+  const double *theta;
+};
+
+// a lane's work object in parameter mode: the record, the overlay and the step's state in TdsRev form
+template <class B>
+struct TdsVjpParamLane {
+  static constexpr int cap = TdsVjpParamCap<B>::N;
+  TdsRev x[B::NX], y[B::NY];
+  TdsParamOverlay<TdsRev, B> P;
+  TdsDiffWork<TdsRev, B> w;
+  TDS_HD static int n_extra(const TdsVjpParamArgs &a) { return a.p; }
+  // x: variables 0 .. input_dim - 1, theta: input_dim .. input_dim + p - 1
+  TDS_HD int record(const TdsVjpParamArgs &a, long long env) {
+    const tds_model_t *m = a.m;
+    const int nin = m->input_dim;
+    const double *xe = a.x + env * nin, *th = a.theta + env * a.p;
+    for (int i = 0; i < nin; ++i) x[i] = TdsRev(xe[i], i);
+    tds_param_seed(m, P);
+    for (int j = 0; j < a.p; ++j) tds_param_set(P, a.params[j], TdsRev(th[j], nin + j));
+    tds_rev_cursor(tds_rev_lane()) = 0;
+    return tds_diff_step_view(m, TdsOverlayView<TdsRev, B>{&P}, w, x, y);
+  }
+};
+
+template <class B>
+int tds_vjp_param_launch(tds_hip_sim *s, TdsVjpParamArgs a, const tds_param_t *params_host) {
+  const long long n_lanes = tds_vjp_lanes(a.n);
+  const size_t sel = (size_t)a.p * sizeof(tds_param_t);
+  const TdsVjpLayout<TdsVjpParamLane<B>> lay(n_lanes, s->model.input_dim + a.p, sel);
+  int rc = tds_jvp_tmp(s, lay.total);
+  if (rc) return rc;
+  // the selection after the overflow flag's slot, copied with a blocking copy: earlier calls on the stream may still
+  // read the work buffer
+  tds_param_t *d_sel = (tds_param_t *)((char *)s->d_diff_tmp + 256);
+  TDS_HIP_TRY(hipStreamSynchronize(s->stream));
+  TDS_HIP_TRY(hipMemcpy(d_sel, params_host, sel, hipMemcpyHostToDevice));
+  a.params = d_sel;
+  return tds_vjp_run(s, a, lay, n_lanes);
+}
+
+// ---------------------------------------------------------------- checks shared by the entry points
+int tds_param_check_sel(const tds_model_t *m, int p, const tds_param_t *params) {
+  const char *why = "";
+  if (tds_param_check(m, p, params, &why)) return fail(TDS_ERR_INVALID_ARG, "%s", why);
+  return TDS_OK;
+}
+
+// the host entry points' model checks: class (refusals as for the Jacobians), blob indices, selection
+int tds_param_host_prepare(const tds_model_t *m, int p, const tds_param_t *params, int *cls) {
+  const char *why = "";
+  *cls = tds_jvp_pick(m, &why);
+  if (*cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
+  const int rc = tds_hip_model_check(m);
+  if (rc) return rc;
+  return tds_param_check_sel(m, p, params);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tds_hip_params_get(const tds_model_t *model, int p, const tds_param_t *params, double *theta) {
+  if (!model || (p > 0 && !theta)) return fail(TDS_ERR_INVALID_ARG, "tds_hip_params_get: NULL argument%s");
+  int rc = tds_hip_model_check(model);
+  if (rc) return rc;
+  if ((rc = tds_param_check_sel(model, p, params))) return rc;
+  for (int j = 0; j < p; ++j) theta[j] = tds_param_value(model, params[j]);
+  return TDS_OK;
+}
+
+int tds_hip_jvp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const tds_param_t *params_host,
+                       const void *theta_dev, int k, const void *v_dev, void *y_dev, void *jv_dev) {
+  if (!s || !x_dev || n < 1 || k < 0 || p < 0 || (p > 0 && (!params_host || !theta_dev)) ||
+      (k > 0 && (!v_dev || !jv_dev)) || (k == 0 && !y_dev))
+    return fail(TDS_ERR_INVALID_ARG, "tds_hip_jvp_params: NULL or empty argument%s");
+  if (p == 0 && k > 0) return tds_hip_jvp(s, n, x_dev, k, v_dev, y_dev, jv_dev);  // the plain path
+  DeviceGuard guard(s->device);
+  int cls, rc = tds_jvp_prepare(s, &cls);
+  if (rc) return rc;
+  if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
+  // work buffer: the lanes' work objects (k = 0: of the double step) | the selection
+  size_t ws;
+  switch (cls) {
+    case 0: ws = k ? tds_jvp_param_ws_bytes<TdsBoundS>(n, k) : tds_param_y_ws_bytes<TdsBoundS>(n); break;
+    case 1: ws = k ? tds_jvp_param_ws_bytes<TdsBoundA>(n, k) : tds_param_y_ws_bytes<TdsBoundA>(n); break;
+    default: ws = k ? tds_jvp_param_ws_bytes<TdsBoundL>(n, k) : tds_param_y_ws_bytes<TdsBoundL>(n); break;
+  }
+  const size_t sel = (size_t)p * sizeof(tds_param_t);
+  if ((rc = tds_jvp_tmp(s, ws + sel))) return rc;
+  tds_param_t *d_sel = (tds_param_t *)((char *)s->d_diff_tmp + ws);
+  if (p > 0) {  // a blocking copy: earlier calls on the stream may still read the work buffer
+    TDS_HIP_TRY(hipStreamSynchronize(s->stream));
+    TDS_HIP_TRY(hipMemcpy(d_sel, params_host, sel, hipMemcpyHostToDevice));
+  }
+  const TdsJvpParamArgs a = {(const tds_model_t *)s->d_diff_model, n, k, p, (const double *)x_dev,
+                             (const double *)theta_dev, (const double *)v_dev, d_sel, (double *)y_dev,
+                             (double *)jv_dev};
+  if (k == 0) switch (cls) {  // y only: the double step
+      case 0: return tds_param_y_launch<TdsBoundS>(s, a, s->d_diff_tmp);
+      case 1: return tds_param_y_launch<TdsBoundA>(s, a, s->d_diff_tmp);
+      default: return tds_param_y_launch<TdsBoundL>(s, a, s->d_diff_tmp);
+    }
+  switch (cls) {
+    case 0: return tds_jvp_param_launch<TdsBoundS>(s, a, s->d_diff_tmp);
+    case 1: return tds_jvp_param_launch<TdsBoundA>(s, a, s->d_diff_tmp);
+    default: return tds_jvp_param_launch<TdsBoundL>(s, a, s->d_diff_tmp);
+  }
+}
+
+int tds_hip_vjp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const tds_param_t *params_host,
+                       const void *theta_dev, int k, const void *w_dev, void *y_dev, void *wj_dev) {
+  if (!s || !x_dev || !w_dev || !wj_dev || n < 1 || k < 1 || p < 0 || (p > 0 && (!params_host || !theta_dev)))
+    return fail(TDS_ERR_INVALID_ARG, "tds_hip_vjp_params: NULL or empty argument%s");
+  if (p == 0) return tds_hip_vjp(s, n, x_dev, k, w_dev, y_dev, wj_dev);  // the plain path
+  DeviceGuard guard(s->device);
+  int cls, rc = tds_jvp_prepare(s, &cls);
+  if (rc) return rc;
+  if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
+  TdsVjpParamArgs a;
+  static_cast<TdsVjpArgs &>(a) = {(const tds_model_t *)s->d_diff_model, n, k, (const double *)x_dev,
+                                  (const double *)w_dev, (double *)y_dev, (double *)wj_dev, nullptr};
+  a.p = p, a.params = nullptr, a.theta = (const double *)theta_dev;
+  switch (cls) {
+    case 0: return tds_vjp_param_launch<TdsBoundS>(s, a, params_host);
+    case 1: return tds_vjp_param_launch<TdsBoundA>(s, a, params_host);
+    default: return tds_vjp_param_launch<TdsBoundL>(s, a, params_host);
+  }
+}
+
+int tds_hip_jvp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
+                            const double *theta, int k, const double *v, double *y, double *jv) {
+  if (!model || !x || n < 1 || k < 0 || p < 0 || (p > 0 && (!params || !theta)) || (k > 0 && (!v || !jv)) ||
+      (k == 0 && !y))
+    return fail(TDS_ERR_INVALID_ARG, "tds_hip_jvp_params_host: NULL or empty argument%s");
+  int cls, rc = tds_param_host_prepare(model, p, params, &cls);
+  if (rc) return rc;
+  const TdsJvpParamArgs a = {model, n, k, p, x, theta, v, params, y, jv};
+  switch (cls) {
+    case 0: return tds_jvp_param_host_impl<TdsBoundS>(a);
+    case 1: return tds_jvp_param_host_impl<TdsBoundA>(a);
+    default: return tds_jvp_param_host_impl<TdsBoundL>(a);
+  }
+}
+
+int tds_hip_vjp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
+                            const double *theta, int k, const double *w, double *y, double *wj, int tape_cap,
+                            int *tape_len) {
+  if (!model || !x || !w || !wj || n < 1 || k < 1 || p < 0 || (p > 0 && (!params || !theta)))
+    return fail(TDS_ERR_INVALID_ARG, "tds_hip_vjp_params_host: NULL or empty argument%s");
+  int cls, rc = tds_param_host_prepare(model, p, params, &cls);
+  if (rc) return rc;
+  TdsVjpParamArgs a;
+  static_cast<TdsVjpArgs &>(a) = {model, n, k, x, w, y, wj, nullptr};
+  a.p = p, a.params = params, a.theta = theta;
+  switch (cls) {
+    case 0: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundS>>(a, tape_cap, tape_len);
+    case 1: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundA>>(a, tape_cap, tape_len);
+    default: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundL>>(a, tape_cap, tape_len);
+  }
+}
+
+}  // extern "C"

@@ -19,15 +19,6 @@ using namespace tds_internal;
 
 namespace {
 
-// tangents per lane of each class on the device (the lane's work object grows with K + 1)
-template <class B>
-struct TdsJvpK;
-template <>
-struct TdsJvpK<TdsBoundS> { static constexpr int K = 4; };
-template <>
-struct TdsJvpK<TdsBoundA> { static constexpr int K = 2; };
-template <>
-struct TdsJvpK<TdsBoundL> { static constexpr int K = 2; };
 constexpr int kHostK = 8;  // tangents per evaluation on the host
 
 // What a launch computes.  JVP: directions v[n][kdirs][input_dim], out = jv[n][kdirs][output_dim].  Jacobian: unit
@@ -93,11 +84,6 @@ __device__ inline void tds_jvp_item(const TdsJvpArgs &a, TdsJvpLane<B, K> &L, lo
 }
 
 
-// lanes of one launch: each walks the (environment, direction block) items with the grid's stride.  The cap bounds the
-// work buffer (kJvpLanes work objects: 0.9 - 1.2 GB); it also leaves three of four SIMDs without a wave at the kernel's
-// occupancy of one
-constexpr long long kJvpLanes = 16384;
-
 template <class B, int K>
 __global__ void __launch_bounds__(64) tds_jvp_kernel(TdsJvpArgs a, TdsJvpLane<B, K> *lanes, long long n_lanes) {
   const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -113,14 +99,6 @@ __global__ void tds_jac_accumulate(const double *per_env, int n, long long len, 
   double s = per_env[j];
   for (int i = 1; i < n; ++i) s += per_env[(size_t)i * len + j];
   out[j] = mean ? s / n : s;
-}
-
-// lanes of a launch over n environments x kdirs directions: one per item, at most kJvpLanes
-template <class B>
-long long tds_jvp_lanes(int n, int kdirs) {
-  constexpr int K = TdsJvpK<B>::K;
-  const long long items = (long long)n * ((kdirs + K - 1) / K);
-  return items < kJvpLanes ? items : kJvpLanes;
 }
 
 // bytes of the lanes' work objects of such a launch

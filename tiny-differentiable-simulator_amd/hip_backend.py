@@ -120,8 +120,67 @@ def lib():
         L.tds_hip_vjp_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tds_hip_vjp_host_tape.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_void_p]
+        PP = C.POINTER(Param)
+        L.tds_hip_params_get.argtypes = [P, C.c_int, PP, C.c_void_p]
+        L.tds_hip_jvp_params.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PP] + [C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 3
+        L.tds_hip_vjp_params.argtypes = L.tds_hip_jvp_params.argtypes
+        L.tds_hip_jvp_params_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 3
+        L.tds_hip_vjp_params_host.argtypes = L.tds_hip_jvp_params_host.argtypes + [C.c_int, C.c_void_p]
         _lib = L
     return _lib
+
+
+class Param(C.Structure):
+    """tds_param_t (include/tds_hip.h): one selected model scalar"""
+    _fields_ = [("kind", C.c_int32), ("link", C.c_int32), ("comp", C.c_int32), ("pad_", C.c_int32)]
+
+
+# parameter kinds (TDS_PARAM_*): name -> (code, on a link, number of components)
+PARAM_KINDS = {
+    "mass": (0, True, 1), "com": (1, True, 3), "inertia": (2, True, 6), "xt_trans": (3, True, 3),
+    "stiffness": (4, True, 1), "damping": (5, True, 1), "base_mass": (6, False, 1), "base_com": (7, False, 3),
+    "base_inertia": (8, False, 6), "gravity": (9, False, 3), "friction": (10, False, 1), "restitution": (11, False, 1),
+}
+
+
+def param_spec(params):
+    """a parameter selection as a tds_param_t array: entries are tds_param_t, or tuples (kind name, link[, comp]) for
+    the link kinds and (kind name[, comp]) for the others, e.g. ("mass", 3), ("com", 3, 2), ("gravity", 2),
+    ("friction",).  Inertia comps 0..5 = xx, yy, zz, xy, xz, yz.  The library checks ranges and duplicates."""
+    if isinstance(params, C.Array) and params._type_ is Param:
+        return params
+    out = (Param * max(len(params), 1))()
+    for j, q in enumerate(params):
+        if isinstance(q, Param):
+            out[j] = q
+            continue
+        name, rest = q[0], list(q[1:])
+        if name not in PARAM_KINDS:
+            raise ValueError(f"unknown parameter kind {name!r} (one of {', '.join(PARAM_KINDS)})")
+        code, on_link, nc = PARAM_KINDS[name]
+        if on_link and not rest:
+            raise ValueError(f"parameter {q!r}: kind {name!r} needs a link index")
+        link = rest.pop(0) if on_link else 0
+        comp = rest.pop(0) if rest else 0
+        if rest:
+            raise ValueError(f"parameter {q!r}: too many indices")
+        out[j] = Param(code, int(link), int(comp), 0)
+    return out
+
+
+def all_params(m: _model.Model):
+    """every selectable parameter of a model: per link mass, com, inertia, xt_trans, stiffness, damping; the base's
+    (floating base); gravity, friction, restitution"""
+    sel = []
+    for name, (_, on_link, nc) in PARAM_KINDS.items():
+        if name.startswith("base_") and not m.is_floating:
+            continue
+        for link in (range(m.num_links) if on_link else [None]):
+            for c in range(nc):
+                sel.append((name,) + ((link,) if on_link else ()) + ((c,) if nc > 1 else ()))
+    return sel
 
 
 class Rings(C.Structure):
@@ -156,6 +215,8 @@ EXPORTED_SYMBOLS = [
     "tds_hip_single_step_kernel",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
+    "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
+    "tds_hip_vjp_params_host",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step",
 ]
@@ -285,6 +346,91 @@ def vjp_host(m: _model.Model, x, w, want_y: bool = False, tape_cap: int = 0, tap
     _check(lib().tds_hip_vjp_host_tape(C.byref(m), n, x.ctypes.data, k, w3.ctypes.data,
                                        y.ctypes.data if want_y else None, wj.ctypes.data, int(tape_cap),
                                        lens.ctypes.data if tape_len else None))
+    out = (wj[:, 0] if squeeze else wj,)
+    if want_y:
+        out += (y,)
+    if tape_len:
+        out += (lens,)
+    return out if len(out) > 1 else out[0]
+
+
+def params_get(m: _model.Model, params):
+    """theta [p]: the model blob's values of a parameter selection (tds_hip_params_get; checks the selection)"""
+    import numpy as np
+
+    sel = param_spec(params)
+    p = len(params)
+    theta = np.zeros(max(p, 1), dtype=np.float64)
+    _check(lib().tds_hip_params_get(C.byref(m), p, sel, theta.ctypes.data))
+    return theta[:p]
+
+
+def _theta_rows(theta, n, p):
+    """theta [p] (every environment) or [n, p] as a contiguous [n, p] float64 array"""
+    import numpy as np
+
+    t = np.asarray(theta, dtype=np.float64)
+    if t.ndim == 1:
+        t = np.broadcast_to(t, (n, t.shape[0]))
+    if t.shape != (n, p):
+        raise ValueError(f"theta: expected [{p}] or [{n}, {p}], got {tuple(np.shape(theta))}")
+    return np.ascontiguousarray(t)
+
+
+def jvp_params_host(m: _model.Model, x, theta, params, v=None, want_y: bool = False):
+    """Forward mode in [x | theta] on the CPU (tds_hip_jvp_params_host; needs no GPU).
+
+    x [N, input_dim], theta [p] or [N, p] (the selected parameters' values), v [N, K, input_dim + p] or
+    [N, input_dim + p] (K = 1).  Returns jv = J v [N, K, output_dim] (or [N, output_dim]), with want_y also y
+    [N, output_dim]; v None: y alone."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x.shape[0], len(params)
+    sel = param_spec(params)
+    th = _theta_rows(theta, n, p)
+    y = np.zeros((n, m.output_dim), dtype=np.float64)
+    if v is None:
+        _check(lib().tds_hip_jvp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, 0, None,
+                                             y.ctypes.data, None))
+        return y
+    v = np.asarray(v, dtype=np.float64)
+    squeeze = v.ndim == 2
+    v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
+    if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != m.input_dim + p:
+        raise ValueError(f"v: expected [{n}, K, {m.input_dim + p}], got {tuple(v.shape)}")
+    k = v3.shape[1]
+    jv = np.zeros((n, k, m.output_dim), dtype=np.float64)
+    _check(lib().tds_hip_jvp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, k, v3.ctypes.data,
+                                         y.ctypes.data, jv.ctypes.data))
+    jv = jv[:, 0] if squeeze else jv
+    return (jv, y) if want_y else jv
+
+
+def vjp_params_host(m: _model.Model, x, theta, params, w, want_y: bool = False, tape_cap: int = 0,
+                    tape_len: bool = False):
+    """Reverse mode in [x | theta] on the CPU (tds_hip_vjp_params_host; needs no GPU).
+
+    x [N, input_dim], theta [p] or [N, p], w [N, K, output_dim] or [N, output_dim].  Returns wj = w^T J
+    [N, K, input_dim + p] (or [N, input_dim + p]), the x part first; want_y, tape_cap and tape_len as for vjp_host."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x.shape[0], len(params)
+    sel = param_spec(params)
+    th = _theta_rows(theta, n, p)
+    w = np.asarray(w, dtype=np.float64)
+    squeeze = w.ndim == 2
+    w3 = np.ascontiguousarray(w[:, None] if squeeze else w)
+    if w3.ndim != 3 or w3.shape[0] != n or w3.shape[2] != m.output_dim:
+        raise ValueError(f"w: expected [{n}, K, {m.output_dim}] or [{n}, {m.output_dim}], got {tuple(w.shape)}")
+    k = w3.shape[1]
+    wj = np.zeros((n, k, m.input_dim + p), dtype=np.float64)
+    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
+    lens = np.zeros(n, dtype=np.int32) if tape_len else None
+    _check(lib().tds_hip_vjp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, k, w3.ctypes.data,
+                                         y.ctypes.data if want_y else None, wj.ctypes.data, int(tape_cap),
+                                         lens.ctypes.data if tape_len else None))
     out = (wj[:, 0] if squeeze else wj,)
     if want_y:
         out += (y,)
@@ -622,6 +768,65 @@ class HipSim:
         _check(lib().tds_hip_vjp(self.h, n, C.c_void_p(x.data_ptr()), k, C.c_void_p(w3.data_ptr()),
                                  C.c_void_p(y.data_ptr()), C.c_void_p(wj.data_ptr())))
         return y, (wj[:, 0] if squeeze else wj)
+
+    # -- parameter derivatives: [x | theta], theta the selected model scalars per environment ---------------------
+    def _theta(self, theta, n, p):
+        import torch
+
+        assert theta.is_cuda and theta.dtype == torch.float64
+        if theta.dim() == 1:
+            theta = theta.unsqueeze(0).expand(n, p)
+        assert tuple(theta.shape) == (n, p), (tuple(theta.shape), n, p)
+        return theta.contiguous()
+
+    def jvp_params(self, x, theta, params, v=None):
+        """y = f(x; theta) [N, output_dim] (v None), else (y, jv): jv = J v [N, K, output_dim] for directions v
+        [N, K, input_dim + p] over [x | theta] (or [N, input_dim + p]: K = 1, jv [N, output_dim]).  theta [p] (every
+        environment) or [N, p], the values of the selection `params` (tuples or tds_param_t, see param_spec).  Any N;
+        f64 handles only (async)."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        x = x.contiguous()
+        n, p = x.shape[0], len(params)
+        sel = param_spec(params)
+        th = self._theta(theta, n, p)
+        y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
+        if v is None:
+            _check(lib().tds_hip_jvp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), 0,
+                                            None, C.c_void_p(y.data_ptr()), None))
+            return y
+        squeeze = v.dim() == 2
+        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
+        assert v3.is_cuda and v3.dtype == torch.float64 and tuple(v3.shape[::2]) == (n, self.input_dim + p)
+        k = v3.shape[1]
+        jv = torch.empty((n, k, self.output_dim), dtype=torch.float64, device=x.device)
+        _check(lib().tds_hip_jvp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), k,
+                                        C.c_void_p(v3.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(jv.data_ptr())))
+        return y, (jv[:, 0] if squeeze else jv)
+
+    def vjp_params(self, x, theta, params, w):
+        """(y, wj_x, wj_theta): y = f(x; theta) and w^T J split into its x part [N, (K,) input_dim] and its theta part
+        [N, (K,) p], for cotangents w [N, K, output_dim] (or [N, output_dim]: K = 1).  theta and params as for
+        jvp_params.  Reverse mode; the call waits for its kernels."""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        squeeze = w.dim() == 2
+        w3 = (w.unsqueeze(1) if squeeze else w).contiguous()
+        assert w3.is_cuda and w3.dtype == torch.float64 and w3.dim() == 3
+        assert tuple(w3.shape[::2]) == (x.shape[0], self.output_dim)
+        x = x.contiguous()
+        n, k, p = x.shape[0], w3.shape[1], len(params)
+        sel = param_spec(params)
+        th = self._theta(theta, n, p)
+        y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
+        wj = torch.empty((n, k, self.input_dim + p), dtype=torch.float64, device=x.device)
+        _check(lib().tds_hip_vjp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), k,
+                                        C.c_void_p(w3.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(wj.data_ptr())))
+        if squeeze:
+            wj = wj[:, 0]
+        return y, wj[..., :self.input_dim], wj[..., self.input_dim:]
 
     def step(self, actions=None, substeps: int = 1, obs=None):
         """Closed-loop step on the resident records (async): x[:, act] <- actions, y = f(x),
