@@ -855,6 +855,26 @@ int tds_rb_get_state(tds_rb_sim_t *sim, double *state_host);
 /* `steps` World::step calls on every world, one launch (async on the stream) */
 int tds_rb_step(tds_rb_sim_t *sim, int steps);
 
+/* Forward-mode derivatives of rollouts: s_T after `steps` World::steps from s0, and jv = (d s_T / d [s0 | theta]) v.
+   The derivative is that of the algorithm as executed (contact activation, the nrv / impulse tests, the friction clamp
+   and the lateral-speed test follow the primal's branch; quaternion entries raw).  theta [n][p] per world: the scalars a
+   selection params[p] names, of these kinds only: TDS_PARAM_LINK_MASS (link = body index, dynamic bodies; inv_mass =
+   1 / theta, the inverse inertia stays eye3), TDS_PARAM_GRAVITY (comp 0..2), TDS_PARAM_FRICTION, TDS_PARAM_RESTITUTION.
+   Any other kind, a body out of range, a static body's mass or a duplicate gives TDS_ERR_INVALID_ARG.
+   s0 [n][num_bodies][TDS_RB_STATE], v [n][k][num_bodies * TDS_RB_STATE + p] (columns in the order of the state, then
+   theta), sT [n][num_bodies][TDS_RB_STATE], jv [n][k][num_bodies * TDS_RB_STATE].  k = 0 computes sT only (v, jv may then
+   be NULL); with k > 0 sT may be NULL.  theta NULL: the model's values.  Any n >= 1, independent of num_worlds; the
+   handle's resident state is not touched.  Device pointers (params_host: host array), f64 handles only (an f32 handle
+   gives TDS_ERR_UNSUPPORTED); enqueued on the handle's stream.  Work buffer (kept by the handle, grown as needed):
+   num_bodies * 15 * 2 doubles per lane of a launch, min(n * ceil(k / 2), 262144) lanes. */
+int tds_rb_jvp(tds_rb_sim_t *sim, int n, int steps, const void *s0_dev, int p, const tds_param_t *params_host,
+               const void *theta_dev, int k, const void *v_dev, void *sT_dev, void *jv_dev);
+/* The same template on the CPU (host arrays, needs no GPU): the checker of tds_rb_jvp. */
+int tds_rb_jvp_host(const tds_rb_model_t *model, int n, int steps, const double *s0, int p, const tds_param_t *params,
+                    const double *theta, int k, const double *v, double *sT, double *jv);
+/* theta [p] = the model's values of the selection (host arrays); checks the selection. */
+int tds_rb_params_get(const tds_rb_model_t *model, int p, const tds_param_t *params, double *theta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,11 +8,15 @@ as executed (clamps, PGS projections and contact activation follow the branch th
 differentiated raw): see DESIGN.md, "Step Jacobians".
 
 ``param_step_fn(sim, params)(x, theta)`` is the step at the model parameters theta (the selection ``params``,
-hip_backend.param_spec), differentiable in x and theta: see DESIGN.md, "Parameter derivatives"."""
+hip_backend.param_spec), differentiable in x and theta: see DESIGN.md, "Parameter derivatives".
+
+``rb_rollout_fn(sim, steps, wrt, params)(s0, u, theta)`` is a rollout of a rigid-body world (RigidBodySim), differentiable
+in the state entries ``wrt`` (overwritten by u) and the parameters theta: see DESIGN.md, "Rigid-body rollouts"."""
 
 _StepFunction = None
 _StepFunctionReverse = None
 _ParamStepFunction = None
+_RbRolloutFunction = None
 
 
 def _function():
@@ -148,5 +152,82 @@ def param_step_fn(sim, params, mode: str = "reverse"):
 
     def f(x, theta):
         return fn.apply(x, theta, sim, spec, mode)
+
+    return f
+
+
+def _rb_rollout_function():
+    global _RbRolloutFunction
+    if _RbRolloutFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class RbRolloutFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, u, theta, s0, sim, steps, idx, dirs, params):
+                n, nb = s0.shape[0], sim.model.num_bodies
+                s = s0.detach().reshape(n, -1).clone()
+                s[:, idx] = u.detach().to(s.dtype)
+                s = s.reshape(n, nb, -1)
+                th = None if theta is None else theta.detach()
+                ctx.shared = th is not None and th.dim() == 1
+                ctx.has_theta = th is not None
+                if not any(ctx.needs_input_grad[:2]):
+                    return sim.jvp(s, None, steps, params, th)[0]
+                # only the len(wrt) + p columns that are needed: J [N, nb * 13, len(wrt) + p]
+                sT, jv = sim.jvp(s, dirs.expand(n, -1, -1), steps, params, th)
+                ctx.save_for_backward(jv.reshape(n, dirs.shape[0], -1))
+                ctx.nu = len(idx)
+                return sT
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_sT):
+                (jt,) = ctx.saved_tensors  # [N, len(wrt) + p, nb * 13] = J^T
+                n = jt.shape[0]
+                g = torch.bmm(jt, grad_sT.reshape(n, -1, 1).to(jt.dtype)).squeeze(2)
+                gu, gth = g[:, :ctx.nu], g[:, ctx.nu:]
+                if ctx.shared:
+                    gth = gth.sum(0)
+                return gu, (gth if ctx.has_theta else None), None, None, None, None, None, None
+
+        _RbRolloutFunction = RbRolloutFunction
+    return _RbRolloutFunction
+
+
+def rb_rollout_fn(sim, steps: int, wrt, params=()):
+    """(s0, u, theta=None) -> s_T: `steps` World::steps of a RigidBodySim (f64) from s0 [N, num_bodies, 13] with the
+    state entries wrt (a list of (body, comp), comp 0..12 of position | quaternion xyzw | linear | angular velocity)
+    overwritten by u [N, len(wrt)], differentiable in u and theta.
+
+    params: a selection of ("mass", body), ("gravity", comp), ("friction",), ("restitution",) (hip_backend.param_spec);
+    theta: None (the model's values), [p] shared by every world (its gradient is summed over them) or [N, p].  Where u
+    or theta requires grad, the forward pass computes the len(wrt) + p needed columns of d s_T / d [u | theta] with
+    RigidBodySim.jvp and backward is J^T grad.  s0 itself is not differentiated: s0.requires_grad raises."""
+    from . import hip_backend
+
+    nb = sim.model.num_bodies
+    p = len(params)
+    sel = hip_backend.param_spec(params)
+    spec = [sel[j] for j in range(p)]
+    idx = [b * 13 + c for b, c in wrt]
+    fn = _rb_rollout_function()
+    cache = {}
+
+    def f(s0, u, theta=None):
+        import torch
+
+        if s0.requires_grad:
+            raise ValueError("rb_rollout_fn: s0 is not differentiated (only the entries wrt, through u): detach s0 "
+                             "or list the entries in wrt")
+        if u.dim() != 2 or u.shape[1] != len(idx):
+            raise ValueError(f"rb_rollout_fn: u must be [N, {len(idx)}], got {tuple(u.shape)}")
+        if theta is not None and p == 0:
+            raise ValueError("rb_rollout_fn: theta given but no params selected")
+        key = str(s0.device)
+        if key not in cache:
+            cache[key] = hip_backend.rb_directions(nb, wrt, p, device=s0.device)
+        ix = torch.tensor(idx, dtype=torch.long, device=s0.device)
+        return fn.apply(u, theta, s0, sim, int(steps), ix, cache[key], spec)
 
     return f

@@ -13,7 +13,9 @@
 // scratch).  The contact list is not stored: body
 // poses do not change during the solver sweeps, so each sweep re-derives the contacts of a pair from
 // the poses — the same numbers the reference keeps in rb_contacts_.  Capsules and boxes collide as the
-// reference's sets of spheres (2 end spheres / 8 corner spheres placed by Pose * offset).
+// reference's sets of spheres (2 end spheres / 8 corner spheres placed by Pose * offset).  tds_rb_step.h states the
+// same step once more as a template over the scalar type, for the forward-mode derivatives (tds_rb_diff.hip); this
+// kernel keeps its own statement so that its f32 build stays bit-identical ("Rigid-body rollouts").
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "tds_hip.h"
+#include "tds_rb_internal.h"
 
 namespace {
 
@@ -31,45 +34,8 @@ int rb_fail(int code, const char *msg) {
   return code;
 }
 
-template <typename T>
-struct RbDev {
-  int nb, iters;
-  T dt, grav[3], restitution, friction, erp;
-  T mass[TDS_RB_MAX_BODIES], inv_mass[TDS_RB_MAX_BODIES], inv_in[TDS_RB_MAX_BODIES];
-  T radius[TDS_RB_MAX_BODIES];  // of the body's collision spheres (box: max(1e-2, corner radius))
-  T pn[TDS_RB_MAX_BODIES][3], pc[TDS_RB_MAX_BODIES];
-  int type[TDS_RB_MAX_BODIES];
-  int ns[TDS_RB_MAX_BODIES];    // collision spheres of the body: sphere 1, capsule 2, box 8 (plane 0)
-  T off[TDS_RB_MAX_BODIES][8][3];  // their centres in body coordinates
-};
-
-template <typename T>
-__device__ __forceinline__ void cross3(const T *a, const T *b, T *o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-template <typename T>
-__device__ __forceinline__ T dot3(const T *a, const T *b) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-// q v q^-1 for a unit quaternion (x, y, z, w) — tiny_quaternion.h:171-176
-template <typename T>
-__device__ __forceinline__ void quat_rotate(const T *q, const T *v, T *o) {
-  const T t0 = q[3] * v[0] + q[1] * v[2] - q[2] * v[1];
-  const T t1 = q[3] * v[1] + q[2] * v[0] - q[0] * v[2];
-  const T t2 = q[3] * v[2] + q[0] * v[1] - q[1] * v[0];
-  const T t3 = -q[0] * v[0] - q[1] * v[1] - q[2] * v[2];
-  const T i0 = -q[0], i1 = -q[1], i2 = -q[2], i3 = q[3];
-  o[0] = t3 * i0 + t0 * i3 + t1 * i2 - t2 * i1;
-  o[1] = t3 * i1 + t1 * i3 + t2 * i0 - t0 * i2;
-  o[2] = t3 * i2 + t2 * i3 + t0 * i1 - t1 * i0;
-}
-
 // LDS slot of (body b, component c) for this lane; c: 0..2 position, 3..5 linear, 6..8 angular velocity,
 // 9..12 orientation quaternion (x, y, z, w)
-#define RB_NC 13
 #define RB_AT(b, c) sm[((b)*RB_NC + (c)) * 64 + lane]
 
 template <typename T>
@@ -298,61 +264,9 @@ __global__ __launch_bounds__(64) void tds_rb_kernel(const RbDev<T> *__restrict__
   }
 }
 
-template <typename T>
-void rb_build(const tds_rb_model_t *m, RbDev<T> *d) {
-  memset(d, 0, sizeof(*d));
-  d->nb = m->num_bodies;
-  d->iters = m->solver_iterations;
-  d->dt = (T)m->dt;
-  for (int k = 0; k < 3; ++k) d->grav[k] = (T)m->gravity[k];
-  d->restitution = (T)m->restitution;
-  d->friction = (T)m->friction;
-  d->erp = (T)m->erp;
-  for (int i = 0; i < m->num_bodies; ++i) {
-    const tds_rb_body_t &b = m->bodies[i];
-    d->mass[i] = (T)b.mass;
-    d->inv_mass[i] = b.mass == 0.0 ? T(0) : (T)(1.0 / b.mass);  // rigid_body.hpp:49-53
-    d->inv_in[i] = b.mass == 0.0 ? T(0) : T(1);                  // zero33 / eye3
-    d->type[i] = b.geom_type;
-    double rad = b.radius;
-    if (b.geom_type == TDS_GEOM_SPHERE) {
-      d->ns[i] = 1;
-    } else if (b.geom_type == TDS_GEOM_CAPSULE) {  // contact_point.hpp:143-158
-      d->ns[i] = 2;
-      d->off[i][0][2] = (T)(0.5 * b.length);
-      d->off[i][1][2] = (T)(-0.5 * b.length);
-    } else if (b.geom_type == TDS_GEOM_BOX) {      // contact_point.hpp:179-196, geometry.hpp:244-259
-      d->ns[i] = 8;
-      rad = b.radius > 1e-2 ? b.radius : 1e-2;
-      const double dx = b.extents[0] * 0.5 - rad, dy = b.extents[1] * 0.5 - rad, dz = b.extents[2] * 0.5 - rad;
-      for (int c = 0; c < 8; ++c) {
-        d->off[i][c][0] = (T)((c & 4) ? -dx : dx);
-        d->off[i][c][1] = (T)((c & 2) ? -dy : dy);
-        d->off[i][c][2] = (T)((c & 1) ? -dz : dz);
-      }
-    }
-    d->radius[i] = (T)rad;
-    // Plane's constructor normalises the normal (geometry.hpp:163-168)
-    double nl = sqrt(b.plane_normal[0] * b.plane_normal[0] + b.plane_normal[1] * b.plane_normal[1] +
-                     b.plane_normal[2] * b.plane_normal[2]);
-    if (nl == 0.0) nl = 1.0;
-    for (int k = 0; k < 3; ++k) d->pn[i][k] = (T)(b.plane_normal[k] / nl);
-    d->pc[i] = (T)b.plane_constant;
-  }
-}
-
 }  // namespace
 
-struct tds_rb_sim {
-  tds_rb_model_t model;
-  int num_worlds = 0, device = 0, dtype = TDS_DTYPE_F64;
-  size_t elem = 8;
-  hipStream_t stream = nullptr;
-  void *d_state = nullptr, *d_model = nullptr;
-  RbDev<double> h64;
-  RbDev<float> h32;
-  std::vector<float> stage;
-};
+int tds_rb_fail(int code, const char *msg) { return rb_fail(code, msg); }
 
 #define RB_TRY(expr)                                                                       \
   do {                                                                                     \
@@ -421,6 +335,7 @@ int tds_rb_destroy(tds_rb_sim_t *s) {
   (void)hipSetDevice(s->device);
   (void)hipFree(s->d_state);
   (void)hipFree(s->d_model);
+  (void)hipFree(s->d_work);
   delete s;
   return TDS_OK;
 }

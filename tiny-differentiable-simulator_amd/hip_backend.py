@@ -128,6 +128,12 @@ def lib():
         L.tds_hip_jvp_params_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3
         L.tds_hip_vjp_params_host.argtypes = L.tds_hip_jvp_params_host.argtypes + [C.c_int, C.c_void_p]
+        RP = C.POINTER(_model.RbModel)
+        L.tds_rb_params_get.argtypes = [RP, C.c_int, PP, C.c_void_p]
+        L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 3
+        L.tds_rb_jvp_host.argtypes = [RP, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 3
         _lib = L
     return _lib
 
@@ -218,7 +224,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
     "tds_hip_vjp_params_host",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
-    "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step",
+    "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
 ]
 
 
@@ -437,6 +443,55 @@ def vjp_params_host(m: _model.Model, x, theta, params, w, want_y: bool = False, 
     if tape_len:
         out += (lens,)
     return out if len(out) > 1 else out[0]
+
+
+def _rb_check(rc):
+    if rc != TDS_OK:
+        raise TdsHipError(f"tds_rb error {rc}: {lib().tds_rb_last_error().decode()}")
+
+
+def rb_params_get(m: _model.RbModel, params):
+    """theta [p]: the rigid-body model's values of a parameter selection (tds_rb_params_get; checks the selection).
+    Kinds: ("mass", body), ("gravity", comp), ("friction",), ("restitution",)."""
+    import numpy as np
+
+    sel = param_spec(params)
+    p = len(params)
+    theta = np.zeros(max(p, 1), dtype=np.float64)
+    _rb_check(lib().tds_rb_params_get(C.byref(m), p, sel, theta.ctypes.data))
+    return theta[:p]
+
+
+def rb_jvp_host(m: _model.RbModel, s0, steps: int, v=None, params=(), theta=None):
+    """Forward-mode rollout derivative on the CPU (tds_rb_jvp_host; the checker of RigidBodySim.jvp, needs no GPU).
+
+    s0 [N, num_bodies, 13], v [N, K, num_bodies * 13 + p] (or [N, num_bodies * 13 + p]: K = 1), theta None (the model's
+    values), [p] or [N, p].  Returns s_T [N, num_bodies, 13] (v None) or (s_T, jv), jv [N, K, num_bodies, 13] (or
+    [N, num_bodies, 13])."""
+    import numpy as np
+
+    nb = m.num_bodies
+    ns = nb * _model.TDS_RB_STATE
+    s0 = np.ascontiguousarray(s0, dtype=np.float64).reshape(-1, nb, _model.TDS_RB_STATE)
+    n, p = s0.shape[0], len(params)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    thp = None if th is None else th.ctypes.data
+    sT = np.zeros_like(s0)
+    if v is None:
+        _rb_check(lib().tds_rb_jvp_host(C.byref(m), n, int(steps), s0.ctypes.data, p, sel, thp, 0, None,
+                                        sT.ctypes.data, None))
+        return sT
+    v = np.asarray(v, dtype=np.float64)
+    squeeze = v.ndim == 2
+    v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
+    if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != ns + p:
+        raise ValueError(f"v: expected [{n}, K, {ns + p}], got {tuple(v.shape)}")
+    k = v3.shape[1]
+    jv = np.zeros((n, k, nb, _model.TDS_RB_STATE), dtype=np.float64)
+    _rb_check(lib().tds_rb_jvp_host(C.byref(m), n, int(steps), s0.ctypes.data, p, sel, thp, k, v3.ctypes.data,
+                                    sT.ctypes.data, jv.ctypes.data))
+    return sT, (jv[:, 0] if squeeze else jv)
 
 
 def jacobian_tangents(m: _model.Model) -> int:
@@ -1148,6 +1203,56 @@ class RigidBodySim:
         self.state = HipSim._wrap(self, lib().tds_rb_state_device(self.h),
                                   (self.num_worlds, m.num_bodies, _model.TDS_RB_STATE))
 
+    def jvp(self, s0, v=None, steps: int = 1, params=(), theta=None):
+        """(s_T, jv): `steps` World::steps from s0 [N, num_bodies, 13] (any N) and jv = (d s_T / d [s0 | theta]) v
+        [N, K, num_bodies, 13] for directions v [N, K, num_bodies * 13 + p] (or [N, num_bodies * 13 + p]: K = 1, jv
+        [N, num_bodies, 13]); v None: jv None.  params: a selection of ("mass", body), ("gravity", comp), ("friction",),
+        ("restitution",) (hip_backend.param_spec); theta None (the model's values), [p] or [N, p].  The resident state
+        is not touched.  f64 handles only (async on the handle's stream)."""
+        import torch
+
+        nb = self.model.num_bodies
+        ns = nb * _model.TDS_RB_STATE
+        assert s0.is_cuda and s0.dtype == torch.float64
+        s0 = s0.reshape(-1, nb, _model.TDS_RB_STATE).contiguous()
+        n, p = s0.shape[0], len(params)
+        sel = param_spec(params)
+        th = None
+        if theta is not None:
+            assert theta.is_cuda and theta.dtype == torch.float64
+            th = (theta.unsqueeze(0).expand(n, p) if theta.dim() == 1 else theta).contiguous()
+            assert tuple(th.shape) == (n, p), (tuple(th.shape), n, p)
+        thp = None if th is None else C.c_void_p(th.data_ptr())
+        sT = torch.empty_like(s0)
+        if v is None:
+            _rb_check(lib().tds_rb_jvp(self.h, n, int(steps), C.c_void_p(s0.data_ptr()), p, sel, thp, 0, None,
+                                       C.c_void_p(sT.data_ptr()), None))
+            return sT, None
+        squeeze = v.dim() == 2
+        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
+        assert v3.is_cuda and v3.dtype == torch.float64 and v3.dim() == 3 and tuple(v3.shape[::2]) == (n, ns + p)
+        k = v3.shape[1]
+        jv = torch.empty((n, k, nb, _model.TDS_RB_STATE), dtype=torch.float64, device=s0.device)
+        if k > 0:
+            _rb_check(lib().tds_rb_jvp(self.h, n, int(steps), C.c_void_p(s0.data_ptr()), p, sel, thp, k,
+                                       C.c_void_p(v3.data_ptr()), C.c_void_p(sT.data_ptr()), C.c_void_p(jv.data_ptr())))
+        else:
+            sT = self.jvp(s0, None, steps, params, theta)[0]
+        return sT, (jv[:, 0] if squeeze else jv)
+
+    def jacobian(self, s0, steps: int, wrt, params=(), theta=None):
+        """dense d s_T / d [s0 entries wrt | theta]: [N, num_bodies * 13, len(wrt) + p] from unit directions.  wrt: a
+        list of (body, comp) entries of the state (comp 0..12: position, quaternion xyzw, linear, angular velocity)."""
+        import torch
+
+        nb = self.model.num_bodies
+        ns = nb * _model.TDS_RB_STATE
+        s0 = s0.reshape(-1, nb, _model.TDS_RB_STATE)
+        n, p = s0.shape[0], len(params)
+        v = rb_directions(nb, wrt, p, device=s0.device).expand(n, -1, -1)
+        _, jv = self.jvp(s0, v, steps, params, theta)
+        return jv.reshape(n, -1, ns).transpose(1, 2)
+
     def step(self, steps: int = 1):
         rc = lib().tds_rb_step(self.h, int(steps))
         if rc != TDS_OK:
@@ -1163,3 +1268,21 @@ class RigidBodySim:
             self.close()
         except Exception:
             pass
+
+
+def rb_directions(num_bodies: int, wrt, p: int = 0, device=None):
+    """unit directions [len(wrt) + p, num_bodies * 13 + p]: one per state entry (body, comp) of wrt, then one per
+    parameter"""
+    import torch
+
+    ns = num_bodies * _model.TDS_RB_STATE
+    cols = []
+    for b, c in wrt:
+        if not (0 <= b < num_bodies and 0 <= c < _model.TDS_RB_STATE):
+            raise ValueError(f"wrt entry {(b, c)} out of range ({num_bodies} bodies, {_model.TDS_RB_STATE} comps)")
+        cols.append(b * _model.TDS_RB_STATE + c)
+    cols += [ns + j for j in range(p)]
+    v = torch.zeros((len(cols), ns + p), dtype=torch.float64, device=device)
+    if cols:
+        v[torch.arange(len(cols)), torch.tensor(cols)] = 1.0
+    return v
