@@ -18,8 +18,8 @@
 namespace {
 
 // tape entries a lane may record in parameter mode, per class: the longest tape counted with every selectable
-// parameter of the model selected, over each model's tests/golden records and with every contact point active
-// (pendulum5_plane 14 248, ant 73 107, laikago_soft 70 352), plus 29 %, 18 % and 16 %
+// parameter of the model selected, over each model's tests/golden records and the contact sweep of
+// tests/diff_states.py (pendulum5_plane 14 248, ant 73 128, laikago 70 355), plus 29 %, 18 % and 16 %
 template <class B>
 struct TdsVjpParamCap;
 template <>

@@ -20,7 +20,7 @@
 namespace {
 
 // tape entries a lane may record, per class: the longest tape counted for the class's models (golden records, and
-// every contact point active), plus 18 - 28 %
+// the contact sweep of tests/diff_states.py, every reachable contact count), plus 18 - 28 %
 template <class B>
 struct TdsVjpCap;
 template <>
