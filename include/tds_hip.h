@@ -623,6 +623,34 @@ int tds_hip_vjp_params_host(const tds_model_t *model, int n, const double *x, in
                             const double *theta, int k, const double *w, double *y, double *wj, int tape_cap,
                             int *tape_len);
 
+/* Forward-mode derivatives of articulated-body trajectories: forward_zero chained over `steps` steps (the derivatives'
+   statement of the step, as tds_hip_jvp_params), the states s recorded after steps every, 2 every, .., steps, and
+   js = (d s / d [x0 | theta]) v.  Step 0 reads x0 [n][input_dim] as forward_zero reads it; step t >= 1 reads
+   [y_{t-1}'s q | qd | u[t-1] | x0's gains (LOCOMOTION: kp kd max_force)], u [n][steps - 1][n_act] with
+   n_act = input_dim - dof_q - dof_qd - (3 for LOCOMOTION, else 0); u NULL holds x0's action slots every step.  The
+   actions of u are inputs, not differentiated.  theta [n][p]: the scalars a selection params[p] names (kinds and checks
+   as tds_hip_jvp_params), for the whole trajectory; NULL: the model's values.  s [n][n_rec][dof_q + dof_qd] with
+   n_rec = steps / every, v [n][k][input_dim + p] (x0's columns, then theta's), js [n][k][n_rec][dof_q + dof_qd].
+   k = 0 computes s only (the double step; v, js may then be NULL); with k > 0 s may be NULL.  The derivative is that of
+   the algorithm as executed (the primal's branch at clamps, PGS projections, friction boxes and contact activation,
+   quaternions raw).  An environment whose joint-space inertia is not positive definite at some step gets NaN for that
+   record and every later one.  steps < 1, an `every` that does not divide steps or a bad selection gives
+   TDS_ERR_INVALID_ARG; scope and refusals are those of tds_hip_jacobian, f64 handles only.  Any n >= 1, independent of
+   num_envs; the handle's resident state is not touched.  Device pointers (params_host: host array); enqueued on the
+   handle's stream as launches of at most option traj_steps steps each (the host waits only where the work buffer grows
+   or the selection is copied).  Work buffer (shared with the step derivatives): min(n ceil(k / K), 16384) lane work
+   objects plus (dof_q + dof_qd) (K + 1) + 1 doubles per (environment, block of K directions), K of
+   tds_hip_jacobian_tangents (k = 0: K = 0). */
+int tds_hip_trajectory_jvp(tds_hip_sim_t *sim, int n, int steps, int every, const void *x0_dev, const void *u_dev,
+                           int p, const tds_param_t *params_host, const void *theta_dev, int k, const void *v_dev,
+                           void *s_dev, void *js_dev);
+/* The same per-step function on the CPU (host arrays, needs no GPU; s required): the checker of
+   tds_hip_trajectory_jvp.  Returns TDS_ERR_INVALID_ARG where some environment's inertia was not positive definite,
+   after writing every record. */
+int tds_hip_trajectory_jvp_host(const tds_model_t *model, int n, int steps, int every, const double *x0,
+                                const double *u, int p, const tds_param_t *params, const double *theta, int k,
+                                const double *v, double *s, double *js);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

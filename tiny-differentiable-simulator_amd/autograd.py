@@ -11,12 +11,17 @@ differentiated raw): see DESIGN.md, "Step Jacobians".
 hip_backend.param_spec), differentiable in x and theta: see DESIGN.md, "Parameter derivatives".
 
 ``rb_rollout_fn(sim, steps, wrt, params)(s0, u, theta)`` is a rollout of a rigid-body world (RigidBodySim), differentiable
-in the state entries ``wrt`` (overwritten by u) and the parameters theta: see DESIGN.md, "Rigid-body rollouts"."""
+in the state entries ``wrt`` (overwritten by u) and the parameters theta: see DESIGN.md, "Rigid-body rollouts".
+
+``trajectory_fn(sim, steps, wrt, params, every)(x0, z, theta, u)`` is an articulated-body trajectory (forward_zero
+chained), differentiable in the record entries ``wrt`` (overwritten by z) and the parameters theta: see DESIGN.md,
+"Articulated trajectories"."""
 
 _StepFunction = None
 _StepFunctionReverse = None
 _ParamStepFunction = None
 _RbRolloutFunction = None
+_TrajectoryFunction = None
 
 
 def _function():
@@ -229,5 +234,88 @@ def rb_rollout_fn(sim, steps: int, wrt, params=()):
             cache[key] = hip_backend.rb_directions(nb, wrt, p, device=s0.device)
         ix = torch.tensor(idx, dtype=torch.long, device=s0.device)
         return fn.apply(u, theta, s0, sim, int(steps), ix, cache[key], spec)
+
+    return f
+
+
+def _trajectory_function():
+    global _TrajectoryFunction
+    if _TrajectoryFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class TrajectoryFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, z, theta, x0, u, sim, steps, every, idx, dirs, params):
+                x = x0.detach().clone()
+                if z is not None:
+                    x[:, idx] = z.detach().to(x.dtype)
+                th = None if theta is None else theta.detach()
+                ud = None if u is None else u.detach()
+                ctx.shared = th is not None and th.dim() == 1
+                ctx.has_z, ctx.has_theta = z is not None, th is not None
+                if not any(ctx.needs_input_grad[:2]):
+                    return sim.trajectory_jvp(x, None, steps, every, ud, params, th)[0]
+                # only the len(wrt) + p columns that are needed: J^T [N, len(wrt) + p, n_rec (nq + nd)]
+                n = x.shape[0]
+                s, js = sim.trajectory_jvp(x, dirs.expand(n, -1, -1), steps, every, ud, params, th)
+                ctx.save_for_backward(js.reshape(n, dirs.shape[0], -1))
+                ctx.nz = len(idx)
+                return s
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_s):
+                (jt,) = ctx.saved_tensors
+                n = jt.shape[0]
+                g = torch.bmm(jt, grad_s.reshape(n, -1, 1).to(jt.dtype)).squeeze(2)
+                gz, gth = g[:, :ctx.nz], g[:, ctx.nz:]
+                if ctx.shared:  # one theta for every environment: its gradient sums over them
+                    gth = gth.sum(0)
+                return ((gz if ctx.has_z else None), (gth if ctx.has_theta else None)) + (None,) * 8
+
+        _TrajectoryFunction = TrajectoryFunction
+    return _TrajectoryFunction
+
+
+def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1):
+    """(x0, z=None, theta=None, u=None) -> s [N, n_rec, nq + nd]: the states after steps every, 2 every, .., steps of
+    forward_zero chained from x0 [N, input_dim] (a HipSim, f64), with x0's entries wrt (indices into its input_dim
+    entries) overwritten by z [N, len(wrt)], differentiable in z and theta.
+
+    params: the selection (hip_backend.param_spec); theta: None (the model's values), [p] shared by every environment
+    (its gradient is summed over them) or [N, p].  u: None (x0's actions every step) or [N, steps - 1, n_act], the
+    actions of steps 1 .. (HipSim.trajectory_jvp).  Where z or theta requires grad, the forward pass computes the
+    len(wrt) + p needed columns of d s / d [z | theta] in forward mode and backward is J^T grad.  x0 and u are not
+    differentiated: x0.requires_grad and u.requires_grad raise."""
+    from . import hip_backend
+
+    p = len(params)
+    sel = hip_backend.param_spec(params)
+    spec = [sel[j] for j in range(p)]
+    idx = [int(i) for i in wrt]
+    fn = _trajectory_function()
+    cache = {}
+
+    def f(x0, z=None, theta=None, u=None):
+        import torch
+
+        if x0.requires_grad:
+            raise ValueError("trajectory_fn: x0 is not differentiated: list the entries to differentiate in wrt and "
+                             "pass them as z")
+        if u is not None and u.requires_grad:
+            raise ValueError("trajectory_fn: the actions u are not differentiated: for gradients in an action sequence "
+                             "chain step_fn(sim, mode='reverse')")
+        if z is None and idx:
+            z = x0[:, idx]
+        if z is not None and (z.dim() != 2 or z.shape[1] != len(idx)):
+            raise ValueError(f"trajectory_fn: z must be [N, {len(idx)}], got {tuple(z.shape)}")
+        if theta is not None and p == 0:
+            raise ValueError("trajectory_fn: theta given but no params selected")
+        key = str(x0.device)
+        if key not in cache:
+            cache[key] = hip_backend.trajectory_directions(sim.input_dim, idx, p, device=x0.device)
+        ix = torch.tensor(idx, dtype=torch.long, device=x0.device)
+        return fn.apply(z, theta, x0, u, sim, int(steps), int(every), ix, cache[key], spec)
 
     return f

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include "tds_dparam.h"
 #include "tds_vjp_kernels.h"
 
 namespace {
@@ -28,46 +29,6 @@ template <>
 struct TdsVjpParamCap<TdsBoundA> { static constexpr int N = 86016; };
 template <>
 struct TdsVjpParamCap<TdsBoundL> { static constexpr int N = 81920; };
-
-constexpr int kHostK = 8;  // tangents per evaluation on the host
-
-// ---------------------------------------------------------------- forward mode
-// directions v[n][kdirs][input_dim + p] -> jv[n][kdirs][output_dim]; kdirs = 0: y only
-struct TdsJvpParamArgs {
-  const tds_model_t *m;
-  int n, kdirs, p;
-  const double *x, *theta, *v;
-  const tds_param_t *params;
-  double *y, *out;
-};
-
-template <class B, int K>
-struct TdsJvpParamLane {
-  TdsDual<K> x[B::NX], y[B::NY];
-  TdsParamOverlay<TdsDual<K>, B> P;
-  TdsDiffWork<TdsDual<K>, B> w;
-};
-
-// evaluate environment env with directions d0 .. d0 + K - 1 (those below kdirs); 0 or the step's -1
-template <class B, int K>
-TDS_HD inline int tds_jvp_param_eval(const TdsJvpParamArgs &a, TdsJvpParamLane<B, K> &L, int env, int d0) {
-  using D = TdsDual<K>;
-  const tds_model_t *m = a.m;
-  const int nin = m->input_dim, nall = nin + a.p;
-  const double *xe = a.x + (size_t)env * nin, *th = a.theta + (size_t)env * a.p;
-  for (int i = 0; i < nin; ++i) L.x[i] = D(xe[i]);
-  tds_param_seed(m, L.P);
-  for (int j = 0; j < a.p; ++j) tds_param_set(L.P, a.params[j], D(th[j]));
-  for (int k = 0; k < K && d0 + k < a.kdirs; ++k) {
-    const double *ve = a.v + ((size_t)env * a.kdirs + d0 + k) * nall;
-    for (int i = 0; i < nin; ++i) L.x[i].d[k] = ve[i];
-    for (int j = 0; j < a.p; ++j) {
-      tds_param_slot(L.P, a.params[j], 0)->d[k] = ve[nin + j];
-      tds_param_slot(L.P, a.params[j], 1)->d[k] = ve[nin + j];
-    }
-  }
-  return tds_diff_step_view(m, TdsOverlayView<D, B>{&L.P}, L.w, L.x, L.y);
-}
 
 // jv of the directions d0 .. of environment env; `bad`: NaN
 template <class B, int K>
@@ -119,15 +80,6 @@ int tds_jvp_param_launch(tds_hip_sim *s, const TdsJvpParamArgs &a, void *ws) {
   TDS_HIP_TRY(hipGetLastError());
   return TDS_OK;
 }
-
-// y only (k = 0): the double step over an overlay of doubles, a lane's work object (no tangents: about a third of the
-// dual lane's bytes)
-template <class B>
-struct TdsParamYLane {
-  double y[B::NY];
-  TdsParamOverlay<double, B> P;
-  TdsDiffWork<double, B> w;
-};
 
 // y of environment env into ye (NaN where M is not positive definite); 0 or the step's -1
 template <class B>
@@ -227,23 +179,6 @@ int tds_vjp_param_launch(tds_hip_sim *s, TdsVjpParamArgs a, const tds_param_t *p
   TDS_HIP_TRY(hipMemcpy(d_sel, params_host, sel, hipMemcpyHostToDevice));
   a.params = d_sel;
   return tds_vjp_run(s, a, lay, n_lanes);
-}
-
-// ---------------------------------------------------------------- checks shared by the entry points
-int tds_param_check_sel(const tds_model_t *m, int p, const tds_param_t *params) {
-  const char *why = "";
-  if (tds_param_check(m, p, params, &why)) return fail(TDS_ERR_INVALID_ARG, "%s", why);
-  return TDS_OK;
-}
-
-// the host entry points' model checks: class (refusals as for the Jacobians), blob indices, selection
-int tds_param_host_prepare(const tds_model_t *m, int p, const tds_param_t *params, int *cls) {
-  const char *why = "";
-  *cls = tds_jvp_pick(m, &why);
-  if (*cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
-  const int rc = tds_hip_model_check(m);
-  if (rc) return rc;
-  return tds_param_check_sel(m, p, params);
 }
 
 }  // namespace

@@ -64,6 +64,8 @@ enum TdsOptKey {
   TDS_OPT_SHARD_PEER_RELEASE,   // peer-store exchange: 1 = system-scope release fences in front of the arrival counts and the flag stores (A/B switch for the first run on a real fabric; default: vmcnt(0) + relaxed stores)
   TDS_OPT_SHARD_PEER_COPY,      // peer exchange, STAGED form: 1 = the launch stores its records into this rank's own ring only and the communication stream pushes the launch's slots to every peer's ring with one strided device-to-device copy per peer (the runtime's copy engines: SDMA over xGMI) + one flag kernel — nothing of the exchange on a compute unit beside the launch, no store over the fabric from inside it (third form of bench.py's warm-up ladder; default 0: in-kernel peer stores)
   TDS_OPT_SHARD_PEER_LOOPBACK,  // diagnostic: k extra "peers" mapped onto scratch rings of this rank's own GPU (the kernel-side cost of k peers, measurable on one GPU)
+  // ---- step derivatives
+  TDS_OPT_TRAJ_STEPS,         // articulated trajectory derivatives (tds_traj.hip): steps per launch (unset: 16; bounds a launch's duration whatever the horizon)
   TDS_OPT_COUNT
 };
 
@@ -127,6 +129,7 @@ inline const TdsOptRow *tds_opt_rows() {
       {"shard_peer_release", false, "TDS_HIP_SHARD_PEER_RELEASE"},
       {"shard_peer_copy", false, "TDS_HIP_SHARD_PEER_COPY"},
       {"shard_peer_loopback", false, "TDS_HIP_SHARD_PEER_LOOPBACK"},
+      {"traj_steps", false, "TDS_HIP_TRAJ_STEPS"},
   };
   return rows;
 }

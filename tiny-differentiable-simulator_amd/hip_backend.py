@@ -128,6 +128,10 @@ def lib():
         L.tds_hip_jvp_params_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3
         L.tds_hip_vjp_params_host.argtypes = L.tds_hip_jvp_params_host.argtypes + [C.c_int, C.c_void_p]
+        L.tds_hip_trajectory_jvp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
+            [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.tds_hip_trajectory_jvp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
+            [C.c_void_p, C.c_int] + [C.c_void_p] * 3
         RP = C.POINTER(_model.RbModel)
         L.tds_rb_params_get.argtypes = [RP, C.c_int, PP, C.c_void_p]
         L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
@@ -222,7 +226,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
-    "tds_hip_vjp_params_host",
+    "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
 ]
@@ -443,6 +447,67 @@ def vjp_params_host(m: _model.Model, x, theta, params, w, want_y: bool = False, 
     if tape_len:
         out += (lens,)
     return out if len(out) > 1 else out[0]
+
+
+def trajectory_dims(m: _model.Model, steps: int, every: int = 1):
+    """(nsd, n_act, n_rec) of a trajectory: state entries q | qd, action slots of a step's record, recorded states"""
+    nsd = m.dof_q + m.dof_qd
+    n_act = m.input_dim - nsd - (3 if m.step_mode == _model.TDS_STEP_LOCOMOTION else 0)
+    return nsd, n_act, (int(steps) // int(every) if int(every) > 0 else 0)
+
+
+def trajectory_jvp_host(m: _model.Model, x0, v=None, steps: int = 1, every: int = 1, u=None, params=(), theta=None):
+    """Forward-mode trajectory derivative on the CPU (tds_hip_trajectory_jvp_host; the checker of
+    HipSim.trajectory_jvp, needs no GPU).
+
+    x0 [N, input_dim], u None or [N, steps - 1, n_act], theta None (the model's values), [p] or [N, p], v
+    [N, K, input_dim + p] (or [N, input_dim + p]: K = 1).  Returns (s, js): s [N, n_rec, nq + nd], js
+    [N, K, n_rec, nq + nd] (or [N, n_rec, nq + nd]); v None: js None."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x0.shape[0], len(params)
+    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    up = None
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (n, max(int(steps) - 1, 0), n_act):
+            raise ValueError(f"u: expected [{n}, {int(steps) - 1}, {n_act}], got {tuple(u.shape)}")
+        up = u.ctypes.data
+    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
+    k, v3, js, squeeze = 0, None, None, False
+    if v is not None:
+        v = np.asarray(v, dtype=np.float64)
+        squeeze = v.ndim == 2
+        v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
+        if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != m.input_dim + p:
+            raise ValueError(f"v: expected [{n}, K, {m.input_dim + p}], got {tuple(v.shape)}")
+        k = v3.shape[1]
+        js = np.zeros((n, k, max(n_rec, 1), nsd), dtype=np.float64)
+    _check(lib().tds_hip_trajectory_jvp_host(C.byref(m), n, int(steps), int(every), x0.ctypes.data, up, p, sel,
+                                             None if th is None else th.ctypes.data, k,
+                                             None if v3 is None else v3.ctypes.data, s.ctypes.data,
+                                             None if js is None else js.ctypes.data))
+    if js is not None and squeeze:
+        js = js[:, 0]
+    return s, js
+
+
+def trajectory_directions(input_dim: int, wrt, p: int = 0, device=None):
+    """unit directions [len(wrt) + p, input_dim + p]: one per entry of x0 in wrt, then one per parameter"""
+    import torch
+
+    cols = [int(i) for i in wrt]
+    for i in cols:
+        if not 0 <= i < input_dim:
+            raise ValueError(f"wrt entry {i} out of range (input_dim {input_dim})")
+    cols += [input_dim + j for j in range(p)]
+    v = torch.zeros((len(cols), input_dim + p), dtype=torch.float64, device=device)
+    if cols:
+        v[torch.arange(len(cols)), torch.tensor(cols)] = 1.0
+    return v
 
 
 def _rb_check(rc):
@@ -882,6 +947,55 @@ class HipSim:
         if squeeze:
             wj = wj[:, 0]
         return y, wj[..., :self.input_dim], wj[..., self.input_dim:]
+
+    # -- articulated trajectories: forward_zero chained, forward mode in [x0 | theta] ----------------------------------
+    def trajectory_jvp(self, x0, v=None, steps: int = 1, every: int = 1, u=None, params=(), theta=None):
+        """(s, js): the states s [N, n_rec, nq + nd] after steps every, 2 every, .., steps of forward_zero chained from
+        x0 [N, input_dim] (any N), and js = (d s / d [x0 | theta]) v [N, K, n_rec, nq + nd] for directions v
+        [N, K, input_dim + p] (or [N, input_dim + p]: K = 1, js [N, n_rec, nq + nd]); v None: js None.  u None (x0's
+        actions every step) or [N, steps - 1, n_act], the actions of steps 1 ..; not differentiated.  params and theta
+        as for jvp_params; theta None: the model's values.  The resident state is not touched.  f64 handles only
+        (async)."""
+        import torch
+
+        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
+        x0 = x0.contiguous()
+        n, p = x0.shape[0], len(params)
+        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
+        sel = param_spec(params)
+        th = None if theta is None else self._theta(theta, n, p)
+        thp = None if th is None else C.c_void_p(th.data_ptr())
+        up = None
+        if u is not None:
+            assert u.is_cuda and u.dtype == torch.float64
+            assert tuple(u.shape) == (n, max(int(steps) - 1, 0), n_act), (tuple(u.shape), n, int(steps) - 1, n_act)
+            u = u.contiguous()
+            up = C.c_void_p(u.data_ptr())
+        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=x0.device)
+        x0p = C.c_void_p(x0.data_ptr())
+        if v is None:
+            _check(lib().tds_hip_trajectory_jvp(self.h, n, int(steps), int(every), x0p, up, p, sel, thp, 0, None,
+                                                C.c_void_p(s.data_ptr()), None))
+            return s, None
+        squeeze = v.dim() == 2
+        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
+        assert v3.is_cuda and v3.dtype == torch.float64 and v3.dim() == 3 and tuple(v3.shape[::2]) == (n, self.input_dim + p)
+        k = v3.shape[1]
+        js = torch.empty((n, k, max(n_rec, 1), nsd), dtype=torch.float64, device=x0.device)
+        if k == 0:
+            return self.trajectory_jvp(x0, None, steps, every, u, params, theta)[0], js
+        _check(lib().tds_hip_trajectory_jvp(self.h, n, int(steps), int(every), x0p, up, p, sel, thp, k,
+                                            C.c_void_p(v3.data_ptr()), C.c_void_p(s.data_ptr()),
+                                            C.c_void_p(js.data_ptr())))
+        return s, (js[:, 0] if squeeze else js)
+
+    def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
+        """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
+        into x0's input_dim entries)"""
+        n, p = x0.shape[0], len(params)
+        v = trajectory_directions(self.input_dim, wrt, p, device=x0.device).expand(n, -1, -1)
+        _, js = self.trajectory_jvp(x0, v, steps, every, u, params, theta)
+        return js.reshape(n, v.shape[1], -1).transpose(1, 2)
 
     def step(self, actions=None, substeps: int = 1, obs=None):
         """Closed-loop step on the resident records (async): x[:, act] <- actions, y = f(x),
