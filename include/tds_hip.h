@@ -701,6 +701,22 @@ int tds_hip_kernel_info(const tds_hip_sim_t *sim, int *lds_bytes_per_env, int *t
    chain = 0).  Optional outputs: that kernel's lanes and LDS bytes per environment. */
 int tds_hip_single_step_kernel(const tds_hip_sim_t *sim, int *lanes_per_env, int *lds_bytes_per_env);
 
+/* Which kernel and build a launch takes, asked on the CPU (no device needed): the plan launch() follows for a handle of
+   `model` / `dtype` / `num_envs` on a device of `num_cus` compute units with `lds_per_cu` bytes of LDS each, under the
+   process's default options (tds_hip_default_option).  req[TDS_PLAN_REQ_INTS]: environments in the launch, environments
+   resident at the same time (0: the same), steps, reset mode (0 none, 1 auto, 2 forced), policy rollout, record rings,
+   ... with progress counters, ... with peer stores, reset states from the pool, refill pass of the reset pool, phase stamps
+   (0 none, 1 room for one wavefront's, 2 for the two-wavefront form's), auto-reset on.  out[TDS_PLAN_OUT_INTS]: kernel (as
+   tds_hip_single_step_kernel), general kernel kind (0 .. 4), the kernel's build, the general kernel's build, its LDS layout
+   (0 one-wave, 1 two-wavefront, 2 reset pool), environments and threads per workgroup, workgroups, refused (option
+   loop_occ), and for a request over all num_envs environments: step-loop launch (1) or chained graphs (0), environment
+   range of the 8-lane kernel's calls (0: one launch), exchange after the launch (ring launch with progress counters).
+   Returns TDS_PLAN_OUT_INTS, or an error code. */
+#define TDS_PLAN_REQ_INTS 12
+#define TDS_PLAN_OUT_INTS 12
+int tds_hip_launch_plan_host(const tds_model_t *model, int dtype, int num_envs, int num_cus, int lds_per_cu, const int *req,
+                             int n_req, int *out, int n_out);
+
 /* ======================================================================================
  * Multi-GPU: the global batch of environments is cut into equal contiguous shards, one per rank /
  * GPU (rank r owns environments [r N/G, (r+1) N/G)); each shard is an ordinary tds_hip_sim on its own device, the

@@ -12,6 +12,7 @@ import pytest
 import tds_amd
 from tds_amd import hip_backend
 from conftest import rel_err
+from test_launch_plan import host_plan_agrees
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6  # BASELINE.json north_star: relative, per step
@@ -101,6 +102,7 @@ def test_golden_single_steps(name, dtype, built):
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
     sim = hip_backend.HipSim(m, g["x"].shape[0], dtype=dtype)
     assert sim.single_step_kernel()[0] == "chain8"
+    host_plan_agrees(sim, m, g["x"].shape[0], dtype)
     x = torch.from_numpy(g["x"]).to(sim.torch_dtype).cuda()
     y = sim.forward_zero(x).double().cpu().numpy()
     y_ref = g["y"]
@@ -185,6 +187,7 @@ def test_closed_loop_against_the_reference_at_full_size(name, n, dtype, built):
     nl, steps = m.num_links, 50
     sim = hip_backend.HipSim(m, n, dtype=dtype)
     assert sim.single_step_kernel()[0] == "chain8" and sim.step_many_is_loop(steps)
+    host_plan_agrees(sim, m, n, dtype, steps=steps)
     tdt = sim.torch_dtype
     x0 = np.zeros((n, m.input_dim))
     x0[:, :nl] = rng.uniform(-1, 1, (n, nl))

@@ -19,6 +19,7 @@ import pytest
 import tds_amd
 from tds_amd import hip_backend
 from conftest import GOLDEN, rel_err
+from test_launch_plan import host_plan_agrees
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +58,8 @@ def test_oct_kernel_takes_the_ant_and_matches_the_golden_steps(dtype, built):
     sim = hip_backend.HipSim(m, n, dtype=dtype)
     gen = hip_backend.HipSim(m, n, dtype=dtype, options={"oct": 0})
     assert sim.single_step_kernel()[:2] == ("oct8", 8) and gen.single_step_kernel()[0] == "general"
+    host_plan_agrees(sim, m, n, dtype)
+    host_plan_agrees(gen, m, n, dtype, {"oct": 0})
     x = torch.from_numpy(g["x"]).to(sim.torch_dtype).cuda()
     y = sim.forward_zero(x).double().cpu().numpy()
     yg = gen.forward_zero(x).double().cpu().numpy()
@@ -191,6 +194,8 @@ def test_oct_step_loop_form_equals_single_steps(dtype, built):
     a = hip_backend.HipSim(m, n, dtype=dtype, options={"step_many_loop": 1})
     b = hip_backend.HipSim(m, n, dtype=dtype, options={"step_many_loop": 0})
     assert a.step_many_is_loop(steps) and not b.step_many_is_loop(steps) and a.single_step_kernel()[0] == "oct8"
+    host_plan_agrees(a, m, n, dtype, {"step_many_loop": 1}, steps)
+    host_plan_agrees(b, m, n, dtype, {"step_many_loop": 0}, steps)
     tdt = a.torch_dtype
     for s_ in (a, b):
         s_.x.copy_(torch.from_numpy(x).to(tdt).cuda())
@@ -323,6 +328,8 @@ def test_oct_calls_beyond_residency_run_as_environment_ranges(built):
     x = _start_state(m, name, n, rng)
     a = hip_backend.HipSim(m, n)
     b = hip_backend.HipSim(m, n, options={"oct_w2": 0})
+    host_plan_agrees(a, m, n, steps=steps)
+    host_plan_agrees(b, m, n, options={"oct_w2": 0}, steps=steps)
     for s_ in (a, b):
         s_.x.copy_(torch.from_numpy(x).cuda())
     actions = torch.from_numpy(rng.uniform(-0.4, 0.4, (5, n, m.action_dim))).cuda().contiguous()

@@ -16,6 +16,7 @@ import pytest
 import tds_amd
 from tds_amd import hip_backend
 from conftest import GOLDEN, rel_err
+from test_launch_plan import host_plan_agrees
 
 pytestmark = pytest.mark.gpu
 QUAD_MODELS = ["laikago", "laikago_soft"]
@@ -335,6 +336,8 @@ def test_quad_loop_form_selection_at_the_residency_boundaries(built):
         a = hip_backend.HipSim(m, n)
         b = hip_backend.HipSim(m, n, options={"step_many_loop": 0})
         assert a.step_many_is_loop(3) == loop and not b.step_many_is_loop(3), n
+        host_plan_agrees(a, m, n, steps=3)
+        host_plan_agrees(b, m, n, options={"step_many_loop": 0}, steps=3)
         x = _start_state(m, name, n, rng)
         actions = torch.from_numpy(rng.uniform(-0.4, 0.4, (3, n, m.action_dim))).cuda().contiguous()
         obs = torch.zeros((n, a.obs_dim + 2), dtype=torch.float64, device="cuda")

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "tds_api_internal.h"
+#include "tds_launch_plan.h"
 
 namespace tds_internal {
 thread_local char g_err[512] = "";
@@ -97,20 +98,6 @@ extern "C" {
 TDS_ALT_DECL(1) TDS_ALT_DECL(2) TDS_ALT_DECL(3) TDS_ALT_DECL(4) TDS_ALT_DECL(5) TDS_ALT_DECL(6)
 #undef TDS_ALT_DECL
 }
-// The 16-lane kernel's step-loop form (tds_quad.hip): how its workgroups are shaped for a launch over n_envs environments —
-// 1: one wavefront per workgroup (resident up to six workgroups per compute unit: the constant table costs LDS), W =
-// TDS_QUAD_WIDE_WAVES: W wavefronts around one table, a workgroup per compute unit (resident up to 32 environments per
-// compute unit: laikago_soft x 8192), 0: neither form has every workgroup resident (the caller takes the chained graphs)
-static int quad_loop_waves(const tds_hip_sim *s, int n_envs) {
-  const int in_dim = s->model.input_dim;
-  const int per_cu = (int)(s->lds_per_cu / (size_t)tds_quad_loop_workgroup_bytes(in_dim, 1));
-  const long long wide = s->opt.get(TDS_OPT_QUAD_WIDE, 1);  // 0: never, 1: where the narrow form is not resident, 2: always
-  const bool wide_fits = (size_t)tds_quad_loop_workgroup_bytes(in_dim, TDS_QUAD_WIDE_WAVES) <= s->lds_per_cu &&
-                         (n_envs + 4 * TDS_QUAD_WIDE_WAVES - 1) / (4 * TDS_QUAD_WIDE_WAVES) <= s->num_cus;
-  if (wide == 2 && wide_fits) return TDS_QUAD_WIDE_WAVES;
-  if ((n_envs + 3) / 4 <= s->num_cus * (per_cu < 8 ? per_cu : 8)) return 1;
-  return (wide != 0 && wide_fits) ? TDS_QUAD_WIDE_WAVES : 0;
-}
 static tds_alt_launch_fn tds_alt_slot(int k) {
   switch (k) {
     case 1: return tds_alt_launch_1;
@@ -121,6 +108,45 @@ static tds_alt_launch_fn tds_alt_slot(int k) {
     case 6: return tds_alt_launch_6;
     default: return nullptr;
   }
+}
+
+// enqueue the kernel and build `p` names (T: compute scalar, TR: record scalar — == T, or float under T = double: "f32
+// records / f64 arithmetic"); prof: 14 phase stamps of workgroup 0 (diagnostic)
+template <typename T, typename TR>
+static int launch_planned_t(const tds_hip_sim *s, const DevModel<T> &h, const TdsLaunchPlan &p, const TdsLds &L, const void *x,
+                            void *y, const void *actions, void *fb, void *obs, void *ovf, int n, hipStream_t stream,
+                            const TdsStepCtl &ctl, long long *prof) {
+  const DevModel<T> *d = (const DevModel<T> *)s->d_model;
+  const TR *xi = (const TR *)x, *a = (const TR *)actions;
+  TR *yo = (TR *)y, *f = (TR *)fb, *ob = (TR *)obs;
+  if (p.kernel == TDS_KERNEL_QUAD16)
+    return tds_launch_quad<T, TR>(d, h, xi, yo, a, f, ob, n, stream, ctl, p.build == TDS_QUAD_WIDE_WAVES);
+  if constexpr (sizeof(T) == 8) {
+    if (p.kernel == TDS_KERNEL_OCT8) return tds_launch_oct<T, TR>(d, h, xi, yo, a, f, ob, n, stream, ctl, p.build);
+    if (p.kernel == TDS_KERNEL_CHAIN8) return tds_launch_chain<T, TR>(d, h, xi, yo, a, f, ob, n, stream, ctl, p.build);
+  }
+#define TDS_ARGS d, h, L, s->lanes, xi, yo, a, f, ob, (T *)ovf, n, stream, ctl, prof, p.gen_build
+  if (p.kind == 1) return tds_launch_step_impl<T, TR, 1>(TDS_ARGS);
+  // (pure float arithmetic — measured only, it misses the 1e-6 contract: tds_hip.h TDS_DTYPE_F32 — is built for the
+  //  plain and the floating-base kernels; tds_hip_create refuses it for spherical joints and worlds of several bodies)
+  if constexpr (sizeof(T) == 8) {
+    if (p.kind == 2) return tds_launch_step_impl<T, TR, 2>(TDS_ARGS);
+    if (p.kind == 4) return tds_launch_step_impl<T, TR, 4>(TDS_ARGS);
+    if (p.kind == 3) return tds_launch_step_impl<T, TR, 3>(TDS_ARGS);
+  } else {
+    if (p.kind >= 2) return -4;
+  }
+  return tds_launch_step_impl<T, TR, 0>(TDS_ARGS);
+#undef TDS_ARGS
+}
+static int launch_planned(const tds_hip_sim *s, const TdsLaunchPlan &p, const TdsLds &L, const void *x, void *y,
+                          const void *actions, void *fb, void *obs, void *ovf, int n, hipStream_t stream, const TdsStepCtl &ctl,
+                          long long *prof) {
+  if (s->dtype == TDS_DTYPE_F64)
+    return launch_planned_t<double, double>(s, s->h64, p, L, x, y, actions, fb, obs, ovf, n, stream, ctl, prof);
+  if (s->dtype == TDS_DTYPE_F64_REC32)
+    return launch_planned_t<double, float>(s, s->h64, p, L, x, y, actions, fb, obs, ovf, n, stream, ctl, prof);
+  return launch_planned_t<float, float>(s, s->h32, p, L, x, y, actions, fb, obs, ovf, n, stream, ctl, prof);
 }
 
 namespace tds_internal {
@@ -136,63 +162,23 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
     ctl.pool_envs = opts->extra->pool_envs;
   }
   const hipStream_t stream = (opts && opts->other_stream) ? opts->stream : s->stream;
-  // two-wavefront workgroups: plain straight-line launches whose whole grid is resident at once (the helper wavefront
-  // then fills issue slots that would otherwise idle; beyond that the one-wave form with more workgroups per CU wins)
-  const int n_resident = (opts && opts->env_total > 0) ? opts->env_total : n;
-  const int n_blocks = (n_resident + (64 / s->lanes) - 1) / (64 / s->lanes);
-  // ... straight-line launches; and step-loop launches of plain steps (no policy, no reset, no reset pool): there the
-  // helper wavefront loops along and is also the RECORDER of per-step rings (option loop_w2 = 0: the one-wave loop build)
-  const bool loop_w2 = s->opt.get(TDS_OPT_LOOP_W2, 1) != 0;
-  const bool w2_fits = s->w2_max_blocks > 0 && n_blocks <= s->w2_max_blocks && reset_mode == TDS_RESET_NONE && !ro &&
-                       !(opts && opts->lds);
-  const bool is_loop_launch = nsub > 1 || (opts && opts->rings);
-  // (loop_w2 = 2: not for launches that take reset states from the pool)
-  const bool loop_w2_pool = s->opt.get(TDS_OPT_LOOP_W2, 1) != 2;
-  // A launch whose ring slots are exchanged while it runs (rings->progress) takes the SAME two-wavefront build an N = 1
-  // launch takes (round 4: every rank of an N > 1 run executes the N = 1 kernel).  Round 3 dropped such launches to the
-  // one-wave loop build — two wavefronts of 256 registers per SIMD leave no register for anybody else, and the exchange's
-  // kernels (the one-lane wait, RCCL's all-gather) get onto a compute unit only when a workgroup of the launch retires
-  // (profiles/r03_ring_exchange_forms.txt: the first wait of a 64-step launch returned after 86 % of it) — at the price of
-  // 13 % of the step rate before a byte travelled.  Measured on one rank (profiles/r04_same_box_ab_and_exchange_forms.txt):
-  // two-wavefront build + 256-step launches 14.9 us per step (0.935 of the N = 1 rate), one-wave build 18.6.
-  // Option exchange_w2 = 0 brings the one-wave build back (bench.py times both forms in its warm-up at N > 1 and keeps the
-  // faster one on every rank); the tests pin BOTH builds on the reference.
-  const bool exchanged = opts && opts->rings && opts->rings->progress && s->opt.get(TDS_OPT_EXCHANGE_W2, 1) == 0;
-  const bool two_waves = w2_fits && (is_loop_launch ? (loop_w2 && !exchanged && (loop_w2_pool || !(opts && opts->extra)) &&
-                                                       s->lds_w2.NDP <= 16)
-                                                    : !(opts && opts->rings));
-  const TdsLds &lds = (opts && opts->lds) ? *opts->lds : (two_waves ? s->lds_w2 : s->lds);
-  const long long occ = s->opt.get(TDS_OPT_LOOP_OCC, 0);
-  // (the one-wavefront-per-SIMD compilation of the step loop does not exist below 24 padded dof: built without
-  //  MachineLICM its <double, double, 16, 8> instantiation never terminated — profiles/r04_diag_loop_hang.txt — and the
-  //  two-wavefront compilation holds no scratch there; at 14 - 18 dof it paid for the Ant and Laikago at small batches,
-  //  which run in kernels of their own since rounds 5 / 6; asked for by option, the launch is refused instead of
-  //  falling back silently)
-  if (occ == 1 && lds.NDP < 24 && !two_waves && (nsub != 1 || reset_mode != TDS_RESET_NONE || ro || (opts && opts->rings)))
+  const tds_hip_rings_t *rings = opts ? opts->rings : nullptr;
+  TdsLaunchReq req;
+  req.n = n;
+  req.env_total = opts ? opts->env_total : 0;
+  req.nsub = nsub;
+  req.reset_mode = reset_mode;
+  req.rollout = ro != nullptr;
+  req.rings = rings != nullptr;
+  req.progress = rings && rings->progress;
+  req.peers = rings && rings->obs_ring && s->peer_launch;
+  req.pool_states = opts && opts->extra;
+  req.pool_pass = opts && opts->pool_pass;
+  const TdsLaunchPlan plan = tds_launch_plan(*s, req);
+  if (plan.refused)
     return fail(TDS_ERR_UNSUPPORTED, "option loop_occ = 1: no one-wavefront-per-SIMD step-loop build below 24 padded dof");
-  // the 8-lane kernel (tds_oct.hip) takes the launch: its two-wavefront build while every workgroup of the launch is resident
-  // with at most two wavefronts per SIMD — four workgroups per compute unit, LDS permitting (Ant: up to 8192 environments)
-  int oct_form = 0;
-  if (s->compute_f64() && s->h64.oct != 0 && nsub >= 1 && reset_mode == TDS_RESET_NONE && !ro) {
-    const long long o2 = s->opt.get(TDS_OPT_OCT_W2, 1);
-    const int per_cu = (int)(s->lds_per_cu / (size_t)tds_oct_workgroup_bytes(s->model.input_dim));
-    const int blocks = (n_resident + 7) / 8;
-    // (two workgroups per compute unit = one wavefront per SIMD: the build compiled for that — no register limit to spill at)
-    // (option oct_w2 = 3: the two-wavefronts-per-SIMD compilation at any grid size — 256 registers, so that OTHER launches fit
-    //  beside it on a SIMD: the reset pool's refill passes, see pool_step_many)
-    if (o2 != 0 && o2 != 3 && per_cu >= 2 && blocks <= 2 * s->num_cus) oct_form = TDS_FORM_OCT_W2_OCC1;
-    else if (o2 == 2 || o2 == 3 || (o2 != 0 && blocks <= s->num_cus * (per_cu < 4 ? per_cu : 4))) oct_form = TDS_FORM_OCT_W2;
-    // a refill pass of the reset pool (pool stream) while the handle's own chunks are of the one-wavefront-per-SIMD build: the
-    // 240-register build, so that the pass runs BESIDE the chunk it was issued next to instead of in its tail
-    if (opts && opts->other_stream && opts->lds == &s->pool_lds && o2 != 0 && o2 != 3 && per_cu >= 4 &&
-        (s->num_envs + 7) / 8 <= 2 * s->num_cus && s->opt.get(TDS_OPT_POOL_BESIDE, 1) != 0)
-      oct_form = TDS_FORM_OCT_BESIDE;
-  }
-  const int quad_form = (s->compute_f64() && s->h64.quad && quad_loop_waves(s, n_resident) > 1) ? TDS_FORM_QUAD_WIDE : 0;
-  const long long cw2 = s->opt.get(TDS_OPT_CHAIN_W2, 1);
-  const int form = (two_waves ? TDS_FORM_W2 : 0) | (occ == 1 ? TDS_FORM_LOOP_OCC1 : (occ == 2 ? TDS_FORM_LOOP_OCC2 : 0)) |
-                   oct_form | quad_form | (cw2 == 0 ? TDS_FORM_CHAIN_W1 : (cw2 == 2 ? TDS_FORM_CHAIN_W2_ANY : 0));
-  void *ovf = (opts && opts->ovf) ? opts->ovf : ((opts && opts->lds) ? nullptr : s->d_ovf);
+  const TdsLds &lds = tds_plan_layout(*s, plan);
+  void *ovf = (opts && opts->ovf) ? opts->ovf : ((opts && opts->pool_pass) ? nullptr : s->d_ovf);
   if (opts && opts->env_first > 0) {  // a sub-range of the environments: every per-environment array moves along
     const size_t e0 = (size_t)opts->env_first, el = s->elem;
     auto at = [&](const void *p, size_t per_env, size_t bytes) -> void * {
@@ -262,9 +248,7 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
       if (pl.reward_done_only) ctl.ring_flags |= TDS_RING_PEER_REWARD_DONE;
       if (s->opt.get(TDS_OPT_SHARD_PEER_RELEASE, 0) == 1) ctl.ring_flags |= TDS_RING_PEER_RELEASE;
       {  // a wavefront's records as one row of 8-byte units (put_obs_wide): every stride a multiple of 8 bytes
-        // (environments per wavefront: eight where the 8-lane kernel takes the launch — tds_oct_takes)
-        const bool oct_launch = s->compute_f64() && (s->h64.oct != 0 || s->h64.chain != 0) && nsub >= 1 && reset_mode == TDS_RESET_NONE && !ro;
-        const size_t wb = r.obs_f32 ? 4 : s->elem, w = (size_t)s->obs_width(), epw = oct_launch ? 8 : (size_t)(64 / s->lanes);
+        const size_t wb = r.obs_f32 ? 4 : s->elem, w = (size_t)s->obs_width(), epw = (size_t)plan.envs_per_wg;
         if ((epw * w * wb) % 8 == 0 && ((size_t)ctl.obs_envs * w * wb) % 8 == 0 && ((size_t)(uintptr_t)ctl.obs_ring) % 8 == 0 &&
             (size_t)ctl.peer_off % 8 == 0 && (size_t)n % epw == 0 && pl.wide_ok)
           ctl.ring_flags |= TDS_RING_WIDE;
@@ -294,19 +278,10 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
     const bool plain = !s->h64.is_floating && !s->h64.num_spherical && s->h64.num_bodies < 2;
     if (!fn || s->dtype != TDS_DTYPE_F64 || !plain || key != s->lanes * 100 + lds.NDP)
       return fail(TDS_ERR_UNSUPPORTED, "option alt_build: no such experiment slot in this library for this handle's kernels");
-    rc = fn(s->d_model, &s->h64, &lds, s->lanes, x, y, actions, fb, obs, ovf, n, stream, &ctl, form, nullptr);
-  } else if (s->dtype == TDS_DTYPE_F64)
-    rc = tds_launch_step<double, double>((const DevModel<double> *)s->d_model, s->h64, lds, s->lanes,
-                                         (const double *)x, (double *)y, (const double *)actions, (double *)fb,
-                                         (double *)obs, (double *)ovf, n, stream, ctl, nullptr, form);
-  else if (s->dtype == TDS_DTYPE_F64_REC32)
-    rc = tds_launch_step<double, float>((const DevModel<double> *)s->d_model, s->h64, lds, s->lanes,
-                                        (const float *)x, (float *)y, (const float *)actions, (float *)fb, (float *)obs,
-                                        (double *)ovf, n, stream, ctl, nullptr, form);
-  else
-    rc = tds_launch_step<float, float>((const DevModel<float> *)s->d_model, s->h32, lds, s->lanes, (const float *)x,
-                                       (float *)y, (const float *)actions, (float *)fb, (float *)obs,
-                                       (float *)ovf, n, stream, ctl, nullptr, form);
+    rc = fn(s->d_model, &s->h64, &lds, s->lanes, x, y, actions, fb, obs, ovf, n, stream, &ctl, plan.gen_build, nullptr);
+  } else {
+    rc = launch_planned(s, plan, lds, x, y, actions, fb, obs, ovf, n, stream, ctl, nullptr);
+  }
   if (rc != 0) {
     snprintf(g_err, sizeof(g_err), "kernel launch failed: %s", rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad lanes_per_env");
     return TDS_ERR_HIP;
@@ -389,14 +364,10 @@ int tds_hip_model_check(const tds_model_t *model) {
   return TDS_OK;
 }
 
-int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype, tds_hip_sim_t **out) {
-  if (!out) return fail(TDS_ERR_INVALID_ARG, "out is NULL");
-  *out = nullptr;
-  if (num_envs <= 0) return fail(TDS_ERR_INVALID_ARG, "num_envs must be positive");
-  if (dtype != TDS_DTYPE_F64 && dtype != TDS_DTYPE_F32 && dtype != TDS_DTYPE_F64_REC32)
-    return fail(TDS_ERR_INVALID_ARG, "unknown dtype");
-  int rc = tds_hip_model_check(model);
-  if (rc != TDS_OK) return rc;
+}  // extern "C"
+
+// the handle's launch shape (tds_launch_plan.h): everything of tds_hip_create that needs no device
+int tds_shape_handle(tds_hip_sim *s, const tds_model_t *model, int num_envs, int dtype) {
   if (dtype == TDS_DTYPE_F32) {
     // pure float arithmetic is a measured-only variant (it misses the 1e-6 contract, tds_hip.h): built for the plain and
     // the floating-base kernels, not for spherical joints or worlds of several bodies
@@ -406,41 +377,16 @@ int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype
       return fail(TDS_ERR_UNSUPPORTED, "TDS_DTYPE_F32 (pure float arithmetic) is not built for spherical joints or worlds of "
                                        "several bodies: use TDS_DTYPE_F64_REC32 (float records, double arithmetic)");
   }
-  int ndev = tds_hip_device_count();
-  if (ndev <= 0) return fail(TDS_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(TDS_ERR_INVALID_ARG, "device index out of range");
-  DeviceGuard guard(device);  // (the caller's current device is restored on return)
-  tds_hip_sim *s = new (std::nothrow) tds_hip_sim();  // value-initialised: both host models start zeroed
-  if (!s) return fail(TDS_ERR_INVALID_ARG, "out of host memory");
-  s->opt = tds_opt_snapshot();  // (override > environment > library default; the environment is not read again)
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-      if (prop.multiProcessorCount > 0) s->num_cus = prop.multiProcessorCount;
-      // (gfx950: 160 KiB per compute unit, of which one workgroup may take 64 KiB without opting in)
-      if (prop.maxSharedMemoryPerMultiProcessor >= 64 * 1024) s->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
-    }
-  }
   s->model = *model;
   s->num_envs = num_envs;
-  s->device = device;
   s->dtype = dtype;
   s->elem = dtype == TDS_DTYPE_F64 ? 8 : 4;
   const bool c64 = dtype != TDS_DTYPE_F32;  // compute scalar (DevModel / LDS / slab): double unless the pure f32 build
   const size_t celem = c64 ? 8 : 4;
   // (a floating base takes six more lanes: its pseudo links, tds_device_model.h)
   char why[128];
-  size_t msize;
-  const void *hsrc;
-  if (c64) {
-    tds_build_dev_model<double>(model, &s->h64, why);
-    msize = sizeof(DevModel<double>);
-    hsrc = &s->h64;
-  } else {
-    tds_build_dev_model<float>(model, &s->h32, why);
-    msize = sizeof(DevModel<float>);
-    hsrc = &s->h32;
-  }
+  const int rc = c64 ? tds_build_dev_model<double>(model, &s->h64, why) : tds_build_dev_model<float>(model, &s->h32, why);
+  if (rc != TDS_OK) return fail(rc, "%s", why);
   // lanes per environment: the device model's link count (pseudo links of a floating base / of spherical joints
   // included, folded fixed links excluded) and the padded dof count
   s->lanes = default_lanes_per_env(c64 ? s->h64.num_links : s->h32.num_links, model->dof_qd);
@@ -449,14 +395,14 @@ int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype
     return c64 ? tds_make_lds_layout<double>(s->h64, cap, s->lanes) : tds_make_lds_layout<float>(s->h32, cap, s->lanes);
   };
   // Contacts whose constraint rows stay in LDS (the surplus goes to a global slab: exact, slower).
-  // Default: up to 8, lowered (not below 5) if that is what lets EIGHT workgroups share a CU's 160 KiB,
+  // Default: up to 8, lowered (not below 5) if that is what lets EIGHT workgroups share a CU's LDS (160 KiB on gfx950),
   // i.e. two wavefronts per SIMD, which hides most of the instruction-stream latency once the batch
   // provides them (Ant f64: 6 -> 19.8 KiB per workgroup).  TDS_HIP_NA_CAP overrides.
   int na_cap = 8;
   if (s->opt.is_set(TDS_OPT_NA_CAP)) {
     na_cap = (int)s->opt.v[TDS_OPT_NA_CAP];
   } else {
-    const size_t budget = (160 * 1024) / 8;
+    const size_t budget = s->lds_per_cu / 8;
     for (int cap = 8; cap >= 5; --cap)
       if ((size_t)layout(cap).stride * epw * celem <= budget) {
         na_cap = cap;
@@ -481,16 +427,16 @@ int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype
       s->lds_w2 = c64 ? tds_make_lds_layout<double>(s->h64, na_cap, s->lanes, true)
                       : tds_make_lds_layout<float>(s->h32, na_cap, s->lanes, true);
       const size_t b2 = (size_t)s->lds_w2.stride * epw * celem;
-      const int per_cu = b2 > 0 ? (int)((160 * 1024) / b2) : 0;
-      // 256 CUs; two wavefronts per workgroup, four SIMDs per CU: the form pays while every wavefront is resident
-      // with at most two per SIMD, i.e. up to four workgroups per CU
+      const int per_cu = b2 > 0 ? (int)(s->lds_per_cu / b2) : 0;
+      // two wavefronts per workgroup, four SIMDs per CU: the form pays while every wavefront is resident with at most
+      // two per SIMD, i.e. up to four workgroups per CU
       const int wg_per_cu = per_cu < 4 ? per_cu : 4;
-      if (b2 <= 64 * 1024 && wg_per_cu >= 1) s->w2_max_blocks = w2_opt == 2 ? (1 << 30) : wg_per_cu * 256;
+      if (b2 <= 64 * 1024 && wg_per_cu >= 1) s->w2_max_blocks = w2_opt == 2 ? (1 << 30) : wg_per_cu * s->num_cus;
       // the workgroup's constant table of the step-loop launches (TdsLds::cw): as many rows as the LDS left over by
       // wg_per_cu workgroups holds — never at the price of a workgroup per CU (LDS is granted in 512-byte units)
       for (const int rows : {TDS_CW_LANE(celem) + TDS_CW_XT, TDS_CW_LANE(celem)}) {
         const size_t with = ((b2 + (size_t)rows * s->lanes * celem + 511) / 512) * 512;
-        if (wg_per_cu >= 1 && with <= 64 * 1024 && (size_t)wg_per_cu * with <= 160 * 1024) {
+        if (wg_per_cu >= 1 && with <= 64 * 1024 && (size_t)wg_per_cu * with <= s->lds_per_cu) {
           s->lds_w2.cw = rows;
           break;
         }
@@ -506,31 +452,67 @@ int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype
     const size_t per_cu = s->lds.NDP < 24 ? 8 : 4;
     for (const int rows : {TDS_CW_LANE(celem) + TDS_CW_XT, TDS_CW_LANE(celem)}) {
       const size_t with = ((b1 + (size_t)rows * s->lanes * celem + 511) / 512) * 512;
-      if (plain && with <= 64 * 1024 && per_cu * with <= 160 * 1024) {
+      if (plain && with <= 64 * 1024 && per_cu * with <= s->lds_per_cu) {
         s->lds.cw = rows;
         break;
       }
     }
   }
-  const int lds_bytes = (int)((size_t)s->lds.stride * epw * celem);
-  if (lds_bytes > 160 * 1024) {
-    delete s;
-    return fail(TDS_ERR_UNSUPPORTED, "model needs more than 160 KiB of LDS per workgroup");
-  }
-  if (lds_bytes > 64 * 1024) {
-    const bool is_fl = c64 ? s->h64.is_floating : s->h32.is_floating;
-    const bool is_sph = c64 ? s->h64.num_spherical != 0 : s->h32.num_spherical != 0;
-    const bool is_two = c64 ? s->h64.num_bodies >= 2 : s->h32.num_bodies >= 2;
-    const bool is_mfl = c64 ? s->h64.multi_floating != 0 : s->h32.multi_floating != 0;
-    const int kind = is_fl ? 1 : (is_sph ? 2 : (is_two ? (is_mfl ? 4 : 3) : 0));
-    int e = dtype == TDS_DTYPE_F64         ? tds_kernel_max_dynamic_lds<double, double>(s->lanes, s->lds.NDP, lds_bytes, kind)
-            : dtype == TDS_DTYPE_F64_REC32 ? tds_kernel_max_dynamic_lds<double, float>(s->lanes, s->lds.NDP, lds_bytes, kind)
-                                           : tds_kernel_max_dynamic_lds<float, float>(s->lanes, s->lds.NDP, lds_bytes, kind);
-    if (e != 0) {
-      delete s;
-      return fail(TDS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  if ((size_t)s->lds.stride * epw * celem > s->lds_per_cu)
+    return fail(TDS_ERR_UNSUPPORTED, "model needs more LDS per workgroup than a compute unit has");
+  return TDS_OK;
+}
+
+namespace {
+// dynamic LDS above the 64 KiB a workgroup may take without opting in: every build of the general kernel that may run with
+// layout L is told so (a hipFuncSetAttribute per build, once per handle)
+int set_max_lds(tds_hip_sim *s, const TdsLds &L) {
+  const int bytes = (int)((size_t)L.stride * (64 / s->lanes) * (s->compute_f64() ? 8 : 4));
+  if (bytes <= 64 * 1024) return TDS_OK;
+  const int kind = tds_launch_plan(*s, TdsLaunchReq()).kind;
+  const int e = s->dtype == TDS_DTYPE_F64         ? tds_kernel_max_dynamic_lds<double, double>(s->lanes, L.NDP, bytes, kind)
+                : s->dtype == TDS_DTYPE_F64_REC32 ? tds_kernel_max_dynamic_lds<double, float>(s->lanes, L.NDP, bytes, kind)
+                                                  : tds_kernel_max_dynamic_lds<float, float>(s->lanes, L.NDP, bytes, kind);
+  return e != 0 ? fail(TDS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed") : TDS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tds_hip_create(const tds_model_t *model, int num_envs, int device, int dtype, tds_hip_sim_t **out) {
+  if (!out) return fail(TDS_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  if (num_envs <= 0) return fail(TDS_ERR_INVALID_ARG, "num_envs must be positive");
+  if (dtype != TDS_DTYPE_F64 && dtype != TDS_DTYPE_F32 && dtype != TDS_DTYPE_F64_REC32)
+    return fail(TDS_ERR_INVALID_ARG, "unknown dtype");
+  int rc = tds_hip_model_check(model);
+  if (rc != TDS_OK) return rc;
+  int ndev = tds_hip_device_count();
+  if (ndev <= 0) return fail(TDS_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(TDS_ERR_INVALID_ARG, "device index out of range");
+  DeviceGuard guard(device);  // (the caller's current device is restored on return)
+  tds_hip_sim *s = new (std::nothrow) tds_hip_sim();  // value-initialised: both host models start zeroed
+  if (!s) return fail(TDS_ERR_INVALID_ARG, "out of host memory");
+  s->opt = tds_opt_snapshot();  // (override > environment > library default; the environment is not read again)
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
+      if (prop.multiProcessorCount > 0) s->num_cus = prop.multiProcessorCount;
+      // (gfx950: 160 KiB per compute unit, of which one workgroup may take 64 KiB without opting in)
+      if (prop.maxSharedMemoryPerMultiProcessor >= 64 * 1024) s->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
     }
   }
+  s->device = device;
+  rc = tds_shape_handle(s, model, num_envs, dtype);
+  if (rc == TDS_OK) rc = set_max_lds(s, s->lds);
+  if (rc != TDS_OK) {
+    delete s;
+    return rc;
+  }
+  const bool c64 = s->compute_f64();
+  const size_t celem = c64 ? 8 : 4;
+  const size_t msize = c64 ? sizeof(DevModel<double>) : sizeof(DevModel<float>);
+  const void *hsrc = c64 ? (const void *)&s->h64 : (const void *)&s->h32;
 #define CREATE_TRY(expr)                                                                   \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \
@@ -817,19 +799,10 @@ int pool_alloc(tds_hip_sim *s) {
       s->pool_lds = s->lds;
     }
   }
-  const int lds_bytes = (int)((size_t)s->pool_lds.stride * epw * (s->compute_f64() ? 8 : 4));
-  if (lds_bytes > 160 * 1024) return fail(TDS_ERR_UNSUPPORTED, "reset pool: the refill launches need more than 160 KiB of LDS");
-  if (lds_bytes > 64 * 1024) {
-    const bool is_fl = s->compute_f64() ? s->h64.is_floating : s->h32.is_floating;
-    const bool is_sph = s->compute_f64() ? s->h64.num_spherical != 0 : s->h32.num_spherical != 0;
-    const bool is_two = s->compute_f64() ? s->h64.num_bodies >= 2 : s->h32.num_bodies >= 2;
-    const bool is_mfl = s->compute_f64() ? s->h64.multi_floating != 0 : s->h32.multi_floating != 0;
-    const int kind = is_fl ? 1 : (is_sph ? 2 : (is_two ? (is_mfl ? 4 : 3) : 0));
-    const int e = s->dtype == TDS_DTYPE_F64         ? tds_kernel_max_dynamic_lds<double, double>(s->lanes, s->pool_lds.NDP, lds_bytes, kind)
-                  : s->dtype == TDS_DTYPE_F64_REC32 ? tds_kernel_max_dynamic_lds<double, float>(s->lanes, s->pool_lds.NDP, lds_bytes, kind)
-                                                    : tds_kernel_max_dynamic_lds<float, float>(s->lanes, s->pool_lds.NDP, lds_bytes, kind);
-    if (e != 0) return fail(TDS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (reset pool)");
-  }
+  if ((size_t)s->pool_lds.stride * epw * (s->compute_f64() ? 8 : 4) > s->lds_per_cu)
+    return fail(TDS_ERR_UNSUPPORTED, "reset pool: the refill launches need more LDS than a compute unit has");
+  const int rc = set_max_lds(s, s->pool_lds);
+  if (rc != TDS_OK) return rc;
   return TDS_OK;
 }
 
@@ -876,7 +849,7 @@ int pool_run(tds_hip_sim *s, hipEvent_t done) {
     LaunchOpts o;
     o.other_stream = true;
     o.stream = s->pool_stream;
-    o.lds = &s->pool_lds;
+    o.pool_pass = true;
     o.ovf = s->d_pool_ovf;
     // straight-line step kernel on the staging records: zero action, state fed back in place, no y / obs record
     // (the settle steps as ONE launch of the step-loop build; option pool_settle_loop = 0: one straight-line launch per
@@ -1329,41 +1302,17 @@ int build_graph(tds_hip_sim *s, const void *actions, int pool, int first, int n_
 
 extern "C++" {
 namespace {
-// K steps as ONE launch of the step-loop build, every step taking its own action block (TdsStepCtl::act_pool): no kernel
-// boundaries at all, the state stays in LDS between the steps.  Always for worlds without contact points (pendulums,
-// the cartpole: ~7 us step kernels of which a boundary is a third), and for narrow kernels with contacts while the
-// batch is at most three rounds of workgroups (see below).  TDS_HIP_STEP_MANY_LOOP=0 / 1 forbids / forces it.
-bool step_many_as_loop(const tds_hip_sim *s, int n_steps) {
-  if (n_steps < 2) return false;
-  if (s->opt.is_set(TDS_OPT_STEP_MANY_LOOP)) return s->opt.v[TDS_OPT_STEP_MANY_LOOP] == 1;
-  const int ncp = s->compute_f64() ? s->h64.num_cp : s->h32.num_cp;
-  const bool two = s->compute_f64() ? s->h64.num_bodies >= 2 : s->h32.num_bodies >= 2;
-  if (!(s->model.has_plane && ncp > 0) && !two) return true;
-  // Worlds with contacts, kernels up to 16 dof (their step-loop builds fit the registers: 256 VGPR + 12 AGPR at one
-  // wavefront per SIMD, 52 B of scratch at two): one launch beats the chained graphs up to three rounds of workgroups
-  // (Ant x 2048 / 4096 / 8192: 14.4 / 14.9 / 20.3 us per step against 15.3 / 16.6 / 23.2; x 16384: 39.0 against 36.6).
-  // Wider kernels (Laikago, 18 dof) spill in the loop build and stay with the graphs (66 against 49 us).
-  const bool plain = !two && !(s->compute_f64() ? s->h64.is_floating : s->h32.is_floating) &&
-                     (s->compute_f64() ? s->h64.num_spherical : s->h32.num_spherical) == 0;
-  // the star-shaped legged robots (tds_quad.hip; 248 VGPR, no scratch in its step-loop form): the step-loop form while
-  // EVERY workgroup of the launch is resident at once — its constant table costs LDS: six workgroups per compute unit
-  // instead of the straight-line form's eight — and the chained graphs (single steps through the reset pool with
-  // auto-reset on) beyond that, where the loop form would run its workgroups in two rounds of all the steps each.
-  // laikago_soft (tools/quad_occupancy_sweep.sh, us per step, loop / graphs): x 4096 13.4 / 20.8, x 6144 18.3 / 23.2,
-  // x 8192 32.5 / 24.7; with auto-reset: 13.2 / 21.0, 17.8 / 25.8, 30.9 / 27.4.  Option step_many_loop = 0 / 1 forces a form.
-  if (s->compute_f64() && s->h64.quad) {
-    return quad_loop_waves(s, s->num_envs) != 0;
-  }
-  // the 8-lane kernel of the stars with two-link legs (tds_oct.hip: the Ant): always one launch.  Its straight-line form costs
-  // the same table copy and workgroup rounds per step plus a kernel boundary and the state's round trip through HBM, so
-  // beyond one round of resident workgroups (8192 environments) R rounds of K steps still beat K launches of R rounds
-  if (s->compute_f64() && (s->h64.oct || s->h64.chain)) return true;  // (and the serial-chain kernel, tds_chain.hip)
-  const int n_blocks = (s->num_envs + (64 / s->lanes) - 1) / (64 / s->lanes);
-  // With auto-reset on the alternative is not the chained graphs but single steps through the reset pool: the step-loop
-  // launches (pool_step_many) win at every batch size (Ant x 16384 / 32768 at 5 % resets per step: 2.81e8 / 2.87e8
-  // against 2.29e8 / 2.40e8; with hardly any resets 3.97e8 / 4.07e8 against 3.39e8 / 3.76e8)
-  return plain && s->lds.NDP <= 16 && (n_blocks <= 3072 || s->auto_reset);
+// a call of n_steps steps over the handle's environments (tds_launch_plan.h: step-loop launch or chained graphs, ranges)
+TdsLaunchPlan step_many_plan(const tds_hip_sim *s, int n_steps, const tds_hip_rings_t *rings) {
+  TdsLaunchReq r;
+  r.n = s->num_envs;
+  r.nsub = n_steps;
+  r.rings = rings != nullptr;
+  r.progress = rings && rings->progress;
+  r.peers = rings && rings->obs_ring && s->peer_launch;
+  return tds_launch_plan(*s, r);
 }
+bool step_many_as_loop(const tds_hip_sim *s, int n_steps) { return step_many_plan(s, n_steps, nullptr).loop; }
 }  // namespace
 }  // extern "C++"
 
@@ -1470,25 +1419,17 @@ int step_many_impl(tds_hip_sim_t *s, const void *actions_dev, int action_blocks,
     lo.rings = rings;
     // (a single step with rings is a step-loop launch too: the launcher picks that build whenever a ring is set)
     // (no copy of the last y slot behind the launch: the step-loop kernel writes the last step's record into d_y as well)
-    // The 8-lane kernel beyond one round of resident two-wavefront workgroups (Ant: 8192 environments): the environments are
-    // independent, so the call runs as environment ranges of that size ONE AFTER THE OTHER, each a launch of
-    // all the steps in the two-wavefront build — instead of one launch of the one-wavefront build in several rounds
-    // (Ant x 16384: 20.8 -> see DESIGN 2d; the exchange's launches count workgroups per slot and stay whole)
-    if (s->compute_f64() && s->h64.oct != 0 && s->opt.get(TDS_OPT_OCT_W2, 1) == 1 && !(rings && rings->progress) && !s->peer_launch) {
-      const int per_cu = (int)(s->lds_per_cu / (size_t)tds_oct_workgroup_bytes(s->model.input_dim));
-      const int cap = 8 * s->num_cus * (per_cu < 4 ? per_cu : 4);
-      if (cap > 0 && s->num_envs > cap) {
-        // (full rounds first, the rest last: a step costs the same from 4097 to 8192 environments — two wavefronts on some
-        //  SIMD — and less up to 4096; x 12288 as 8192 + 4096: 15.7 us per step, as 2 x 6144: 17.5)
-        for (int e0 = 0; e0 < s->num_envs; e0 += cap) {
-          const int e1 = e0 + cap < s->num_envs ? e0 + cap : s->num_envs;
-          lo.env_first = e0;
-          lo.env_total = e1 - e0;
-          const int rc = launch(s, s->d_x, s->d_y, a0, s->d_x, obs_dev, e1 - e0, n_steps, TDS_RESET_NONE, nullptr, nullptr, 0, &lo);
-          if (rc != TDS_OK) return rc;
-        }
-        return TDS_OK;
+    // (the 8-lane kernel beyond one round of resident two-wavefront workgroups: environment ranges one after the other)
+    const int cap = step_many_plan(s, n_steps, rings).env_range;
+    if (cap > 0) {
+      for (int e0 = 0; e0 < s->num_envs; e0 += cap) {
+        const int e1 = e0 + cap < s->num_envs ? e0 + cap : s->num_envs;
+        lo.env_first = e0;
+        lo.env_total = e1 - e0;
+        const int rc = launch(s, s->d_x, s->d_y, a0, s->d_x, obs_dev, e1 - e0, n_steps, TDS_RESET_NONE, nullptr, nullptr, 0, &lo);
+        if (rc != TDS_OK) return rc;
       }
+      return TDS_OK;
     }
     return launch(s, s->d_x, s->d_y, a0, s->d_x, obs_dev, s->num_envs, n_steps, TDS_RESET_NONE, nullptr, nullptr, 0, &lo);
   }
@@ -1551,8 +1492,11 @@ int tds_hip_step_many_rings(tds_hip_sim_t *s, const void *actions_dev, int actio
 
 int tds_hip_step_many_rings_blocks(const tds_hip_sim_t *s) {
   if (!s) return 0;
-  if (s->compute_f64() && (s->h64.oct || s->h64.chain)) return (s->num_envs + 7) / 8;  // (the 8-lane kernels: eight environments per workgroup)
-  return (s->num_envs + (64 / s->lanes) - 1) / (64 / s->lanes);
+  TdsLaunchReq r;  // (a step-loop launch of the exchange: the workgroups its progress counters count)
+  r.n = s->num_envs;
+  r.nsub = 2;
+  r.rings = r.progress = true;
+  return tds_launch_plan(*s, r).blocks;
 }
 
 int tds_hip_step_many_is_loop(const tds_hip_sim_t *s, int n_steps) { return s && step_many_as_loop(s, n_steps) ? 1 : 0; }
@@ -2128,11 +2072,14 @@ int tds_hip_profile_phases(tds_hip_sim_t *s, long long *cycles_host, int n) {
   if (n < TDS_NUM_PHASE_STAMPS) return fail(TDS_ERR_INVALID_ARG, "need room for 14 stamps");
   DeviceGuard guard(s->device);
   // room for 2 x 14 stamps and a grid the two-wavefront form serves: profile THAT form (14..: the helper wavefront)
-  const int n_blocks = (s->num_envs + (64 / s->lanes) - 1) / (64 / s->lanes);
-  const bool two_waves = n >= 2 * TDS_NUM_PHASE_STAMPS && s->w2_max_blocks > 0 && n_blocks <= s->w2_max_blocks;
+  TdsLaunchReq r;
+  r.n = s->num_envs;
+  r.prof = n >= 2 * TDS_NUM_PHASE_STAMPS ? 2 : 1;
+  const TdsLaunchPlan plan = tds_launch_plan(*s, r);
+  const bool two_waves = (plan.gen_build & TDS_FORM_W2) != 0;
   // (two-wavefront form: + the 100 MHz wall clock at the first / last stamp of EVERY workgroup, 28 + 2 b + {0, 1})
-  const int ns = two_waves ? 2 * TDS_NUM_PHASE_STAMPS + 2 * n_blocks : TDS_NUM_PHASE_STAMPS;
-  const TdsLds &lds = two_waves ? s->lds_w2 : s->lds;
+  const int ns = two_waves ? 2 * TDS_NUM_PHASE_STAMPS + 2 * plan.blocks : TDS_NUM_PHASE_STAMPS;
+  const TdsLds &lds = tds_plan_layout(*s, plan);
   long long *d = nullptr;
   HIP_TRY(hipMalloc(&d, sizeof(long long) * ns));
   HIP_TRY(hipMemset(d, 0, sizeof(long long) * ns));
@@ -2152,19 +2099,7 @@ int tds_hip_profile_phases(tds_hip_sim_t *s, long long *cycles_host, int n) {
       ctl.flags |= (it < 0 ? 0 : (it >= k ? k - 1 : it)) << 16;
     }
   }
-  int rc;
-  if (s->dtype == TDS_DTYPE_F64)
-    rc = tds_launch_step<double, double>((const DevModel<double> *)s->d_model, s->h64, lds, s->lanes,
-                                         (const double *)s->d_x, (double *)s->d_y, nullptr, nullptr, nullptr,
-                                         (double *)s->d_ovf, s->num_envs, s->stream, ctl, d, two_waves ? TDS_FORM_W2 : 0);
-  else if (s->dtype == TDS_DTYPE_F64_REC32)
-    rc = tds_launch_step<double, float>((const DevModel<double> *)s->d_model, s->h64, lds, s->lanes,
-                                        (const float *)s->d_x, (float *)s->d_y, nullptr, nullptr, nullptr,
-                                        (double *)s->d_ovf, s->num_envs, s->stream, ctl, d, two_waves ? TDS_FORM_W2 : 0);
-  else
-    rc = tds_launch_step<float, float>((const DevModel<float> *)s->d_model, s->h32, lds, s->lanes,
-                                       (const float *)s->d_x, (float *)s->d_y, nullptr, nullptr, nullptr,
-                                       (float *)s->d_ovf, s->num_envs, s->stream, ctl, d, two_waves ? TDS_FORM_W2 : 0);
+  const int rc = launch_planned(s, plan, lds, s->d_x, s->d_y, nullptr, nullptr, nullptr, s->d_ovf, s->num_envs, s->stream, ctl, d);
   if (rc != 0) {
     (void)hipFree(d);
     return fail(TDS_ERR_HIP, "profiling launch failed");
@@ -2253,19 +2188,55 @@ int tds_hip_kernel_info(const tds_hip_sim_t *s, int *lds_bytes_per_env, int *thr
 
 int tds_hip_single_step_kernel(const tds_hip_sim_t *s, int *lanes_per_env, int *lds_bytes_per_env) {
   if (!s) return -1;
-  const bool quad = s->compute_f64() && s->h64.quad != 0, oct = s->compute_f64() && s->h64.oct != 0;
-  const bool chain = s->compute_f64() && s->h64.chain != 0;
-  if (chain) {
-    if (lanes_per_env) *lanes_per_env = 8;
-    if (lds_bytes_per_env) *lds_bytes_per_env = tds_chain_lds_bytes(s->h64.chain);
-    return 3;
-  }
-  if (lanes_per_env) *lanes_per_env = oct ? 8 : (quad ? 16 : s->lanes);
+  TdsLaunchReq r;
+  r.n = s->num_envs;
+  const int k = tds_launch_plan(*s, r).kernel;
+  if (lanes_per_env) *lanes_per_env = k == TDS_KERNEL_GENERAL ? s->lanes : (k == TDS_KERNEL_QUAD16 ? 16 : 8);
   if (lds_bytes_per_env)
-    *lds_bytes_per_env = oct    ? tds_oct_lds_bytes(s->model.input_dim)
-                         : quad ? tds_quad_lds_bytes<double>(s->model.input_dim)
-                                : (int)(s->lds.stride * (s->compute_f64() ? 8 : 4));
-  return oct ? 2 : (quad ? 1 : 0);
+    *lds_bytes_per_env = k == TDS_KERNEL_CHAIN8   ? tds_chain_lds_bytes(s->h64.chain)
+                         : k == TDS_KERNEL_OCT8   ? tds_oct_lds_bytes(s->model.input_dim)
+                         : k == TDS_KERNEL_QUAD16 ? tds_quad_lds_bytes<double>(s->model.input_dim)
+                                                  : (int)(s->lds.stride * (s->compute_f64() ? 8 : 4));
+  return k;
+}
+
+int tds_hip_launch_plan_host(const tds_model_t *model, int dtype, int num_envs, int num_cus, int lds_per_cu, const int *req,
+                             int n_req, int *out, int n_out) {
+  if (!model || !req || !out || n_req != TDS_PLAN_REQ_INTS || n_out < TDS_PLAN_OUT_INTS || num_envs <= 0 || num_cus <= 0 ||
+      lds_per_cu < 64 * 1024 || req[0] <= 0)
+    return fail(TDS_ERR_INVALID_ARG, "launch plan: bad arguments");
+  if (dtype != TDS_DTYPE_F64 && dtype != TDS_DTYPE_F32 && dtype != TDS_DTYPE_F64_REC32) return fail(TDS_ERR_INVALID_ARG, "unknown dtype");
+  int rc = tds_hip_model_check(model);
+  if (rc != TDS_OK) return rc;
+  tds_hip_sim *s = new (std::nothrow) tds_hip_sim();
+  if (!s) return fail(TDS_ERR_INVALID_ARG, "out of host memory");
+  s->opt = tds_opt_snapshot();
+  s->num_cus = num_cus;
+  s->lds_per_cu = (size_t)lds_per_cu;
+  rc = tds_shape_handle(s, model, num_envs, dtype);
+  if (rc == TDS_OK) {
+    s->pool_lds = s->lds;  // (the refill passes' layout differs from it in the slab's rows only)
+    s->auto_reset = req[11] != 0;
+    TdsLaunchReq r;
+    r.n = req[0];
+    r.env_total = req[1];
+    r.nsub = req[2];
+    r.reset_mode = req[3];
+    r.rollout = req[4] != 0;
+    r.rings = req[5] != 0;
+    r.progress = req[6] != 0;
+    r.peers = req[7] != 0;
+    r.pool_states = req[8] != 0;
+    r.pool_pass = req[9] != 0;
+    r.prof = req[10];
+    const TdsLaunchPlan p = tds_launch_plan(*s, r);
+    const int v[TDS_PLAN_OUT_INTS] = {p.kernel,      p.kind,           p.build,    p.gen_build, p.layout,   p.envs_per_wg,
+                                      p.threads_per_wg, p.blocks,      p.refused,  p.loop,      p.env_range, p.exchange_after};
+    for (int i = 0; i < TDS_PLAN_OUT_INTS; ++i) out[i] = v[i];
+    rc = TDS_PLAN_OUT_INTS;
+  }
+  delete s;
+  return rc;
 }
 
 }  // extern "C"

@@ -140,7 +140,7 @@ struct LaunchOpts {
   const TdsStepCtl *extra = nullptr;  // n_dev / pool fields
   bool other_stream = false;          // launch on `stream` instead of the handle's
   hipStream_t stream = nullptr;
-  const TdsLds *lds = nullptr;        // LDS layout (the refill launches keep every constraint row in LDS: no slab)
+  bool pool_pass = false;             // a refill pass of the reset pool: LDS layout pool_lds (every constraint row in LDS) ...
   void *ovf = nullptr;                // ... or a surplus-row slab of the launch's own
   const void *act_pool = nullptr;     // step-loop launch with a different action block per step (TdsStepCtl::act_pool)
   int act_blocks = 0, act_first = 0;

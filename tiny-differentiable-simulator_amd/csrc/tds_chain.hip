@@ -742,24 +742,12 @@ int tds_chain_lds_bytes(int num_links) {
 
 template <typename T, typename TR>
 int tds_launch_chain(const DevModel<T> *d_model, const DevModel<T> &h_model, const TR *x_in, TR *y_out, const TR *actions,
-                     TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int w2_opt) {
+                     TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int build) {
   const int blocks = (n_envs + 7) / 8;
-  // one plain step without rings: the straight-line form; K steps, record rings: the step-loop form
+  // one plain step without rings: the straight-line form; K steps, record rings: the step-loop form of `build` (TDS_CHAIN_*:
+  // a recorder wavefront, with the links' constants in registers — tds_launch_plan.h decides which)
   const bool one_step = ctl.nsub == 1 && ctl.obs_ring == nullptr && ctl.y_ring == nullptr;
-  // the recorder wavefront: step-loop launches that store per-step records, while the launch is resident with at most two
-  // wavefronts per SIMD (1024 workgroups of two on 1024 SIMDs); option chain_w2 = 0 / 2: never / at any grid size
-  const bool two_waves = !one_step && (ctl.obs_ring != nullptr || ctl.y_ring != nullptr) && w2_opt != 0 && (blocks <= 1024 || w2_opt == 2);
-  // ... with my link's constants in registers while the launch puts at most ONE wavefront on a SIMD (that build holds 276
-  // registers: a SIMD has room for one)
-  static int n_simd = 0;
-  if (n_simd == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-      n_simd = 4 * cus;
-    else
-      n_simd = 1024;
-  }
-  const bool creg = two_waves && 2 * blocks <= n_simd;
+  const bool two_waves = build != TDS_CHAIN_W1, creg = build == TDS_CHAIN_W2_CREG;
 #define CH_LAUNCH(NL_)                                                                                                           \
   case NL_:                                                                                                                      \
     if (one_step)                                                                                                                \

@@ -131,17 +131,22 @@ struct TdsStepCtl {
 // upper bound of the peers of a rank (ranks of one node - 1)
 #define TDS_MAX_PEERS 15
 
-// which build of the step kernel a launch takes (tds_launch_step's `form`)
+// the general kernel's builds (tds_launch_step_impl's `form`; tds_launch_plan.h decides which a launch takes)
 #define TDS_FORM_W2 1         // L is the w2 layout: launch the two-wavefront form (plain kernels)
 #define TDS_FORM_LOOP_OCC1 2  // step-loop build: the one-wavefront-per-SIMD compilation whatever the grid
 #define TDS_FORM_LOOP_OCC2 4  // ... the two-wavefronts-per-SIMD compilation whatever the grid
-#define TDS_FORM_OCT_W2 8     // the 8-lane kernel (tds_oct.hip): its two-wavefront build compiled for two wavefronts per SIMD
-#define TDS_FORM_OCT_W2_OCC1 16  // ... compiled for one wavefront per SIMD (at most two workgroups per compute unit)
-#define TDS_FORM_CHAIN_W1 32     // the serial-chain kernel (tds_chain.hip): no recorder wavefront (option chain_w2 = 0)
-#define TDS_FORM_CHAIN_W2_ANY 64 // ... the recorder wavefront at any grid size (option chain_w2 = 2)
-#define TDS_FORM_QUAD_WIDE 128   // the 16-lane kernel (tds_quad.hip): step-loop launch in workgroups of TDS_QUAD_WIDE_WAVES wavefronts
-#define TDS_FORM_OCT_BESIDE 256  // the 8-lane kernel's two-wavefront build of at most 240 registers: fits on a SIMD beside a wavefront of the OCC1 build
-#define TDS_QUAD_WIDE_WAVES 8    // ... around ONE constant table: a workgroup per compute unit, 32 environments each
+// the 8-lane kernel's builds (tds_launch_oct's `build`)
+#define TDS_OCT_W1 1          // one wavefront per workgroup
+#define TDS_OCT_W2 2          // two wavefronts per workgroup, compiled for two wavefronts per SIMD
+#define TDS_OCT_W2_OCC1 3     // ... compiled for one wavefront per SIMD (at most two workgroups per compute unit)
+#define TDS_OCT_BESIDE 4      // ... of at most 240 registers: fits on a SIMD beside a wavefront of the OCC1 build
+// the serial-chain kernel's step-loop builds (tds_launch_chain's `build`)
+#define TDS_CHAIN_W1 0        // no recorder wavefront
+#define TDS_CHAIN_W2 1        // a recorder wavefront beside the stepping one
+#define TDS_CHAIN_W2_CREG 2   // ... with the links' constants in registers (at most one such wavefront per SIMD)
+// the 16-lane kernel's wide step-loop form: workgroups of this many wavefronts around ONE constant table (a workgroup per
+// compute unit, 32 environments each)
+#define TDS_QUAD_WIDE_WAVES 8
 
 // EXPERIMENT SLOTS (tools/build_alt.sh): the kernel sources compiled once more — other compiler flags, -DTDS_X_... source
 // switches — as a small extra translation unit holding ONE (lanes, padded dof) instantiation of the f64 / KIND 0 kernels,
@@ -183,68 +188,17 @@ int tds_launch_quad(const DevModel<T> *d_model, const DevModel<T> &h_model, cons
 template <typename T>
 int tds_quad_lds_bytes(int input_dim);
 int tds_quad_loop_workgroup_bytes(int input_dim, int waves);  // LDS of one workgroup of its step-loop form: 4 * waves environments + the table
-// what tds_launch_step hands to it: plain steps — one per launch, or K of them with action replay, record rings and
-// reset-pool entries taken in the loop (tds_hip_step_many / _rings) —, no in-kernel reset, no policy, no exchange launch
-// (progress counters / peer stores), no profile stamps
-inline bool tds_quad_takes(int quad, const TdsStepCtl &ctl, const long long *prof) {
-  return quad != 0 && prof == nullptr && ctl.nsub >= 1 && ctl.reset_mode == TDS_RESET_NONE && ctl.policy == nullptr &&
-         ctl.progress == nullptr && ctl.peer_arrive == nullptr;
-}
-
-// the 8-lane kernel of the stars with two-link legs (tds_oct.hip; DevModel::oct: the Ant): the same launches as the 16-lane
-// kernel, and the exchange launches of the multi-GPU layer (progress counters / peer stores) as well
+// the 8-lane kernel of the stars with two-link legs (tds_oct.hip; DevModel::oct: the Ant)
 template <typename T, typename TR>
 int tds_launch_oct(const DevModel<T> *d_model, const DevModel<T> &h_model, const TR *x_in, TR *y_out, const TR *actions,
                    TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int build);
 int tds_oct_lds_bytes(int input_dim);        // LDS of one environment
 int tds_oct_workgroup_bytes(int input_dim);  // LDS of one workgroup: eight environments + the constant table
-inline bool tds_oct_takes(int oct, const TdsStepCtl &ctl, const long long *prof) {
-  return oct != 0 && prof == nullptr && ctl.nsub >= 1 && ctl.reset_mode == TDS_RESET_NONE && ctl.policy == nullptr;
-}
-
-// the serial-chain kernel (tds_chain.hip): plain steps and step loops incl. record rings and the exchange; no resets (its
-// models have no reward rule: no environment is ever done), no policy, no phase stamps
+// the serial-chain kernel (tds_chain.hip; DevModel::chain)
 template <typename T, typename TR>
 int tds_launch_chain(const DevModel<T> *d_model, const DevModel<T> &h_model, const TR *x_in, TR *y_out, const TR *actions,
-                     TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int w2_opt);
+                     TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int build);
 int tds_chain_lds_bytes(int num_links);
-inline bool tds_chain_takes(int chain, const TdsStepCtl &ctl, const long long *prof) {
-  return chain != 0 && prof == nullptr && ctl.nsub >= 1 && ctl.reset_mode == TDS_RESET_NONE && ctl.policy == nullptr;
-}
-
-// T: compute scalar, TR: record scalar (== T, or float under T = double: "f32 records / f64 arithmetic")
-template <typename T, typename TR>
-inline int tds_launch_step(const DevModel<T> *d_model, const DevModel<T> &h_model, const TdsLds &L, int lanes_per_env,
-                           const TR *x_in, TR *y_out, const TR *actions, TR *x_feedback, TR *obs_out, T *ovf, int n_envs,
-                           hipStream_t stream, const TdsStepCtl &ctl,
-                           long long *prof = nullptr,  // prof: 14 phase stamps of workgroup 0 (diagnostic)
-                           int form = 0) {   // TDS_FORM_*: which build of the kernel
-#define TDS_ARGS d_model, h_model, L, lanes_per_env, x_in, y_out, actions, x_feedback, obs_out, ovf, n_envs, stream, ctl, prof, form
-  if (tds_quad_takes(h_model.quad, ctl, prof))
-    return tds_launch_quad<T, TR>(d_model, h_model, x_in, y_out, actions, x_feedback, obs_out, n_envs, stream, ctl,
-                                  (form & TDS_FORM_QUAD_WIDE) != 0);
-  if constexpr (sizeof(T) == 8) {
-    if (tds_oct_takes(h_model.oct, ctl, prof))
-      return tds_launch_oct<T, TR>(d_model, h_model, x_in, y_out, actions, x_feedback, obs_out, n_envs, stream, ctl,
-                                   (form & TDS_FORM_OCT_BESIDE) ? 4 : (form & TDS_FORM_OCT_W2_OCC1) ? 3 : ((form & TDS_FORM_OCT_W2) ? 2 : 1));
-    if (tds_chain_takes(h_model.chain, ctl, prof))
-      return tds_launch_chain<T, TR>(d_model, h_model, x_in, y_out, actions, x_feedback, obs_out, n_envs, stream, ctl,
-                                     (form & TDS_FORM_CHAIN_W1) ? 0 : ((form & TDS_FORM_CHAIN_W2_ANY) ? 2 : 1));
-  }
-  if (h_model.is_floating) return tds_launch_step_impl<T, TR, 1>(TDS_ARGS);
-  // (pure float arithmetic — measured only, it misses the 1e-6 contract: tds_hip.h TDS_DTYPE_F32 — is built for the
-  //  plain and the floating-base kernels; tds_hip_create refuses it for spherical joints and worlds of several bodies)
-  if constexpr (sizeof(T) == 8) {
-    if (h_model.num_spherical) return tds_launch_step_impl<T, TR, 2>(TDS_ARGS);
-    if (h_model.num_bodies >= 2 && h_model.multi_floating) return tds_launch_step_impl<T, TR, 4>(TDS_ARGS);
-    if (h_model.num_bodies >= 2) return tds_launch_step_impl<T, TR, 3>(TDS_ARGS);
-  } else {
-    if (h_model.num_spherical || h_model.num_bodies >= 2) return -4;
-  }
-  return tds_launch_step_impl<T, TR, 0>(TDS_ARGS);
-#undef TDS_ARGS
-}
-
 template <typename T, typename TR, int KIND>
 int tds_kernel_max_dynamic_lds_impl(int lanes_per_env, int ndp, int bytes);
 template <typename T, typename TR>

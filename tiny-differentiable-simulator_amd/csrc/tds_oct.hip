@@ -1728,8 +1728,7 @@ int tds_oct_workgroup_bytes(int input_dim) {
   return (oct_layout(input_dim).stride * 8 + TdsOctTab::TOTAL) * (int)sizeof(double);
 }
 
-// build: 1 one wavefront per workgroup, 2 / 3 the two-wavefront builds (the host grants them while every workgroup of the
-// launch is resident with at most two wavefronts per SIMD / one: tds_api.hip), 4 the two-wavefront build of at most 240 registers
+// build: TDS_OCT_* (tds_kernels.h; which one a launch takes: tds_launch_plan.h)
 template <typename T, typename TR>
 int tds_launch_oct(const DevModel<T> *d_model, const DevModel<T> &h_model, const TR *x_in, TR *y_out, const TR *actions,
                    TR *x_feedback, TR *obs_out, int n_envs, hipStream_t stream, const TdsStepCtl &ctl, int build) {

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "tds_api_internal.h"
+#include "tds_launch_plan.h"
 #include "tds_shard_plan.h"
 
 using namespace tds_internal;
@@ -787,12 +788,14 @@ bool ring_form(const tds_hip_shard *sh, int n_steps) {
   const tds_hip_sim *s = sh->sim;
   if (sh->block != 1 || s->auto_reset) return false;  // (auto-reset: the refill passes of the reset pool are host-driven)
   if (s->opt.get(TDS_OPT_SHARD_RING, 1) == 0) return false;
+  TdsLaunchReq r;
+  r.n = s->num_envs;
+  r.nsub = n_steps > 1 ? n_steps : 2;
+  r.rings = true;
+  const TdsLaunchPlan p = tds_launch_plan(*s, r);
   // (the 16-lane kernel of the legged robots has a step-loop form, but not the exchange's part of it — progress counters,
   //  peer stores: their shards keep the per-step launches, which run on that kernel's straight-line form)
-  if (s->compute_f64() && s->h64.quad) return false;
-  // (the 8-lane kernel hands its exchange launches to the general kernel: tds_oct_takes; what the ring form needs is that
-  //  kernel's step-loop form, judged as if the handle had no 8-lane kernel)
-  return tds_hip_step_many_is_loop(s, n_steps > 1 ? n_steps : 2) != 0;
+  return p.kernel != TDS_KERNEL_QUAD16 && p.loop;
 }
 
 // one chunk on the CURRENT streams (sim->stream / comm_stream; under capture both belong to the capture)
@@ -894,9 +897,13 @@ int ring_chunk(tds_hip_shard *sh, const void *actions_dev, int pool, const TdsRi
     sh->exchange_form = staged ? TDS_EXCHANGE_PEER_COPY : TDS_EXCHANGE_PEER_STORES;
     return TDS_OK;
   }
-  const int n_blocks = tds_hip_step_many_rings_blocks(s);
-  const bool after_launch = s->opt.get(TDS_OPT_EXCHANGE_W2, 1) != 0 && s->opt.get(TDS_OPT_LOOP_W2, 1) != 0 &&
-                            s->w2_max_blocks > 0 && n_blocks <= s->w2_max_blocks && s->lds_w2.NDP <= 16;
+  TdsLaunchReq req;
+  req.n = s->num_envs;
+  req.nsub = ck.steps;
+  req.rings = req.progress = true;
+  const TdsLaunchPlan plan = tds_launch_plan(*s, req);
+  const int n_blocks = plan.blocks;  // (what the progress counters count: tds_hip_step_many_rings_blocks)
+  const bool after_launch = plan.exchange_after;
   r.progress = after_launch ? nullptr : counters;
   int rc = tds_hip_step_many_rings(s, actions_dev, pool, ck.act_first, ck.steps, &r);
   if (rc != TDS_OK) return rc;

@@ -104,6 +104,8 @@ def lib():
         L.tds_hip_shard_gathered.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
         L.tds_hip_shard_ring_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.tds_hip_shard_gathered_offset.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.tds_hip_launch_plan_host.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                               C.POINTER(C.c_int), C.c_int]
         L.tds_hip_shard_gathered_offset.restype = C.c_longlong
         L.tds_hip_default_option.argtypes = [C.c_char_p, C.c_longlong]
         L.tds_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
@@ -222,7 +224,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_shard_local_envs", "tds_hip_shard_first_env", "tds_hip_shard_wire_bytes", "tds_hip_shard_set_block",
     "tds_hip_shard_step", "tds_hip_shard_step_many", "tds_hip_shard_step_many_prepare", "tds_hip_shard_group_step", "tds_hip_shard_flush", "tds_hip_shard_gathered", "tds_hip_shard_gathered_step",
     "tds_hip_shard_ring_plan", "tds_hip_shard_gathered_offset", "tds_hip_shard_exchange_form", "tds_hip_shard_peer_count",
-    "tds_hip_single_step_kernel",
+    "tds_hip_single_step_kernel", "tds_hip_launch_plan_host",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
@@ -247,6 +249,37 @@ def shard_ring_plan(chunks_done: int, n_steps: int, act_first: int = 0, act_bloc
         raise TdsHipError("tds_hip_shard_ring_plan: bad arguments")
     keys = ("half", "steps", "step0", "act_first", "slot0", "first_wait")
     return [dict(zip(keys, out[6 * i:6 * i + 6])) for i in range(n)]
+
+
+PLAN_KERNELS = {0: "general", 1: "quad16", 2: "oct8", 3: "chain8"}
+_PLAN_REQ = ("n", "env_total", "nsub", "reset_mode", "rollout", "rings", "progress", "peers", "pool_states", "pool_pass",
+             "prof", "auto_reset")
+_PLAN_OUT = ("kernel", "kind", "build", "gen_build", "layout", "envs_per_wg", "threads_per_wg", "blocks", "refused", "loop",
+             "env_range", "exchange_after")
+
+
+def launch_plan_host(m: _model.Model, dtype: str = "f64", num_envs: int = 1, num_cus: int = 256, lds_per_cu: int = 160 * 1024,
+                     **req):
+    """which kernel and build a launch takes (tds_hip_launch_plan_host; no device needed): the plan of a handle of
+    `num_envs` environments on a device of `num_cus` compute units with `lds_per_cu` bytes of LDS each, under the process's
+    default options.  req: n (default num_envs), env_total, nsub (1), reset_mode, rollout, rings, progress, peers,
+    pool_states, pool_pass, prof, auto_reset.  Returns a dict of the plan; "kernel" is named as in single_step_kernel()."""
+    unknown = set(req) - set(_PLAN_REQ)
+    if unknown:
+        raise TypeError(f"launch_plan_host: unknown request fields {sorted(unknown)}")
+    vals = dict(n=num_envs, nsub=1)
+    vals.update(req)
+    r = (C.c_int * len(_PLAN_REQ))(*[int(vals.get(k, 0)) for k in _PLAN_REQ])
+    out = (C.c_int * len(_PLAN_OUT))()
+    rc = lib().tds_hip_launch_plan_host(C.byref(m), dtype_code(dtype), int(num_envs), int(num_cus), int(lds_per_cu), r,
+                                        len(_PLAN_REQ), out, len(_PLAN_OUT))
+    if rc != len(_PLAN_OUT):
+        _check(rc)
+    plan = dict(zip(_PLAN_OUT, out))
+    plan["kernel"] = PLAN_KERNELS[plan["kernel"]]
+    for k in ("refused", "loop", "exchange_after"):
+        plan[k] = bool(plan[k])
+    return plan
 
 
 def default_option(key: str, value) -> None:
