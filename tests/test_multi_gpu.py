@@ -477,9 +477,14 @@ def test_ring_exchange_sends_a_slot_only_when_the_slowest_workgroup_has_stored_i
     sh.close()
 
 
-@pytest.mark.parametrize("with_rccl,wire,loopback,fields", [
-    (False, "f32", 0, 0), (True, "f32", 0, 0), (False, "f64", 3, 0), (True, "f32", 7, 0), (False, "f32", 2, 1)])
-def test_shard_peer_store_exchange_on_one_rank(with_rccl, wire, loopback, fields, built):
+@pytest.mark.parametrize("with_rccl,wire,loopback,fields,oct", [
+    pytest.param(False, "f32", 0, 0, None, id="False-f32-0-0"), pytest.param(True, "f32", 0, 0, None, id="True-f32-0-0"),
+    pytest.param(False, "f64", 3, 0, None, id="False-f64-3-0"), pytest.param(True, "f32", 7, 0, None, id="True-f32-7-0"),
+    pytest.param(False, "f32", 2, 1, None, id="False-f32-2-1"),
+    # the same exchange through the GENERAL kernel (create-time option oct = 0: the Ant otherwise always takes the 8-lane kernel)
+    pytest.param(False, "f64", 3, 0, 0, id="general-f64-3-0"), pytest.param(False, "f64", 3, 1, 0, id="general-f64-3-1"),
+    pytest.param(False, "f32", 2, 1, 0, id="general-f32-2-1")])
+def test_shard_peer_store_exchange_on_one_rank(with_rccl, wire, loopback, fields, oct, built):
     """The DEFAULT ring exchange (round 5): the step-loop launch stores every step's record into the gathered slot itself —
     on every rank; here on the one rank there is, plus `loopback` scratch rings of its own standing in for peers, so that the
     kernel executes exactly what it executes on loopback + 1 GPUs — and raises the slot's flags when its last workgroup has
@@ -493,9 +498,12 @@ def test_shard_peer_store_exchange_on_one_rank(with_rccl, wire, loopback, fields
     x, acts = _start(m, n, seed=43)
     a = torch.from_numpy(acts).cuda().contiguous()
     uid = hip_backend.HipShard.unique_id() if with_rccl else None
-    sh = hip_backend.HipShard(m, n, unique_id=uid, wire_dtype=wire,
-                              options={"shard_chunk": 64, "shard_peer": 2, "shard_peer_loopback": loopback, "exchange_fields": fields})
-    ref = hip_backend.HipSim(m, n)
+    with hip_backend.default_options(**({} if oct is None else {"oct": oct})):
+        sh = hip_backend.HipShard(m, n, unique_id=uid, wire_dtype=wire,
+                                  options={"shard_chunk": 64, "shard_peer": 2, "shard_peer_loopback": loopback, "exchange_fields": fields})
+        ref = hip_backend.HipSim(m, n)
+    # (the rows that say "general kernel" do run it, the others the 8-lane kernel)
+    assert sh.sim.single_step_kernel()[0] == ref.single_step_kernel()[0] == ("general" if oct == 0 else "oct8")
     for s in (sh.sim, ref):
         s.x.copy_(torch.from_numpy(x).cuda())
     K = 75

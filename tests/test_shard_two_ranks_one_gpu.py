@@ -76,7 +76,7 @@ if backs:
     extra["backs"] = torch.stack(backs).cpu().numpy()                         # [b][world][n_local][w] float
     extra["local_backs"] = torch.stack([ring[steps - 1 - b] for b in range(len(backs))]).to(torch.float32).cpu().numpy()
 np.savez(out, gathered=gat.cpu().numpy(), local=obs.to(torch.float32).cpu().numpy(), x=sim.x.cpu().numpy(), xref=ref.x.cpu().numpy(),
-         form=np.array(form), peers=np.array(sh.peer_count()), **extra)
+         form=np.array(form), peers=np.array(sh.peer_count()), kernel=np.array(sim.single_step_kernel()[0]), **extra)
 sh.close()
 '''
 
@@ -120,6 +120,10 @@ RCCL = {"TDS_HIP_SHARD_PEER": "0"}  # the forms of the exchange that go through 
     ("many", "ant", 12, {"TDS_HIP_SHARD_RING": "0"}, "rccl_per_step"),      # per-step launches + exchanges from one hipGraph
     ("many", "laikago", 9, {}, "rccl_per_step"),                            # a model whose step_many is not the step-loop form
     ("single", "ant", 7, {}, "rccl_per_step"),                              # tds_hip_shard_step, one call per step
+    # PEER STORES through the GENERAL kernel (option oct = 0; the Ant otherwise always takes the 8-lane kernel): whole rows, and
+    # the lane-per-component stores of a ragged last wavefront (at the end of the list: the rows above keep their ids)
+    ("many", "ant", 75, {"TDS_HIP_OCT": "0"}, "peer_stores"),
+    ("many", "ant", 75, {"TDS_HIP_OCT": "0", "_n_local": "201"}, "peer_stores"),
 ])
 def test_two_ranks_on_one_gpu(mode, name, steps, env, want_form, built, stub_lib, tmp_path):
     import torch
@@ -154,6 +158,8 @@ def test_two_ranks_on_one_gpu(mode, name, steps, env, want_form, built, stub_lib
     rd_only = env.get("TDS_HIP_EXCHANGE_FIELDS") == "1"
     for k in range(world):
         assert str(r[k]["form"]) == want_form, (k, str(r[k]["form"]), logs[k])
+        if env.get("TDS_HIP_OCT") == "0":  # (the rows that say "general kernel" did run it)
+            assert str(r[k]["kernel"]) == "general", (k, str(r[k]["kernel"]))
         assert int(r[k]["peers"]) == (1 if want_form in ("peer_stores", "peer_copy") else -1)
         got = r[k]["gathered"].reshape(-1, w)
         assert got.shape == want.shape

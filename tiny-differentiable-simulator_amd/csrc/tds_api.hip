@@ -247,7 +247,7 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
       ctl.peer_flag_stride = pl.flag_stride;
       if (pl.reward_done_only) ctl.ring_flags |= TDS_RING_PEER_REWARD_DONE;
       if (s->opt.get(TDS_OPT_SHARD_PEER_RELEASE, 0) == 1) ctl.ring_flags |= TDS_RING_PEER_RELEASE;
-      {  // a wavefront's records as one row of 8-byte units (put_obs_wide): every stride a multiple of 8 bytes
+      {  // a wavefront's records as one row of 8-byte units (tds_obs_store_wide): every stride a multiple of 8 bytes
         const size_t wb = r.obs_f32 ? 4 : s->elem, w = (size_t)s->obs_width(), epw = (size_t)plan.envs_per_wg;
         if ((epw * w * wb) % 8 == 0 && ((size_t)ctl.obs_envs * w * wb) % 8 == 0 && ((size_t)(uintptr_t)ctl.obs_ring) % 8 == 0 &&
             (size_t)ctl.peer_off % 8 == 0 && (size_t)n % epw == 0 && pl.wide_ok)

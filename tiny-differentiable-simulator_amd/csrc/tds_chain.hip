@@ -26,6 +26,7 @@
 #include "tds_device_model.h"
 #include "tds_kernels.h"
 #include "tds_lanes.h"
+#include "tds_step_shared.h"
 
 namespace {
 
@@ -51,60 +52,6 @@ __device__ __forceinline__ double ch_from_child(double old, double v) {
   const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), 0x100 + 2 * K, 0xF, 0xF, false);
   return __hiloint2double(hi, lo);
 }
-
-template <typename P>
-__device__ __forceinline__ P *ch_global(P *p) {  // a loaded pointer: not LDS, not scratch (global_ instead of flat_ accesses)
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_assume(!__builtin_amdgcn_is_shared((const void *)p) && !__builtin_amdgcn_is_private((const void *)p));
-#endif
-  return p;
-}
-
-// sin / cos of a joint angle (the 8-lane kernel's routine: Cody-Waite reduction + the fdlibm kernels, library routine beyond 1e5)
-__device__ __forceinline__ void ch_sincos(double x, double *sn, double *cs) {
-  const bool big = !(__builtin_fabs(x) < 1.0e5);
-  const double k = __builtin_rint(x * 6.36619772367581382433e-01);
-  double r = __builtin_fma(-k, 1.57079632679489655800e+00, x);
-  r = __builtin_fma(-k, 6.12323399573676603587e-17, r);
-  const int q = (int)k;
-  const double z = r * r;
-  double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-  ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-  ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-  ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-  ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
-  const double s0 = __builtin_fma(z * r, ps, r);
-  double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-  pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-  pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-  pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-  pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
-  const double c0 = __builtin_fma(z * z, pc, __builtin_fma(z, -0.5, 1.0));
-  const bool swap = (q & 1) != 0;
-  const double ss = swap ? c0 : s0, cc = swap ? s0 : c0;
-  double s_ = (q & 2) ? -ss : ss, c_ = ((q + 1) & 2) ? -cc : cc;
-  if (__builtin_expect(__any(big), 0)) {  // (per lane: an environment's bits do not depend on its wavefront-mates)
-    double s2, c2;
-    sincos(x, &s2, &c2);
-    s_ = big ? s2 : s_;
-    c_ = big ? c2 : c_;
-  }
-  *sn = s_;
-  *cs = c_;
-}
-
-template <bool LOOP>
-struct ChainCtlRef {
-  using type = const TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &param, const __attribute__((address_space(4))) char *) { return param; }
-};
-template <>
-struct ChainCtlRef<true> {
-  using type = const __attribute__((address_space(4))) TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &, const __attribute__((address_space(4))) char *at) {
-    return *(const __attribute__((address_space(4))) TdsStepCtl *)at;
-  }
-};
 
 // LDS per environment, in scalars: the x record [q | qd | tau] (+ 2: done, reward — always zero for these models, kept where
 // the record code of the other kernels reads them), the rows of M (NL x NL) and the right-hand side
@@ -226,35 +173,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64) void tds_chain_kernel(const DevModel
     //  across the loop they spilled: 47 spills in the 5-link instantiation)
     const __attribute__((address_space(4))) char *ka_seg = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (LOOP) asm volatile("" : "+s"(ka_seg));
-    typename ChainCtlRef<LOOP>::type ctl = ChainCtlRef<LOOP>::get(ctl_arg, ka_seg + 48 /* six pointers in front of ctl */);
-  // a step's records counted in for the multi-GPU layer (tds_shard.hip; see tds_kernels.hip: peer_signal)
-    auto signal_slot = [&](int pslot) {
-      if (ctl.peer_arrive != nullptr) {
-        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): every store of this wavefront acknowledged by the memory it went to
-        const bool rel = (ctl.ring_flags & TDS_RING_PEER_RELEASE) != 0;
-        if (rel) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        if (tid == 0) {
-          constexpr unsigned SUB = TDS_PEER_SUB;
-          const unsigned g = gridDim.x, j = blockIdx.x % SUB;
-          const unsigned n1 = (g - j + SUB - 1u) / SUB;
-          const unsigned n2 = g < SUB ? g : SUB;
-          unsigned *const base = ch_global(ctl.peer_arrive) + (size_t)pslot * TDS_PEER_ARRIVE_STRIDE;
-          if (atomicInc(base + j * TDS_PEER_LINE, n1 - 1u) == n1 - 1u) {
-            if (atomicInc(base + 32 * TDS_PEER_LINE, n2 - 1u) == n2 - 1u) {
-              const size_t fi = (size_t)ctl.peer_flag_off + (size_t)pslot * (size_t)ctl.peer_flag_stride;
-              if (rel) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "");
-              for (int pr = 0; pr <= ctl.n_peers; ++pr)
-                __hip_atomic_store(ctl.peer_flags[pr] + fi, ctl.peer_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-          }
-        }
-      } else if (ctl.progress != nullptr) {
-        if (ctl.ring_flags & TDS_RING_NOFENCE) __builtin_amdgcn_s_waitcnt(0x0f70);
-        else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        if (tid == 0) __hip_atomic_fetch_add(ch_global(ctl.progress) + pslot, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    };
-
+    typename TdsCtlRef<LOOP>::type ctl = TdsCtlRef<LOOP>::get(ctl_arg, ka_seg + 48 /* six pointers in front of ctl */);
     const bool last = it == nsteps - 1;
     int wv_ = 0;
     if constexpr (W2) {
@@ -266,10 +185,10 @@ __global__ __launch_bounds__(W2 ? 128 : 64) void tds_chain_kernel(const DevModel
     if constexpr (LOOP) {
       // the records of step it - 1 are counted in here (by the wavefront that stored them): their stores have long been
       // acknowledged — or, in the recorder's case, it waits for the main wavefront's step anyway
-      if (is_rec && it > 0 && ctl.obs_ring != nullptr) signal_slot((o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
+      if (is_rec && it > 0 && ctl.obs_ring != nullptr) tds_signal_slot(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
       // the NEXT step's torques are requested now (a different action block per step: tds_hip_step_many)
       if (is_main && ctl.act_pool != nullptr && it + 1 < nsteps && valid && mine)
-        next_act = (T)ch_global((const TR *)ctl.act_pool)[((size_t)act_blk * ctl.act_envs + env) * adim + link];
+        next_act = (T)tds_global((const TR *)ctl.act_pool)[((size_t)act_blk * ctl.act_envs + env) * adim + link];
     }
     // where this step's y record goes: the slot of a y ring (every step of a step-loop launch), else the handle's y record
     // (the last step); the last step of a ring launch leaves its record in the handle's y record as well
@@ -277,7 +196,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64) void tds_chain_kernel(const DevModel
     TR *yo = nullptr, *yo2 = nullptr;
     int yend = ystr, yend2 = out_dim;
     if (LOOP && ctl.y_ring != nullptr) {
-      yo = ch_global((TR *)ctl.y_ring) + ((size_t)y_slot * ctl.ring_envs + env) * ystr;
+      yo = tds_global((TR *)ctl.y_ring) + ((size_t)y_slot * ctl.ring_envs + env) * ystr;
       if (last && y_out != nullptr) yo2 = y_out + (size_t)env * out_dim;
     } else if (last && y_out != nullptr) {
       yo = y_out + (size_t)env * (LOOP ? out_dim : ystr);
@@ -321,7 +240,7 @@ __global__ __launch_bounds__(W2 ? 128 : 64) void tds_chain_kernel(const DevModel
     for (int k = 0; k < 6; ++k) S[k] = CREG ? cS[k] : CL[TB::S + k];
     {
       T sn, cs;
-      ch_sincos(q * (CREG ? cROTF : CL[TB::ROTF]), &sn, &cs);
+      tds_sincos(q * (CREG ? cROTF : CL[TB::ROTF]), &sn, &cs);
       const T c1 = T(1) - cs;
       const T nx = CREG ? cNAX[0] : CL[TB::NAX], ny = CREG ? cNAX[1] : CL[TB::NAX + 1], nz = CREG ? cNAX[2] : CL[TB::NAX + 2];
       T RJ[9];
@@ -620,82 +539,13 @@ __global__ __launch_bounds__(W2 ? 128 : 64) void tds_chain_kernel(const DevModel
     if constexpr (LOOP) {
       if (ctl.obs_ring != nullptr) {  // wave-uniform
         const int slot = o_slot;
-        const int rf = ctl.ring_flags;
-        const bool f32w = (rf & TDS_RING_OBS_F32) != 0 || sizeof(TR) == 4;
-        const int np = ctl.peer_arrive != nullptr ? ctl.n_peers : 0;
-        const bool rd_only = (rf & TDS_RING_PEER_REWARD_DONE) != 0;
-        if (ctl.peer_arrive != nullptr && (rf & TDS_RING_WIDE) != 0 && __all(valid)) {
-          // peer-store exchange: the wavefront's eight records as one row of 8-byte units (see tds_oct.hip: help_rec)
-          const int wl = tid;
-          const size_t row0 = ((size_t)slot * ctl.obs_envs + (size_t)blockIdx.x * 8) * (size_t)w_obs;
-          const int per_unit = f32w ? 2 : 1;
-          const int n_units = (8 * w_obs) / per_unit;
-          const unsigned long long *const __attribute__((address_space(4))) *tab =
-              (const unsigned long long *const __attribute__((address_space(4))) *)(const __attribute__((address_space(4))) void *)ctl.peer_ring;
-          for (int u0 = 0; u0 < n_units; u0 += 64) {
-            const int uu = u0 + wl;
-            const bool on = uu < n_units;
-            unsigned lo = 0u, hi = 0u;
-            bool tail = false;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-              if (c < per_unit) {
-                const int f = on ? uu * per_unit + c : 0;
-                const int e = f / w_obs;
-                const int i = f - e * w_obs;
-                const int src = i < nq + nd ? i : (i == nq + nd ? LD::REWARD : LD::DONE);
-                const T vv = i < 2 ? T(0) : sm[e * LD::STRIDE + src];
-                tail = tail || i >= nq + nd;
-                if (f32w) {
-                  const unsigned b = (unsigned)__float_as_int((float)vv);
-                  if (c == 0) lo = b; else hi = b;
-                } else {
-                  const double dv = (double)vv;
-                  lo = (unsigned)__double2loint(dv);
-                  hi = (unsigned)__double2hiint(dv);
-                }
-              }
-            }
-            const unsigned long long bits = ((unsigned long long)hi << 32) | (unsigned long long)lo;
-            const size_t unit_at = row0 / per_unit + (size_t)uu;
-            if (on) __hip_atomic_store(ch_global((unsigned long long *)ctl.obs_ring) + unit_at, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool to_peers = on && (!rd_only || tail);
-            for (int p0 = 0; p0 < np; p0 += 4) {  // (the table is padded to a multiple of four entries)
-              const unsigned long long *const b0 = ch_global(tab[p0]), *const b1 = ch_global(tab[p0 + 1]), *const b2 = ch_global(tab[p0 + 2]),
-                                       *const b3 = ch_global(tab[p0 + 3]);
-              const size_t po = (size_t)ctl.peer_off / 8 + unit_at;
-              if (to_peers) {
-                using G64 = __attribute__((address_space(1))) unsigned long long;
-                __hip_atomic_store((G64 *)((unsigned long long *)b0 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (p0 + 1 < np) __hip_atomic_store((G64 *)((unsigned long long *)b1 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (p0 + 2 < np) __hip_atomic_store((G64 *)((unsigned long long *)b2 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (p0 + 3 < np) __hip_atomic_store((G64 *)((unsigned long long *)b3 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-              }
-            }
-          }
-        } else if (valid) {
-          const size_t at = ((size_t)slot * ctl.obs_envs + env) * w_obs;
-          for (int i = link; i < w_obs; i += 8) {
-            const T vv = i < 2 ? T(0) : xr[i < nq + nd ? i : (i == nq + nd ? LD::REWARD : LD::DONE)];
-            if (rf & TDS_RING_OBS_F32) {
-              float *const pp = ch_global((float *)ctl.obs_ring) + at + i;
-              if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              else *pp = (float)vv;
-            } else {
-              TR *const pp = ch_global((TR *)ctl.obs_ring) + at + i;
-              if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              else *pp = (TR)vv;
-            }
-            if (np > 0 && (i >= nq + nd || !rd_only)) {
-              for (int pr = 0; pr < np; ++pr) {
-                char *const pb = (char *)ch_global(((void *const __attribute__((address_space(4))) *)(const __attribute__((address_space(4))) void *)ctl.peer_ring)[pr]) + ctl.peer_off;
-                if (rf & TDS_RING_OBS_F32) __hip_atomic_store((float *)pb + (at + i), (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                else __hip_atomic_store((TR *)pb + (at + i), (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-              }
-            }
-          }
-        }
-        if (last && ctl.peer_arrive != nullptr) signal_slot(slot);
+        auto at = [&](int i) { return i < nq + nd ? i : (i == nq + nd ? LD::REWARD : LD::DONE); };  // column i in the LDS record
+        // peer-store exchange: the wavefront's eight records as one row of 8-byte units; else scalar by scalar
+        if (ctl.peer_arrive != nullptr && (ctl.ring_flags & TDS_RING_WIDE) != 0 && __all(valid))
+          tds_obs_store_wide<8, w_obs, TR>(ctl, slot, tid, w_obs, [&](int e, int i) { return sm[e * LD::STRIDE + at(i)]; });
+        else if (valid)
+          tds_obs_store_scalar<8, TR>(ctl, slot, env, link, w_obs, [&](int i) { return xr[at(i)]; }, [](auto v, auto *p) { *p = v; });
+        if (last && ctl.peer_arrive != nullptr) tds_signal_slot(ctl, slot);
       }
     }
     if (valid && last) {

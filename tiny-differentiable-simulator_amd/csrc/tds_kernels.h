@@ -91,7 +91,7 @@ struct TdsStepCtl {
   unsigned long long *const *peer_flags;  // [n_peers + 1]: peer p's flag array [slots][world]; the last entry is this rank's own
   unsigned int *peer_arrive;        // [obs_slots][TDS_PEER_ARRIVE_STRIDE] arrival counters of this launch's slots: TDS_PEER_SUB
                                     // first-level counters + one second-level counter per slot, a 128-byte line each
-                                    // (all wrap at their own count: atomicInc, never reset) — see peer_signal
+                                    // (all wrap at their own count: atomicInc, never reset) — see tds_step_shared.h: tds_peer_count_in
   long long peer_off;               // bytes from a ring's base to THIS rank's block of the launch's slot 0
   unsigned long long peer_epoch;    // the launch's sequence number (what a completed slot's flags are raised to)
   int n_peers;                      // ranks other than this one (0: one rank — the counters and the own flags only)
@@ -121,7 +121,7 @@ struct TdsStepCtl {
 // for logging"); this rank's own block still receives the whole record
 #define TDS_RING_PEER_REWARD_DONE 8
 // peer-store exchange: every stride of the obs ring (record row of a wavefront, slot, rank block, peer offset) is a multiple
-// of 8 bytes — a wavefront's records may leave as one row of 8-byte units (tds_kernels.hip: put_obs_wide); the peer table is
+// of 8 bytes — a wavefront's records may leave as one row of 8-byte units (tds_step_shared.h: tds_obs_store_wide); the peer table is
 // padded to a multiple of four entries
 #define TDS_RING_WIDE 16
 // peer-store exchange, A/B switch for the first run on a real fabric (option shard_peer_release = 1): a SYSTEM-scope release

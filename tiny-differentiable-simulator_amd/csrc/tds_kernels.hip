@@ -41,14 +41,11 @@
 #include "tds_device_model.h"
 #include "tds_kernels.h"
 #include "tds_lanes.h"
+#include "tds_step_shared.h"
 // two-wavefront workgroups of the narrow kernels: the generalised force of the PD block waits in LDS for phase F
 // (0: carried in registers)
 #ifndef TDS_PARK_W2
 #define TDS_PARK_W2 1
-#endif
-// scope of the peer-store exchange's stores into the other ranks' rings (experiments on one GPU may lower it)
-#ifndef TDS_PEER_SCOPE
-#define TDS_PEER_SCOPE __HIP_MEMORY_SCOPE_SYSTEM
 #endif
 #ifndef TDS_PARK_LOOP
 #define TDS_PARK_LOOP 0
@@ -82,22 +79,7 @@ namespace {
 #define TDS_LDS_PUBLISH 1
 #endif
 #define TDS_AS3 __attribute__((address_space(3)))
-// A pointer that was LOADED (a field of the kernel-argument structs read through the laundered segment pointer, an entry of a
-// pointer table) has no address space the compiler could know: its accesses are FLAT instructions — both counters, out of
-// order with the DS instructions, and a flat LOAD (the action block requested a step ahead) holds the next LDS wait until it
-// has returned from memory.  tds_global() says "global memory" (an assumption `neither LDS nor scratch`, which the
-// address-space inference pass turns into address space 1 for every access derived from the pointer).  -DTDS_RINGS_GLOBAL=0: the loaded pointers as they are.
-#ifndef TDS_RINGS_GLOBAL
-#define TDS_RINGS_GLOBAL 1
-#endif
-template <typename P>
-__device__ __forceinline__ P *tds_global(P *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (TDS_RINGS_GLOBAL != 0)
-    __builtin_assume(!__builtin_amdgcn_is_shared((const void *)p) && !__builtin_amdgcn_is_private((const void *)p));
-#endif
-  return p;
-}
+// (loaded pointers — kernel-argument fields, pointer-table entries — are declared global memory by tds_global(): tds_step_shared.h)
 template <int WHO = 1, typename T>
 __device__ __forceinline__ T tds_lds_poll(const T *p) {  // WHO: 1 the main wavefront's polls, 2 the helper's
   if constexpr (WHO == 1) return *(const volatile TDS_AS3 T *)p;
@@ -774,7 +756,6 @@ __device__ __forceinline__ double tds_gram_solve(double *sm, const TdsLds &L, in
 // lane, the lane group and the model pointer — and reads the two structs THROUGH it (constant address space: scalar
 // loads, hit the scalar cache), so that a field lives from its first use in an iteration to its last.  The straight-line
 // builds keep the parameters.  (The mirror struct below has the kernel's parameter list, hence the segment's layout.)
-#define TDS_AS4 __attribute__((address_space(4)))
 template <typename T, typename TR>
 struct TdsKernArgs {
   const DevModel<T> *mdl;
@@ -789,16 +770,7 @@ struct TdsKernArgs {
   TdsStepCtl ctl;
   int n_envs;
 };
-template <bool LOOP, typename S>
-struct TdsKaRef {
-  using type = const S &;
-  static __device__ __forceinline__ type get(const S &param, const TDS_AS4 char *) { return param; }
-};
-template <typename S>
-struct TdsKaRef<true, S> {
-  using type = const TDS_AS4 S &;
-  static __device__ __forceinline__ type get(const S &, const TDS_AS4 char *at) { return *(const TDS_AS4 S *)at; }
-};
+// (TdsKaRef — the parameter, or the reference into the segment — is shared with the other step kernels: tds_step_shared.h)
 template <bool ON, typename P>
 __device__ __forceinline__ P tds_ka_val(P param, const TDS_AS4 char *at) {  // a pointer / scalar parameter, by value
   if constexpr (ON) return *(const TDS_AS4 P *)at;
@@ -1396,20 +1368,6 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   const bool do_reward = last_run || ((pol || pool_r || ring_o) && mode == TDS_MODE_RUN);
   // where this step's y record goes, and whether it is packed at all: the handle's y record for the last normal step
   // of a launch, or — with a y ring — the ring slot of EVERY step
-  // one scalar into the obs ring: float or record dtype; streaming store, or (TDS_RING_NOFENCE) a device-scope
-  // write-through store that needs no cache write-back to become visible to the exchange
-  auto ring_put = [&](size_t idx, T v) {
-    const int rf = ctl.ring_flags;
-    if (rf & TDS_RING_OBS_F32) {
-      float *const p = tds_global((float *)ctl.obs_ring) + idx;
-      if (rf & TDS_RING_NOFENCE) __hip_atomic_store(p, (float)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else TDS_NT_STORE((float)v, p);
-    } else {
-      TR *const p = tds_global((TR *)ctl.obs_ring) + idx;
-      if (rf & TDS_RING_NOFENCE) __hip_atomic_store(p, (TR)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else TDS_NT_STORE((TR)v, p);
-    }
-  };
   // Plain kernels (KIND 0) store the END-of-step records of a ring launch — the state part + tail of the y record, the
   // whole obs record — from the LDS record in the MIDDLE of the following step, behind that step's visual poses: on gfx9
   // loads and stores drain through ONE in-order counter, so the first wait for a load at the top of a step would also
@@ -1432,6 +1390,20 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     }
     for (int i = tail + lane; i < yend; i += G) TDS_NT_STORE((TR)(0), &yo[i]);
   };
+  // one scalar into the obs ring: float or record dtype; streaming store, or (TDS_RING_NOFENCE) a device-scope
+  // write-through store that needs no cache write-back to become visible to the exchange
+  auto ring_put = [&](size_t idx, T v) {
+    const int rf = ctl.ring_flags;
+    if (rf & TDS_RING_OBS_F32) {
+      float *const p = tds_global((float *)ctl.obs_ring) + idx;
+      if (rf & TDS_RING_NOFENCE) __hip_atomic_store(p, (float)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else TDS_NT_STORE((float)v, p);
+    } else {
+      TR *const p = tds_global((TR *)ctl.obs_ring) + idx;
+      if (rf & TDS_RING_NOFENCE) __hip_atomic_store(p, (TR)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else TDS_NT_STORE((TR)v, p);
+    }
+  };
   // [q | qd with obs[0] = obs[1] = 0 | reward | done] of ring slot `slot` (ars_vectorized_environment.h:250-289): the
   // observation from the LDS record as it is NOW, reward / done from their LDS slots (written by the reward block)
   // Peer-store exchange (TdsStepCtl::peer_arrive): the same scalar goes into the same place of every peer's gathered ring —
@@ -1450,9 +1422,9 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
           for (int pr = 0; pr < np; ++pr) {
             char *const pb = (char *)tds_global(((void *const TDS_AS4 *)(const TDS_AS4 void *)ctl.peer_ring)[pr]) + ctl.peer_off;  // (see put_obs_wide)
             if (ctl.ring_flags & TDS_RING_OBS_F32)
-              __hip_atomic_store((float *)pb + (at + i), (float)v, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
+              __hip_atomic_store((float *)pb + (at + i), (float)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             else
-              __hip_atomic_store((TR *)pb + (at + i), (TR)v, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
+              __hip_atomic_store((TR *)pb + (at + i), (TR)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           }
         }
       }
@@ -1477,15 +1449,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     // (the pointer table is read through the CONSTANT address space — written once at set-up, uniform index: scalar loads.
     //  As vector loads each pointer was fetched right in front of its store, and the wait for it — loads and stores return
     //  through one in-order counter — was a wait for the acknowledgement of the PREVIOUS peer's row: the seven rows of an
-    //  8-GPU run went out one after the other, 2.3 us per step.  -DTDS_PEER_TAB_CONST=0)
-#ifndef TDS_PEER_TAB_CONST
-#define TDS_PEER_TAB_CONST 1
-#endif
-#if TDS_PEER_TAB_CONST
+    //  8-GPU run went out one after the other, 2.3 us per step)
     const unsigned long long *const TDS_AS4 *tab = (const unsigned long long *const TDS_AS4 *)(const TDS_AS4 void *)ctl.peer_ring;
-#else
-    const unsigned long long *const *tab = tds_global((const unsigned long long *const *)ctl.peer_ring);
-#endif
     for (int u0 = 0; u0 < n_units; u0 += 64) {  // (one pass on a float wire up to 128 scalars per wavefront)
       const int u = u0 + wl;
       const bool on = u < n_units;
@@ -1527,10 +1492,10 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
         if (to_peers) {
           // (stores through explicitly global pointers: as generic ones they were FLAT stores)
           using G64 = __attribute__((address_space(1))) unsigned long long;
-          __hip_atomic_store((G64 *)((unsigned long long *)b0 + po), bits, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
-          if (p0 + 1 < np) __hip_atomic_store((G64 *)((unsigned long long *)b1 + po), bits, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
-          if (p0 + 2 < np) __hip_atomic_store((G64 *)((unsigned long long *)b2 + po), bits, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
-          if (p0 + 3 < np) __hip_atomic_store((G64 *)((unsigned long long *)b3 + po), bits, __ATOMIC_RELAXED, TDS_PEER_SCOPE);
+          __hip_atomic_store((G64 *)((unsigned long long *)b0 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          if (p0 + 1 < np) __hip_atomic_store((G64 *)((unsigned long long *)b1 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          if (p0 + 2 < np) __hip_atomic_store((G64 *)((unsigned long long *)b2 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          if (p0 + 3 < np) __hip_atomic_store((G64 *)((unsigned long long *)b3 + po), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
     }
@@ -1558,6 +1523,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   // environments carry more contacts falls steps behind the others over a long launch — so a single running total says
   // nothing about the slowest workgroup; the slot's own counter reaches (uses of the slot) x (workgroups) exactly when
   // EVERY workgroup has stored its records of that step.
+  // (the same protocol as tds_step_shared.h: tds_peer_count_in / tds_peer_finish / tds_signal_slot — kept as this kernel's own
+  //  text: see there)
   // Peer-store exchange: this workgroup's records of ring slot `pslot` are out — acknowledged by the memory they went to,
   // this rank's and the peers' — so it counts itself in on the slot's arrival counters (two levels, each wrapping at its own
   // count: never reset); the workgroup that completes the slot raises the slot's flag of THIS rank on every rank, its own

@@ -42,6 +42,7 @@
 #include "tds_device_model.h"
 #include "tds_kernels.h"
 #include "tds_lanes.h"
+#include "tds_step_shared.h"
 
 // Phase stamps (a build of its own: -DTDS_OCT_PROF, tools/oct_profile.sh): workgroup TDS_OCT_PROF_WG writes the shader clock
 // at the phase boundaries of iteration TDS_OCT_PROF_ITER of a step-loop launch into tds_oct_prof_buf
@@ -130,45 +131,6 @@ __device__ __forceinline__ float oct_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(t, b, 0x150 + 8 + K, 0xF, 0xC, false));
 }
 
-// sin and cos of a joint angle: Cody-Waite reduction by pi / 2 in two fused steps (exact for |x| < 1e5: the product k * hi is
-// formed exactly inside the FMA and cancels against x) and the fdlibm kernels on [-pi/4, pi/4] (__kernel_sin / __kernel_cos:
-// < 1 ulp) — ~35 instructions where the library routine takes ~90 with its branch to the Payne-Hanek reduction; angles
-// beyond 1e5 rad (no simulation gets there, but a caller may hand in anything) take the library routine, wave-uniformly
-__device__ __forceinline__ void oct_sincos(double x, double *sn, double *cs) {
-  const bool big = !(__builtin_fabs(x) < 1.0e5);
-  const double k = __builtin_rint(x * 6.36619772367581382433e-01);
-  double r = __builtin_fma(-k, 1.57079632679489655800e+00, x);
-  r = __builtin_fma(-k, 6.12323399573676603587e-17, r);
-  const int q = (int)k;
-  const double z = r * r;
-  double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-  ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-  ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-  ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-  ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
-  const double s0 = __builtin_fma(z * r, ps, r);
-  double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-  pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-  pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-  pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-  pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
-  const double c0 = __builtin_fma(z * z, pc, __builtin_fma(z, -0.5, 1.0));
-  const bool swap = (q & 1) != 0;
-  const double ss = swap ? c0 : s0, cc = swap ? s0 : c0;
-  double s_ = (q & 2) ? -ss : ss, c_ = ((q + 1) & 2) ? -cc : cc;
-  // (the lanes beyond 1e5 — or NaN — take the library routine; the OTHER lanes of the wavefront keep their own result: an
-  //  environment's bits must not depend on a wavefront-mate that has left the finite range)
-  if (__builtin_expect(__any(big), 0)) {
-    double s2, c2;
-    sincos(x, &s2, &c2);
-    s_ = big ? s2 : s_;
-    c_ = big ? c2 : c_;
-  }
-  *sn = s_;
-  *cs = c_;
-}
-__device__ __forceinline__ void oct_sincos(float x, float *sn, float *cs) { sincosf(x, sn, cs); }
-
 // LDS per environment, offsets in scalars of T
 struct OctOff {
   int lcw, legf, swl, qdp, fac, win, xs, cp, stride;
@@ -213,26 +175,6 @@ struct OctKernArgs {
   int n_envs;
   OctOff O;
 };
-template <bool LOOP>
-struct OctCtlRef {
-  using type = const TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &param, const __attribute__((address_space(4))) char *) { return param; }
-};
-template <>
-struct OctCtlRef<true> {
-  using type = const __attribute__((address_space(4))) TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &, const __attribute__((address_space(4))) char *at) {
-    return *(const __attribute__((address_space(4))) TdsStepCtl *)at;
-  }
-};
-template <typename P>
-__device__ __forceinline__ P *oct_global(P *p) {  // a loaded pointer: not LDS, not scratch (global_ instead of flat_ accesses)
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_assume(!__builtin_amdgcn_is_shared((const void *)p) && !__builtin_amdgcn_is_private((const void *)p));
-#endif
-  return p;
-}
-
 // the constants of the model as the kernel reads them: one table in LDS behind the environments' regions, copied from
 // DevModel::oct_tab (laid out by tds_build_oct_table on the host: tds_device_model.h, TDS_OCT_*) at the top of a launch
 using TB = TdsOctTab;
@@ -372,7 +314,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   const int leg = lane >> 1, pos = lane & 1;
   const int dq = 6 + lane;  // my dof in the q / qd records
   const T *const CL = CT + lane * TB::LSTR;  // my lane's constants
-  typename OctCtlRef<LOOP>::type ctl = OctCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(OctKernArgs, ctl));
+  typename TdsCtlRef<LOOP>::type ctl = TdsCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(OctKernArgs, ctl));
   const T dt = CT[TB::SC + TB::DT];
   const int pgs_iters = (int)CT[TB::SC + TB::PGS_ITERATIONS];
   const bool last = it == nsteps - 1;
@@ -456,7 +398,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // joint's angle is multiplied by 0), t_J = S_linear q (zero for a revolute joint) — every joint type of link.hpp:229-287
       // without a branch; X_parent = X_T X_J, and where every X_T rotation is the identity (the Ant) no product at all
       T sn, cs;
-      oct_sincos(q * CL[TB::ROTF], &sn, &cs);
+      tds_sincos(q * CL[TB::ROTF], &sn, &cs);
       const T c1 = T(1) - cs;
       const T nx = CL[TB::NAX], ny = CL[TB::NAX + 1], nz = CL[TB::NAX + 2];
       T RJ[9];
@@ -490,7 +432,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     //         environment, broadcast (and, two-wavefront build, handed to the helper behind the links' world transforms)
     {
       T rs, rc;
-      oct_sincos(xr[3 + (lane < 3 ? lane : 0)], &rs, &rc);
+      tds_sincos(xr[3 + (lane < 3 ? lane : 0)], &rs, &rc);
       const T sx = oct_bcast<0>(rs), cx = oct_bcast<0>(rc);
       const T sy = oct_bcast<1>(rs), cy = oct_bcast<1>(rc);
       const T sz = oct_bcast<2>(rs), cz = oct_bcast<2>(rc);
@@ -630,7 +572,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     yend = ystr;
     yend2 = out_dim;
     if (LOOP && ctl.y_ring != nullptr) {
-      yo = oct_global((TR *)ctl.y_ring) + ((size_t)ys * ctl.ring_envs + env) * ystr;
+      yo = tds_global((TR *)ctl.y_ring) + ((size_t)ys * ctl.ring_envs + env) * ystr;
       if (last && y_out != nullptr) yo2 = y_out + (size_t)env * out_dim;
     } else if (last && y_out != nullptr) {
       yo = y_out + (size_t)env * (LOOP ? out_dim : ystr);
@@ -639,81 +581,26 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   // ---- exchange launches of the multi-GPU layer (tds_shard.hip): the records of a step are counted in on the slot's progress
   //      counter (RCCL forms), or on its arrival counters with the flags of every rank raised by the workgroup that
-  //      completes the slot (peer-store exchange; see tds_kernels.hip: peer_signal)
-  auto signal_slot = [&](int pslot) {
-    if (ctl.peer_arrive != nullptr) {
-      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): every store of this wavefront acknowledged by the memory it went to
-      const bool rel = (ctl.ring_flags & TDS_RING_PEER_RELEASE) != 0;  // (A/B switch for the first run on a fabric: tds_kernels.h)
-      if (rel) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      if ((tid & 63) == 0) {
-        constexpr unsigned SUB = TDS_PEER_SUB;
-        const unsigned g = gridDim.x, j = blockIdx.x % SUB;
-        const unsigned n1 = (g - j + SUB - 1u) / SUB;  // workgroups that count on first-level counter j
-        const unsigned n2 = g < SUB ? g : SUB;          // first-level counters in use
-        unsigned *const base = oct_global(ctl.peer_arrive) + (size_t)pslot * TDS_PEER_ARRIVE_STRIDE;
-        if (atomicInc(base + j * TDS_PEER_LINE, n1 - 1u) == n1 - 1u) {
-          if (atomicInc(base + 32 * TDS_PEER_LINE, n2 - 1u) == n2 - 1u) {
-            const size_t fi = (size_t)ctl.peer_flag_off + (size_t)pslot * (size_t)ctl.peer_flag_stride;
-            if (rel) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "");
-            for (int pr = 0; pr <= ctl.n_peers; ++pr)
-              __hip_atomic_store(ctl.peer_flags[pr] + fi, ctl.peer_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          }
-        }
-      }
-    } else if (ctl.progress != nullptr) {
-      if (ctl.ring_flags & TDS_RING_NOFENCE) __builtin_amdgcn_s_waitcnt(0x0f70);  // (write-through record stores)
-      else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      if ((tid & 63) == 0) __hip_atomic_fetch_add(oct_global(ctl.progress) + pslot, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
-
-  // The peer form's count in two halves: the first-level atomic (with return) is ISSUED behind barrier (1) — the records of
+  //      completes the slot (peer-store exchange): tds_step_shared.h.
+  // The peer form's count goes in two halves: the first-level atomic (with return) is ISSUED behind barrier (1) — the records of
   // step it - 1 went out a kinematics phase ago — and its result is looked at in front of the visual poses (help_poses): as
   // one piece there, the helper waited for the atomic's round trip to the L2 between barriers (1b) and (2), where the main
   // wavefront waits for the helper
   unsigned sig_tok = 0u;
-  auto signal_issue = [&](int pslot) {
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    if ((ctl.ring_flags & TDS_RING_PEER_RELEASE) != 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    if ((tid & 63) == 0) {
-      constexpr unsigned SUB = TDS_PEER_SUB;
-      const unsigned g = gridDim.x, j = blockIdx.x % SUB;
-      const unsigned n1 = (g - j + SUB - 1u) / SUB;
-      unsigned *const base = oct_global(ctl.peer_arrive) + (size_t)pslot * TDS_PEER_ARRIVE_STRIDE;
-      sig_tok = atomicInc(base + j * TDS_PEER_LINE, n1 - 1u);
-    }
-  };
-  auto signal_finish = [&](int pslot) {
-    if ((tid & 63) == 0) {
-      constexpr unsigned SUB = TDS_PEER_SUB;
-      const unsigned g = gridDim.x, j = blockIdx.x % SUB;
-      const unsigned n1 = (g - j + SUB - 1u) / SUB;
-      const unsigned n2 = g < SUB ? g : SUB;
-      unsigned *const base = oct_global(ctl.peer_arrive) + (size_t)pslot * TDS_PEER_ARRIVE_STRIDE;
-      if (sig_tok == n1 - 1u) {
-        if (atomicInc(base + 32 * TDS_PEER_LINE, n2 - 1u) == n2 - 1u) {
-          const size_t fi = (size_t)ctl.peer_flag_off + (size_t)pslot * (size_t)ctl.peer_flag_stride;
-          if ((ctl.ring_flags & TDS_RING_PEER_RELEASE) != 0) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "");
-          for (int pr = 0; pr <= ctl.n_peers; ++pr)
-            __hip_atomic_store(ctl.peer_flags[pr] + fi, ctl.peer_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-    }
-  };
 
   auto help_np = [&]() {
     OCT_MARK("help_np");
     // ================================ helper: narrowphase, visual poses ================================
     if constexpr (LOOP) {
       if (it > 0 && ctl.obs_ring != nullptr && ctl.peer_arrive != nullptr)  // (wave-uniform; in front of the action request: the wait)
-        signal_issue((o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
+        sig_tok = tds_peer_count_in(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
       // The NEXT step's action block is requested here, by the helper (a different block per step: tds_hip_step_many), and goes
       // into the record's action slots in front of the visual poses' stores (help_poses) — the slots are dead since the PD
       // block, in front of barrier (1); the next PD block is behind barrier (0).  Requested by the main wavefront and held
       // until the integration, the value crossed the whole step in a register: the 256-register build spilled it to scratch
       // at the top of the step — a wait for the load itself — and reloaded it on the main wavefront's path
       if (ctl.act_pool != nullptr && it + 1 < nsteps && valid)  // (wave-uniform but for `valid`)
-        next_act = (T)oct_global((const TR *)ctl.act_pool)[((size_t)act_blk * ctl.act_envs + env) * adim + lane];
+        next_act = (T)tds_global((const TR *)ctl.act_pool)[((size_t)act_blk * ctl.act_envs + env) * adim + lane];
     }
     if constexpr (W2) {  // my link's world transform and the root's sines / cosines, from the main wavefront
       const T *const kin = E + O.win + 8 * OctLds::ZW + lane * 12;
@@ -795,8 +682,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // the records of step it - 1 — stored at the end of the iteration before, long acknowledged by now: the wait costs
       // nothing here, in front of this step's first stores — are counted in
       if (it > 0 && ctl.obs_ring != nullptr) {  // (wave-uniform)
-        if (ctl.peer_arrive != nullptr) signal_finish((o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
-        else signal_slot((o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
+        if (ctl.peer_arrive != nullptr) tds_peer_finish(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1, sig_tok);
+        else tds_signal_slot(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
       }
     }
     // ---- M1. visual poses of y, from the PRE-step X_world (locomotion_contact_simulation.h:281-299): visual 1 + lane is
@@ -1438,7 +1325,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         if (yo2 != nullptr) y_state(yo2, yend2);
       }
       const unsigned c = ctl.reset_count[env];
-      const TR *const src = oct_global((const TR *)ctl.pool) + ((size_t)(c % (unsigned)ctl.pool_depth) * ctl.pool_envs + env) * (nq + nd);
+      const TR *const src = tds_global((const TR *)ctl.pool) + ((size_t)(c % (unsigned)ctl.pool_depth) * ctl.pool_envs + env) * (nq + nd);
       T v0 = (T)src[lane], v1 = (T)src[lane + 8], v2 = (T)src[lane + 16], v3 = T(0);
       if (lane + 24 < nq + nd) v3 = (T)src[lane + 24];
       OCT_SYNC();
@@ -1481,7 +1368,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           // on a float wire): every lane takes 8 bytes of the row — read from the environments' LDS records, converted
           // once — and the row goes out with one 8-byte-per-lane store instruction per destination and pass: this rank's
           // own block (device scope, write-through), then every peer's (system scope, over xGMI), the table's pointers by
-          // scalar loads (see tds_kernels.hip: put_obs_wide)
+          // scalar loads (see tds_step_shared.h: tds_obs_store_wide, the same store)
           const int wl = tid & 63;
           const size_t row0 = ((size_t)slot * ctl.obs_envs + (size_t)blockIdx.x * 8) * (size_t)w_obs;
           const int per_unit = f32w ? 2 : 1;
@@ -1514,13 +1401,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             }
             const unsigned long long bits = ((unsigned long long)hi << 32) | (unsigned long long)lo;
             const size_t unit_at = row0 / per_unit + (size_t)uu;  // (row0 is a multiple of per_unit: TDS_RING_WIDE)
-            if (on) __hip_atomic_store(oct_global((unsigned long long *)ctl.obs_ring) + unit_at, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (on) __hip_atomic_store(tds_global((unsigned long long *)ctl.obs_ring) + unit_at, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (reward | done only: a unit travels if ANY of its columns is one of the two — on a float wire they may share a
             //  unit with an observation column)
             const bool to_peers = on && (!rd_only || tail);
             for (int p0 = 0; p0 < np; p0 += 4) {  // (the table is padded to a multiple of four entries)
-              const unsigned long long *const b0 = oct_global(tab[p0]), *const b1 = oct_global(tab[p0 + 1]), *const b2 = oct_global(tab[p0 + 2]),
-                                       *const b3 = oct_global(tab[p0 + 3]);
+              const unsigned long long *const b0 = tds_global(tab[p0]), *const b1 = tds_global(tab[p0 + 1]), *const b2 = tds_global(tab[p0 + 2]),
+                                       *const b3 = tds_global(tab[p0 + 3]);
               const size_t po = (size_t)ctl.peer_off / 8 + unit_at;
               if (to_peers) {
                 using G64 = __attribute__((address_space(1))) unsigned long long;
@@ -1548,17 +1435,17 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             const T vv = ov[k];
             // (TDS_RING_NOFENCE: device-scope write-through stores, visible to the exchange after a plain wait)
             if (rf & TDS_RING_OBS_F32) {
-              float *const pp = oct_global((float *)ctl.obs_ring) + at + i;
+              float *const pp = tds_global((float *)ctl.obs_ring) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               else OCT_ST((float)vv, pp);
             } else {
-              TR *const pp = oct_global((TR *)ctl.obs_ring) + at + i;
+              TR *const pp = tds_global((TR *)ctl.obs_ring) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               else OCT_ST((TR)vv, pp);
             }
             if (np > 0 && (i >= nq + nd || !rd_only)) {
               for (int pr = 0; pr < np; ++pr) {
-                char *const pb = (char *)oct_global(((void *const __attribute__((address_space(4))) *)(const __attribute__((address_space(4))) void *)ctl.peer_ring)[pr]) + ctl.peer_off;
+                char *const pb = (char *)tds_global(((void *const __attribute__((address_space(4))) *)(const __attribute__((address_space(4))) void *)ctl.peer_ring)[pr]) + ctl.peer_off;
                 if (rf & TDS_RING_OBS_F32) __hip_atomic_store((float *)pb + (at + i), (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 else __hip_atomic_store((TR *)pb + (at + i), (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
               }
@@ -1567,7 +1454,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         }
         // (peer-store exchange: EVERY step is counted in — the last one here, by the wavefront that has just stored it; kernel
         //  completion would tell this rank, not the peers)
-        if (last && ctl.peer_arrive != nullptr) signal_slot(slot);
+        if (last && ctl.peer_arrive != nullptr) tds_signal_slot(ctl, slot);
       }
     }
     if (valid && last) {

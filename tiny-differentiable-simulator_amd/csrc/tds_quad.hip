@@ -41,6 +41,7 @@
 #include "tds_device_model.h"
 #include "tds_kernels.h"
 #include "tds_lanes.h"
+#include "tds_step_shared.h"
 
 namespace {
 
@@ -57,42 +58,6 @@ template <int K>
 __device__ __forceinline__ float quad_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), K * 0x55, 0xF, 0xF, true));
 }
-
-// sin and cos of a joint angle: Cody-Waite reduction by pi / 2 in two fused steps and the fdlibm kernels on [-pi/4, pi/4]
-// (< 1 ulp; ~35 instructions where the library routine takes ~90); lanes beyond 1e5 rad — or NaN — take the library routine
-// without changing what the other lanes of the wavefront compute (see tds_oct.hip: oct_sincos)
-__device__ __forceinline__ void quad_sincos(double x, double *sn, double *cs) {
-  const bool big = !(__builtin_fabs(x) < 1.0e5);
-  const double k = __builtin_rint(x * 6.36619772367581382433e-01);
-  double r = __builtin_fma(-k, 1.57079632679489655800e+00, x);
-  r = __builtin_fma(-k, 6.12323399573676603587e-17, r);
-  const int q = (int)k;
-  const double z = r * r;
-  double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-  ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-  ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-  ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-  ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
-  const double s0 = __builtin_fma(z * r, ps, r);
-  double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-  pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-  pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-  pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-  pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
-  const double c0 = __builtin_fma(z * z, pc, __builtin_fma(z, -0.5, 1.0));
-  const bool swap = (q & 1) != 0;
-  const double ss = swap ? c0 : s0, cc = swap ? s0 : c0;
-  double s_ = (q & 2) ? -ss : ss, c_ = ((q + 1) & 2) ? -cc : cc;
-  if (__builtin_expect(__any(big), 0)) {
-    double s2, c2;
-    sincos(x, &s2, &c2);
-    s_ = big ? s2 : s_;
-    c_ = big ? c2 : c_;
-  }
-  *sn = s_;
-  *cs = c_;
-}
-__device__ __forceinline__ void quad_sincos(float x, float *sn, float *cs) { sincosf(x, sn, cs); }
 
 // launder a model pointer WITHOUT losing its address space (laundered as a generic pointer every access behind it is a FLAT
 // load: both counters, out of order with the DS instructions — see tds_kernels.hip)
@@ -169,18 +134,6 @@ struct QuadTable {
 // constant `tab` of the table in a step-loop launch, `glob` of the model otherwise
 #define QC(tab, glob) (LOOP ? (CT->tab) : (mdl->glob))
 
-template <bool LOOP>
-struct QuadCtlRef {
-  using type = const TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &param, const __attribute__((address_space(4))) char *) { return param; }
-};
-template <>
-struct QuadCtlRef<true> {
-  using type = const __attribute__((address_space(4))) TdsStepCtl &;
-  static __device__ __forceinline__ type get(const TdsStepCtl &, const __attribute__((address_space(4))) char *at) {
-    return *(const __attribute__((address_space(4))) TdsStepCtl *)at;
-  }
-};
 __host__ __device__ inline QuadOff quad_layout(int in_dim) {
   QuadOff o;
   int at = in_dim + 4;
@@ -357,7 +310,7 @@ void tds_quad_kernel(const DevModel<T> *__restrict__ mdl_arg, const TR *x_in, TR
   const int dq = 6 + 3 * leg + pos;   // ... this one, in the q / qd records (nq == nd == 18)
   const int in_dim = QC(input_dim, input_dim), adim = QC(action_dim, action_dim);
   // (kernel-argument segment: mdl 0 | x_in 8 | y_out 16 | actions 24 | x_feedback 32 | obs_out 40 | ctl 48: see QuadKernArgs)
-  typename QuadCtlRef<LOOP>::type ctl = QuadCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(QuadKernArgs, ctl));
+  typename TdsCtlRef<LOOP>::type ctl = TdsCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(QuadKernArgs, ctl));
   const T dt = QC(dt, dt);
   const bool last = it == nsteps - 1;
   if constexpr (LOOP) {
@@ -414,7 +367,7 @@ void tds_quad_kernel(const DevModel<T> *__restrict__ mdl_arg, const TR *x_in, TR
   T Rp[9], tp[3], sn, cs;
   {
     const T ang = dofl ? (jt == TDS_JOINT_REVOLUTE_AXIS ? q * T(0.5) : q) : xr[3 + (leg < 3 ? leg : 0)];
-    quad_sincos(ang, &sn, &cs);
+    tds_sincos(ang, &sn, &cs);
     const bool rev = jt >= TDS_JOINT_REVOLUTE_X && jt <= TDS_JOINT_REVOLUTE_AXIS;
     const bool pris = jt >= TDS_JOINT_PRISMATIC_X && jt <= TDS_JOINT_PRISMATIC_AXIS;
     T RJ[9] = {T(1), T(0), T(0), T(0), T(1), T(0), T(0), T(0), T(1)};
@@ -1299,7 +1252,7 @@ void tds_quad_kernel(const DevModel<T> *__restrict__ mdl_arg, const TR *x_in, TR
     //  cos(roll) cos(pitch) — two cosines and a product instead of three half-angle sincos and the quaternion's 30 products;
     //  to rounding the same number, and `done` compares it with 0.6)
     T rs = T(0), rc = T(1);
-    quad_sincos(lane < 2 ? xr[3 + lane] : T(0), &rs, &rc);
+    tds_sincos(lane < 2 ? xr[3 + lane] : T(0), &rs, &rc);
     const T c1 = dpp_bcast<1>(rc);
     if (lane == 0) {
       bool done = false;

@@ -126,8 +126,8 @@ __global__ void tds_ring_wait_kernel(const unsigned long long *progress, unsigne
 // Peer-store exchange (round 5): the all-gather without a collective.  Every rank maps the other ranks' gathered rings and
 // flag arrays into its address space (hipIpcGetMemHandle / hipIpcOpenMemHandle, handles exchanged once over the
 // communicator); the step-loop launch stores each [obs | reward | done] record into its own block of the slot on EVERY
-// rank and raises the slot's flag on every rank when its last workgroup has stored it (tds_kernels.hip: put_obs,
-// peer_signal).  What is left for the streams are three one-wavefront kernels per LAUNCH (not per step), none of which
+// rank and raises the slot's flag on every rank when its last workgroup has stored it (tds_step_shared.h: tds_obs_store_*,
+// tds_peer_finish).  What is left for the streams are three one-wavefront kernels per LAUNCH (not per step), none of which
 // runs beside the launch it belongs to:
 //   credit   (step stream, in front of launch m) publishes "this rank has started launch m" on every rank and waits until
 //            every peer has started launch m - 1: the half of the ring launch m writes holds the records of launch m - 2,
