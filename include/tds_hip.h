@@ -651,6 +651,52 @@ int tds_hip_trajectory_jvp_host(const tds_model_t *model, int n, int steps, int 
                                 const double *u, int p, const tds_param_t *params, const double *theta, int k,
                                 const double *v, double *s, double *js);
 
+/* Batched dynamics queries (the reference's forward_kinematics, mass_matrix, forward_dynamics, point_jacobian of
+   python/pytinydiffsim.inl:629-668 and inverse_dynamics of src/dynamics/inverse_dynamics.hpp, for n states at once).
+   State q [n][dof_q], qd [n][dof_qd] (NULL: zero), f64 device pointers.  Scope and refusals are those of
+   tds_hip_jacobian (one articulated body, 1-DoF and fixed joints, f64 handles; the same messages).  Any n >= 1,
+   independent of num_envs; the handle's resident state is not touched.  Enqueued on the handle's stream with no host
+   wait except where the work buffer (shared with tds_hip_jvp, grown as needed: 8 (75 num_links + 2 dof_qd^2 + 9 dof_qd
+   + 55) bytes for each of min(n, 16384) lanes) grows.  Only the outputs whose pointers are non-NULL are computed and
+   written:
+     x_world      [n][num_links][12]     rotation (9, row-major) and translation (3) of every link
+     mass_matrix  [n][dof_qd][dof_qd]    the joint-space inertia (CRBA), both triangles
+     bias         [n][dof_qd]            ID(q, qd, 0): gravity, Coriolis and centrifugal terms (no springs or dampers);
+                                         fixed base only (TDS_ERR_UNSUPPORTED on a floating base: the reference has no
+                                         floating-base inverse dynamics)
+     qdd          [n][dof_qd]            unconstrained forward dynamics (no contacts, no PD): M = L L^T and a solve
+                                         against tau - K q - D qd - bias (joint stiffness K and damping D as the
+                                         reference's forward_dynamics has them); NaN for an environment whose M is not
+                                         positive definite
+   tau [n][dof_qd - (6 on a floating base)]: the torques of the actuated dofs, in the order the torque-actuated step
+   reads its action slots; NULL: zero. */
+typedef struct {  /* device pointers (tds_hip_dynamics) or host pointers (tds_hip_dynamics_host), each may be NULL */
+  void *x_world;
+  void *mass_matrix;
+  void *bias;
+  void *qdd;
+} tds_dyn_out_t;
+int tds_hip_dynamics(tds_hip_sim_t *sim, int n, const void *q_dev, const void *qd_dev, const void *tau_dev,
+                     const tds_dyn_out_t *out);
+/* tau [n][dof_qd] = ID(q, qd, qdd) (RNEA; qd, qdd NULL: zero): the torques that produce qdd without springs or dampers,
+   M qdd + bias to round-off.  Fixed base only (TDS_ERR_UNSUPPORTED on a floating base). */
+int tds_hip_inverse_dynamics(tds_hip_sim_t *sim, int n, const void *q_dev, const void *qd_dev, const void *qdd_dev,
+                             void *tau_dev);
+/* jac [n][3][dof_qd]: the world-frame Jacobian of a point on link `link` (one value per call; -1: the base), the point
+   [n][3] given in world coordinates or, with is_local, in the link's own frame (taken to the world with X_world).  A
+   link outside [-1, num_links) gives TDS_ERR_INVALID_ARG. */
+int tds_hip_point_jacobian(tds_hip_sim_t *sim, int n, const void *q_dev, int link, const void *point_dev, int is_local,
+                           void *jac_dev);
+/* The same templates on the CPU (host arrays, need no GPU): the checkers of the three calls above.
+   tds_hip_dynamics_host returns TDS_ERR_INVALID_ARG where some environment's M was not positive definite, after writing
+   every output (that environment's qdd NaN). */
+int tds_hip_dynamics_host(const tds_model_t *model, int n, const double *q, const double *qd, const double *tau,
+                          const tds_dyn_out_t *out);
+int tds_hip_inverse_dynamics_host(const tds_model_t *model, int n, const double *q, const double *qd, const double *qdd,
+                                  double *tau);
+int tds_hip_point_jacobian_host(const tds_model_t *model, int n, const double *q, int link, const double *point,
+                                int is_local, double *jac);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

@@ -140,8 +140,42 @@ def lib():
             [C.c_void_p] * 3
         L.tds_rb_jvp_host.argtypes = [RP, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3
+        DP = C.POINTER(DynOut)
+        L.tds_hip_dynamics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [DP]
+        L.tds_hip_inverse_dynamics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.tds_hip_point_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.tds_hip_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 3 + [DP]
+        L.tds_hip_inverse_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 4
+        L.tds_hip_point_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
+
+
+class DynOut(C.Structure):
+    """tds_dyn_out_t: the outputs of a dynamics query, each pointer NULL where the output is not wanted"""
+    _fields_ = [("x_world", C.c_void_p), ("mass_matrix", C.c_void_p), ("bias", C.c_void_p), ("qdd", C.c_void_p)]
+
+
+DYN_OUTPUTS = ("x_world", "mass_matrix", "bias", "qdd")
+
+
+def dyn_shapes(m: _model.Model, n: int) -> dict:
+    """shapes of the outputs of a dynamics query over n states"""
+    nd = m.dof_qd
+    return {"x_world": (n, m.num_links, 12), "mass_matrix": (n, nd, nd), "bias": (n, nd), "qdd": (n, nd)}
+
+
+def dyn_tau_dim(m: _model.Model) -> int:
+    """entries of a dynamics query's tau: the actuated dofs (a floating base's six are not actuated)"""
+    return m.dof_qd - (6 if m.is_floating else 0)
+
+
+def _dyn_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for k in want:
+        if k not in DYN_OUTPUTS:
+            raise ValueError(f"unknown dynamics output {k!r} (one of {DYN_OUTPUTS})")
+    return want
 
 
 class Param(C.Structure):
@@ -229,6 +263,8 @@ EXPORTED_SYMBOLS = [
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
     "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
+    "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
+    "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
 ]
@@ -353,6 +389,60 @@ def jacobian_host(m: _model.Model, x, rows=None, cols=None, accumulate=None, wan
     _check(lib().tds_hip_jacobian_host(C.byref(m), n, x.ctypes.data, nr, rp, nc, cp, acc,
                                        y.ctypes.data if want_y else None, jac.ctypes.data))
     return (jac, y) if want_y else jac
+
+
+def _host_rows(a, n, width):
+    import numpy as np
+
+    if a is None or width == 0:
+        return None, None
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1, width), (n, width)))
+    return a, a.ctypes.data
+
+
+def dynamics_host(m: _model.Model, q, qd=None, tau=None, want=DYN_OUTPUTS):
+    """The dynamics queries on the CPU (tds_hip_dynamics_host; the checker of HipSim.dynamics, needs no GPU).
+
+    q [N, dof_q], qd [N, dof_qd] (None: zero), tau [N, dyn_tau_dim(m)] (None: zero), float64.  Returns a dict of the
+    wanted outputs: x_world [N, num_links, 12], mass_matrix [N, dof_qd, dof_qd], bias [N, dof_qd], qdd [N, dof_qd]."""
+    import numpy as np
+
+    want = _dyn_want(want)
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
+    n = q.shape[0]
+    qd, qdp = _host_rows(qd, n, m.dof_qd)
+    tau, taup = _host_rows(tau, n, dyn_tau_dim(m))
+    res = {k: np.zeros(dyn_shapes(m, n)[k], dtype=np.float64) for k in want}
+    out = DynOut(**{k: v.ctypes.data for k, v in res.items()})
+    _check(lib().tds_hip_dynamics_host(C.byref(m), n, q.ctypes.data, qdp, taup, C.byref(out)))
+    return res
+
+
+def inverse_dynamics_host(m: _model.Model, q, qd=None, qdd=None):
+    """tau [N, dof_qd] = ID(q, qd, qdd) on the CPU (tds_hip_inverse_dynamics_host; None: zero); fixed base only"""
+    import numpy as np
+
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
+    n = q.shape[0]
+    qd, qdp = _host_rows(qd, n, m.dof_qd)
+    qdd, qddp = _host_rows(qdd, n, m.dof_qd)
+    tau = np.zeros((n, m.dof_qd), dtype=np.float64)
+    _check(lib().tds_hip_inverse_dynamics_host(C.byref(m), n, q.ctypes.data, qdp, qddp, tau.ctypes.data))
+    return tau
+
+
+def point_jacobian_host(m: _model.Model, q, link: int, point, local: bool = False):
+    """The world-frame Jacobian [N, 3, dof_qd] of a point [N, 3] (or [3]) on link `link` (-1: the base) on the CPU
+    (tds_hip_point_jacobian_host); local: the point is given in the link's own frame"""
+    import numpy as np
+
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
+    n = q.shape[0]
+    pt, ptp = _host_rows(point, n, 3)
+    jac = np.zeros((n, 3, m.dof_qd), dtype=np.float64)
+    _check(lib().tds_hip_point_jacobian_host(C.byref(m), n, q.ctypes.data, int(link), ptp, int(bool(local)),
+                                             jac.ctypes.data))
+    return jac
 
 
 def step_host(m: _model.Model, x):
@@ -1021,6 +1111,78 @@ class HipSim:
                                             C.c_void_p(v3.data_ptr()), C.c_void_p(s.data_ptr()),
                                             C.c_void_p(js.data_ptr())))
         return s, (js[:, 0] if squeeze else js)
+
+    # -- dynamics queries: kinematics, mass matrix, bias, forward and inverse dynamics, point Jacobians -----------
+    def _dyn_rows(self, a, n, width, what):
+        import torch
+
+        if a is None or width == 0:
+            return None, None
+        assert a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (n, width), what
+        a = a.contiguous()
+        return a, C.c_void_p(a.data_ptr())
+
+    def dynamics(self, q, qd=None, tau=None, want=DYN_OUTPUTS, out=None):
+        """The wanted ones of x_world [N, num_links, 12], mass_matrix [N, dof_qd, dof_qd], bias [N, dof_qd] and
+        qdd [N, dof_qd] at the states q [N, dof_q], qd [N, dof_qd] (None: zero), as a dict of tensors on the handle's
+        device.  tau [N, dyn_tau_dim(model)] (None: zero) are the torques of qdd, the unconstrained forward dynamics.
+        out: a dict of tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
+        import torch
+
+        want = _dyn_want(want)
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
+        q = q.contiguous()
+        n = q.shape[0]
+        qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
+        tau, taup = self._dyn_rows(tau, n, dyn_tau_dim(self.model), "tau")
+        shapes = dyn_shapes(self.model, n)
+        res = {}
+        for k in want:
+            t = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float64, device=q.device)
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k]
+            res[k] = t
+        o = DynOut(**{k: t.data_ptr() for k, t in res.items()})
+        _check(lib().tds_hip_dynamics(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, C.byref(o)))
+        return res
+
+    def forward_kinematics(self, q):
+        """x_world [N, num_links, 12]: rotation (9, row-major) and translation (3) of every link"""
+        return self.dynamics(q, want=("x_world",))["x_world"]
+
+    def mass_matrix(self, q):
+        """the joint-space inertia M(q) [N, dof_qd, dof_qd]"""
+        return self.dynamics(q, want=("mass_matrix",))["mass_matrix"]
+
+    def forward_dynamics(self, q, qd=None, tau=None):
+        """qdd [N, dof_qd] without contacts or PD control: M^-1 (tau - K q - D qd - bias)"""
+        return self.dynamics(q, qd, tau, want=("qdd",))["qdd"]
+
+    def inverse_dynamics(self, q, qd=None, qdd=None):
+        """tau [N, dof_qd] = ID(q, qd, qdd) (None: zero), without springs or dampers; fixed base only (async)"""
+        import torch
+
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
+        q = q.contiguous()
+        n = q.shape[0]
+        qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
+        qdd, qddp = self._dyn_rows(qdd, n, self.model.dof_qd, "qdd")
+        tau = torch.empty((n, self.model.dof_qd), dtype=torch.float64, device=q.device)
+        _check(lib().tds_hip_inverse_dynamics(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, C.c_void_p(tau.data_ptr())))
+        return tau
+
+    def point_jacobian(self, q, link: int, point, local: bool = False):
+        """The world-frame Jacobian [N, 3, dof_qd] of the points [N, 3] on link `link` (-1: the base); local: the points
+        are given in the link's own frame (async)"""
+        import torch
+
+        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
+        q = q.contiguous()
+        n = q.shape[0]
+        point, ptp = self._dyn_rows(point, n, 3, "point")
+        jac = torch.empty((n, 3, self.model.dof_qd), dtype=torch.float64, device=q.device)
+        _check(lib().tds_hip_point_jacobian(self.h, n, C.c_void_p(q.data_ptr()), int(link), ptp, int(bool(local)),
+                                            C.c_void_p(jac.data_ptr())))
+        return jac
 
     def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
         """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
