@@ -697,6 +697,46 @@ int tds_hip_inverse_dynamics_host(const tds_model_t *model, int n, const double 
 int tds_hip_point_jacobian_host(const tds_model_t *model, int n, const double *q, int link, const double *point,
                                 int is_local, double *jac);
 
+/* Batched inverse kinematics (the reference's TinyInverseKinematics::compute of src/tiny_inverse_kinematics.h:140-247,
+   for n environments at once): from q_init [n][dof_q], move the actuated coordinates until the k body points (link
+   links[j], point body_points[j][3] in the link's own frame; the same for every environment) reach
+   targets [n][k][3] (world coordinates).  Each iteration: kinematics of q, J [3k][dof_qd] (a floating base's six
+   columns zeroed) and e [3k] = target - actual, residual = |e|; residual < target_tolerance stops with REACHED;
+   otherwise delta = J^T e (TRANSPOSE), J^+ e (PINV, the Moore-Penrose inverse: rank-deficient J is served) or
+   J^T (J J^T + lambda^2 I)^-1 e (DAMPED_LM, lambda != 0), q_i += alpha delta_i and, with q_ref,
+   q_i += weight_reference (q_ref_i - q_i) on the actuated coordinates (all of a fixed base's, q[7:] of a floating
+   base's: the base pose is returned as given); sum delta_i^2 < step_tolerance^2 stops with CONVERGED; after
+   max_iterations the status is FAILED.  An environment whose q stops being finite is FAILED with iterations =
+   max_iterations, the others are not affected.  Outputs: q [n][dof_q] (f64), iterations [n], status [n] (int32) and
+   residual [n] (f64; -1 for an environment that never iterated); the last three may be NULL.
+   Scope and refusals are those of tds_hip_jacobian (the same messages); 1 <= k <= TDS_IK_MAX_TARGETS, links in
+   [0, num_links), max_iterations >= 0, a known method, lambda != 0 with DAMPED_LM: otherwise TDS_ERR_INVALID_ARG.
+   links, body_points (NULL: the links' origins) and opt (NULL: the defaults) are host pointers, read before the call
+   returns.  Any n >= 1; enqueued on the handle's stream as ONE launch, no host wait except where the work buffer
+   shared with tds_hip_jvp and tds_hip_dynamics grows. */
+#define TDS_IK_MAX_TARGETS 4
+enum { TDS_IK_TRANSPOSE = 0, TDS_IK_PINV = 1, TDS_IK_DAMPED_LM = 2 };    /* the reference's TinyIKMethod */
+enum { TDS_IK_FAILED = 0, TDS_IK_CONVERGED = 1, TDS_IK_REACHED = 2 };    /* the reference's TinyIKStatus */
+typedef struct {
+  int32_t method;          /* TDS_IK_*; tds_hip_ik_default_options: TDS_IK_PINV */
+  int32_t max_iterations;  /* 20 */
+  double lambda;           /* 0.02   damping of DAMPED_LM */
+  double target_tolerance; /* 1e-3   |e| below which the targets count as reached */
+  double step_tolerance;   /* 1e-8   |delta| below which the iteration counts as converged */
+  double alpha;            /* 5      step size */
+  double weight_reference; /* 0.2    pull towards q_ref (used only where q_ref is given) */
+} tds_ik_options_t;
+void tds_hip_ik_default_options(tds_ik_options_t *opt);
+int tds_hip_inverse_kinematics(tds_hip_sim_t *sim, int n, const void *q_init_dev, int k, const int32_t *links,
+                               const double *body_points, const void *targets_dev, const void *q_ref_dev,
+                               const tds_ik_options_t *opt, void *q_dev, void *iter_dev, void *status_dev,
+                               void *residual_dev);
+/* The same statement on the CPU (host arrays, needs no GPU): the checker of tds_hip_inverse_kinematics. */
+int tds_hip_inverse_kinematics_host(const tds_model_t *model, int n, const double *q_init, int k, const int32_t *links,
+                                    const double *body_points, const double *targets, const double *q_ref,
+                                    const tds_ik_options_t *opt, double *q, int32_t *iterations, int32_t *status,
+                                    double *residual);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

@@ -147,6 +147,13 @@ def lib():
         L.tds_hip_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 3 + [DP]
         L.tds_hip_inverse_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 4
         L.tds_hip_point_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        IP = C.POINTER(IkOptions)
+        L.tds_hip_ik_default_options.argtypes = [IP]
+        L.tds_hip_ik_default_options.restype = None
+        ik_tail = [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, IP] + \
+            [C.c_void_p] * 4
+        L.tds_hip_inverse_kinematics.argtypes = [C.c_void_p] + ik_tail
+        L.tds_hip_inverse_kinematics_host.argtypes = [P] + ik_tail
         _lib = L
     return _lib
 
@@ -157,6 +164,51 @@ class DynOut(C.Structure):
 
 
 DYN_OUTPUTS = ("x_world", "mass_matrix", "bias", "qdd")
+
+
+class IkOptions(C.Structure):
+    """tds_ik_options_t: the settings of an inverse-kinematics call (defaults: tds_hip_ik_default_options)"""
+    _fields_ = [("method", C.c_int32), ("max_iterations", C.c_int32), ("lambda_", C.c_double),
+                ("target_tolerance", C.c_double), ("step_tolerance", C.c_double), ("alpha", C.c_double),
+                ("weight_reference", C.c_double)]
+
+
+IK_MAX_TARGETS = 4
+IK_TRANSPOSE, IK_PINV, IK_DAMPED_LM = 0, 1, 2    # TDS_IK_*: the reference's TinyIKMethod
+IK_FAILED, IK_CONVERGED, IK_REACHED = 0, 1, 2    # the reference's TinyIKStatus
+IK_METHODS = {"transpose": IK_TRANSPOSE, "pinv": IK_PINV, "damped_lm": IK_DAMPED_LM}
+IK_OPTIONS = ("max_iterations", "lambda_", "target_tolerance", "step_tolerance", "alpha", "weight_reference")
+
+
+def ik_options(method="pinv", **options) -> IkOptions:
+    """the library's defaults with `method` (a name of IK_METHODS or a TDS_IK_* code) and the given IK_OPTIONS set
+    (`lambda` is spelled lambda_ or lam)"""
+    o = IkOptions()
+    lib().tds_hip_ik_default_options(C.byref(o))
+    if isinstance(method, str):
+        if method not in IK_METHODS:
+            raise ValueError(f"unknown inverse-kinematics method {method!r} (one of {tuple(IK_METHODS)})")
+        method = IK_METHODS[method]
+    o.method = int(method)
+    if "lam" in options:
+        options["lambda_"] = options.pop("lam")
+    for k, v in options.items():
+        if k not in IK_OPTIONS:
+            raise ValueError(f"unknown inverse-kinematics option {k!r} (one of {IK_OPTIONS})")
+        setattr(o, k, v)
+    return o
+
+
+def _ik_targets(links, body_points):
+    """links [K] and body_points [K, 3] (None: the links' origins) as the C arrays of an inverse-kinematics call"""
+    import numpy as np
+
+    links = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1))
+    k = links.shape[0]
+    pts = np.zeros((k, 3)) if body_points is None else np.ascontiguousarray(body_points, dtype=np.float64)
+    if pts.shape != (k, 3):
+        raise ValueError(f"body_points must be [{k}, 3]")
+    return k, links, pts, links.ctypes.data_as(C.POINTER(C.c_int32)), pts.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def dyn_shapes(m: _model.Model, n: int) -> dict:
@@ -265,6 +317,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
     "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
+    "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
 ]
@@ -443,6 +496,32 @@ def point_jacobian_host(m: _model.Model, q, link: int, point, local: bool = Fals
     _check(lib().tds_hip_point_jacobian_host(C.byref(m), n, q.ctypes.data, int(link), ptp, int(bool(local)),
                                              jac.ctypes.data))
     return jac
+
+
+def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points=None, q_reference=None,
+                            method="pinv", **options):
+    """Batched inverse kinematics on the CPU (tds_hip_inverse_kinematics_host; the checker of
+    HipSim.inverse_kinematics, needs no GPU).
+
+    q_init [N, dof_q], links [K] (1 <= K <= 4), targets [N, K, 3] in world coordinates, body_points [K, 3] in the
+    links' own frames (None: their origins), q_reference [N, dof_q] or None, method "transpose" / "pinv" / "damped_lm",
+    options of IK_OPTIONS.  Returns a dict: q [N, dof_q] float64, iterations [N] and status [N] int32 (IK_FAILED /
+    IK_CONVERGED / IK_REACHED), residual [N] float64."""
+    import numpy as np
+
+    q_init = np.ascontiguousarray(q_init, dtype=np.float64).reshape(-1, m.dof_q)
+    n = q_init.shape[0]
+    k, links, pts, lp, pp = _ik_targets(links, body_points)
+    targets = np.asarray(targets, dtype=np.float64).reshape((-1, k, 3) if k else (n, 0, 3))
+    targets = np.ascontiguousarray(np.broadcast_to(targets, (n, k, 3)))
+    qr, qrp = _host_rows(q_reference, n, m.dof_q)
+    o = ik_options(method, **options)
+    res = {"q": np.zeros((n, m.dof_q)), "iterations": np.zeros(n, dtype=np.int32), "status": np.zeros(n, dtype=np.int32),
+           "residual": np.zeros(n)}
+    _check(lib().tds_hip_inverse_kinematics_host(C.byref(m), n, q_init.ctypes.data, k, lp, pp, targets.ctypes.data, qrp,
+                                                 C.byref(o), res["q"].ctypes.data, res["iterations"].ctypes.data,
+                                                 res["status"].ctypes.data, res["residual"].ctypes.data))
+    return res
 
 
 def step_host(m: _model.Model, x):
@@ -1183,6 +1262,42 @@ class HipSim:
         _check(lib().tds_hip_point_jacobian(self.h, n, C.c_void_p(q.data_ptr()), int(link), ptp, int(bool(local)),
                                             C.c_void_p(jac.data_ptr())))
         return jac
+
+    def inverse_kinematics(self, q_init, links, targets, body_points=None, q_reference=None, method="pinv", out=None,
+                           **options):
+        """Batched inverse kinematics (tds_hip_inverse_kinematics: the reference's TinyInverseKinematics::compute for
+        every environment, one launch): from q_init [N, dof_q], move the actuated coordinates until the points
+        body_points [K, 3] (the links' own frames; None: their origins) of links [K] (1 <= K <= 4) reach
+        targets [N, K, 3] (world coordinates).  q_reference [N, dof_q] (optional) pulls towards a configuration;
+        method "transpose" / "pinv" / "damped_lm"; options of IK_OPTIONS.  Returns a dict of tensors on the handle's
+        device: q [N, dof_q] float64, iterations [N] and status [N] int32 (IK_FAILED / IK_CONVERGED / IK_REACHED),
+        residual [N] float64.  out: a dict of tensors to write into; one that names q but leaves out iterations,
+        status or residual has those not computed.  Any N; f64 handles only (async)."""
+        import torch
+
+        assert q_init.is_cuda and q_init.dtype == torch.float64 and q_init.dim() == 2 and q_init.shape[1] == self.model.dof_q
+        q_init = q_init.contiguous()
+        n = q_init.shape[0]
+        k, links, pts, lp, pp = _ik_targets(links, body_points)
+        assert targets.is_cuda and targets.dtype == torch.float64 and tuple(targets.shape) == (n, k, 3), "targets"
+        targets = targets.contiguous()
+        q_reference, qrp = self._dyn_rows(q_reference, n, self.model.dof_q, "q_reference")
+        o = ik_options(method, **options)
+        shapes = {"q": ((n, self.model.dof_q), torch.float64), "iterations": ((n,), torch.int32),
+                  "status": ((n,), torch.int32), "residual": ((n,), torch.float64)}
+        res = {}
+        for name, (shape, dt) in shapes.items():
+            if out is not None and name not in out:
+                assert name != "q", "out must hold q"
+                continue
+            t = out[name] if out is not None else torch.empty(shape, dtype=dt, device=q_init.device)
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, name
+            res[name] = t
+        ptr = {name: C.c_void_p(t.data_ptr()) for name, t in res.items()}
+        _check(lib().tds_hip_inverse_kinematics(self.h, n, C.c_void_p(q_init.data_ptr()), k, lp, pp,
+                                                C.c_void_p(targets.data_ptr()), qrp, C.byref(o), ptr["q"],
+                                                ptr.get("iterations"), ptr.get("status"), ptr.get("residual")))
+        return res
 
     def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
         """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
