@@ -21,6 +21,7 @@ typedef TinyAlgebra<float, ::TINY::FloatUtils> AlgF;
 
 #include "ant_environment2.h"
 #include "laikago_environment2.h"
+#include "tds_hip.h"
 
 namespace {
 
@@ -133,6 +134,63 @@ void tdsref_f32_step(void *h, int n, int in_dim, int out_dim, const double *x, d
       s->generic_step(xe, ye);
     }
   }
+}
+
+// Free rigid bodies in float: the float twin of tdsref_rb_step (ref_harness.cpp) — the reference's World<AlgF>::step on
+// RigidBody<AlgF> objects for n worlds described by the same tds_rb_model_t, every model value rounded to float on
+// entry; state[n][num_bodies][13] floats = position | quaternion xyzw | linear | angular velocity.
+int tdsref_f32_rb_step(const tds_rb_model_t *m, int n, int steps, float *state) {
+  typedef RigidBody<AlgF> RB;
+  for (int e = 0; e < n; ++e) {
+    World<AlgF> world;
+    world.set_gravity(AlgF::Vector3((float)m->gravity[0], (float)m->gravity[1], (float)m->gravity[2]));
+    world.num_solver_iterations = m->solver_iterations;
+    world.default_friction = (float)m->friction;
+    world.default_restitution = (float)m->restitution;
+    world.get_rb_constraint_solver()->erp_ = (float)m->erp;
+    std::vector<RB *> bodies;
+    float *S = state + (size_t)e * m->num_bodies * 13;
+    for (int i = 0; i < m->num_bodies; ++i) {
+      const tds_rb_body_t &b = m->bodies[i];
+      const Geometry<AlgF> *g;
+      if (b.geom_type == TDS_GEOM_SPHERE) {
+        g = world.create_sphere((float)b.radius);
+      } else if (b.geom_type == TDS_GEOM_CAPSULE) {
+        g = world.create_capsule((float)b.radius, (float)b.length);
+      } else if (b.geom_type == TDS_GEOM_BOX) {
+        Box<AlgF> *bx = world.create_box(AlgF::Vector3((float)b.extents[0], (float)b.extents[1], (float)b.extents[2]));
+        bx->set_radius((float)b.radius);
+        g = bx;
+      } else {
+        Plane<AlgF> *pl = world.create_plane();
+        *pl = Plane<AlgF>(AlgF::Vector3((float)b.plane_normal[0], (float)b.plane_normal[1], (float)b.plane_normal[2]),
+                          (float)b.plane_constant);
+        g = pl;
+      }
+      RB *rb = world.create_rigid_body((float)b.mass, g);
+      const float *B = S + i * 13;
+      rb->world_pose_.position_ = AlgF::Vector3(B[0], B[1], B[2]);
+      rb->world_pose_.orientation_ = AlgF::quat_from_xyzw(B[3], B[4], B[5], B[6]);
+      rb->linear_velocity_ = AlgF::Vector3(B[7], B[8], B[9]);
+      rb->angular_velocity_ = AlgF::Vector3(B[10], B[11], B[12]);
+      bodies.push_back(rb);
+    }
+    for (int s = 0; s < steps; ++s) world.step((float)m->dt);
+    for (int i = 0; i < m->num_bodies; ++i) {
+      float *B = S + i * 13;
+      const RB *rb = bodies[i];
+      for (int k = 0; k < 3; ++k) {
+        B[k] = rb->world_pose_.position_[k];
+        B[7 + k] = rb->linear_velocity_[k];
+        B[10 + k] = rb->angular_velocity_[k];
+      }
+      B[3] = rb->world_pose_.orientation_.x();
+      B[4] = rb->world_pose_.orientation_.y();
+      B[5] = rb->world_pose_.orientation_.z();
+      B[6] = rb->world_pose_.orientation_.w();
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

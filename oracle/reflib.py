@@ -70,6 +70,8 @@ def lib():
             L.tdsref_f32_create.argtypes = [C.c_char_p, C.c_char_p, C.c_double]
             L.tdsref_f32_destroy.argtypes = [C.c_void_p]
             L.tdsref_f32_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "tdsref_f32_rb_step"):
+            L.tdsref_f32_rb_step.argtypes = [C.POINTER(tds_amd.RbModel), C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -186,6 +188,16 @@ def rb_step(model, state, steps=1):
     rc = lib().tdsref_rb_step(C.byref(model), st.shape[0], int(steps), st.ctypes.data)
     if rc:
         raise RuntimeError(f"tdsref_rb_step rc={rc}")
+    return st
+
+
+def rb_step_f32(model, state, steps=1):
+    """the reference's own FLOAT World::step on RigidBody objects (TinyAlgebra<float, FloatUtils>,
+    oracle/ref_harness_f32.cpp); state [n, num_bodies, 13] is rounded to float32 on entry, the result is float32"""
+    st = np.array(state, dtype=np.float32, order="C", copy=True).reshape(-1, model.num_bodies, 13)
+    rc = lib().tdsref_f32_rb_step(C.byref(model), st.shape[0], int(steps), st.ctypes.data)
+    if rc:
+        raise RuntimeError(f"tdsref_f32_rb_step rc={rc}")
     return st
 
 

@@ -1505,10 +1505,11 @@ static void rb_world_step(const tds_rb_model_t *m, double *S /* [nb][13] */) {
         rb_contact_t c;
         int got;
         if (kind == 0) {
-          /* Plane's constructor normalises the normal (geometry.hpp:163-168) */
+          /* Plane's constructor normalises the normal (geometry.hpp:163-168) as v * (1 / |v|)
+             (tiny_algebra.hpp:223): a non-unit normal rounds differently under v / |v| */
           const double *pn = m->bodies[p].plane_normal;
-          const double nl = sqrt(v3_dot(pn, pn));
-          const double nn[3] = {pn[0] / nl, pn[1] / nl, pn[2] / nl};
+          const double inl = 1.0 / sqrt(v3_dot(pn, pn));
+          const double nn[3] = {pn[0] * inl, pn[1] * inl, pn[2] * inl};
           got = rb_plane_sphere(nn, m->bodies[p].plane_constant, ctr, rad, &c);
         }
         else got = rb_sphere_sphere(ctr, rad, S + q * 13, m->bodies[q].radius, &c);

@@ -297,6 +297,16 @@ int tds_rb_create(const tds_rb_model_t *model, int num_worlds, int device, int d
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return rb_fail(TDS_ERR_NO_DEVICE, "no HIP device visible (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return rb_fail(TDS_ERR_INVALID_ARG, "device index out of range");
   RB_TRY(hipSetDevice(device));
+  // The kernel's dynamic LDS passes 64 KiB at 10 bodies in f64 and needs the function's ceiling raised.  The ceiling
+  // belongs to the kernel function, not to a handle: it is set to the TDS_RB_MAX_BODIES size of this dtype, so that no
+  // later handle with fewer bodies lowers it under what a live handle launches with.
+  {
+    const int lds_max = TDS_RB_MAX_BODIES * RB_NC * 64 * (dtype == TDS_DTYPE_F64 ? 8 : 4);
+    if (dtype == TDS_DTYPE_F64)
+      RB_TRY(hipFuncSetAttribute((const void *)tds_rb_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    else
+      RB_TRY(hipFuncSetAttribute((const void *)tds_rb_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  }
   tds_rb_sim *s = new tds_rb_sim;
   s->model = *model;
   s->num_worlds = num_worlds;
@@ -321,11 +331,6 @@ int tds_rb_create(const tds_rb_model_t *model, int num_worlds, int device, int d
       return rb_fail(TDS_ERR_HIP, "upload of the rigid-body model failed");
     }
   }
-  const int lds = model->num_bodies * RB_NC * 64 * (int)s->elem;
-  if (dtype == TDS_DTYPE_F64)
-    (void)hipFuncSetAttribute((const void *)tds_rb_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  else
-    (void)hipFuncSetAttribute((const void *)tds_rb_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   *out = s;
   return TDS_OK;
 }

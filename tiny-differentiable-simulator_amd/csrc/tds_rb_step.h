@@ -98,11 +98,13 @@ inline void rb_build(const tds_rb_model_t *m, RbDev<T> *d) {
       }
     }
     d->radius[i] = (T)rad;
-    // Plane's constructor normalises the normal (geometry.hpp:163-168)
+    // Plane's constructor normalises the normal (geometry.hpp:163-168) as v * (1 / |v|) (tiny_algebra.hpp:223); a
+    // non-unit normal rounds differently under v / |v|
     double nl = sqrt(b.plane_normal[0] * b.plane_normal[0] + b.plane_normal[1] * b.plane_normal[1] +
                      b.plane_normal[2] * b.plane_normal[2]);
     if (nl == 0.0) nl = 1.0;
-    for (int k = 0; k < 3; ++k) d->pn[i][k] = (T)(b.plane_normal[k] / nl);
+    const double inl = 1.0 / nl;
+    for (int k = 0; k < 3; ++k) d->pn[i][k] = (T)(b.plane_normal[k] * inl);
     d->pc[i] = (T)b.plane_constant;
   }
 }
