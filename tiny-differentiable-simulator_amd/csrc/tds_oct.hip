@@ -138,8 +138,8 @@ struct OctOff {
 struct OctLds {
   static constexpr int LCW = 6;   // [8 lanes][Lc(6)]  (W = Lc D, needed for the Schur sums only, borrows the impulses' slots)
   // a window row: z~ leg (2) | z~ root (6) | 0 | 0 | b | 1 / (G + cfm) | G | hip lane of the contact's leg.  (The two zeros: lane j
-  // of the sweep reads root entry j — lanes 6, 7 of an environment read them.)  Between its two halves (see help_rows_geom /
-  // rows_solve) a row holds the unsolved Jacobian row and the contact's distance instead.
+  // of the sweep reads root entry j — lanes 6, 7 of an environment read them.)  Every slot is written once per window, with
+  // its final value; the first window's root entries are parked in their slots before they are solved (rows_park).
   static constexpr int ZW = 14;
   static constexpr int Z_B = 10, Z_A = 11, Z_G = 12, Z_HL = 13;
   static constexpr int NCP = 17;  // contact points (torso + 2 per leg link), and the stride of the contact list
@@ -329,6 +329,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   T Cb, Cr[6], It[10];  // (main wavefront: bias forces of my dof / the root dofs, the robot's total inertia — across its barriers)
   T u = T(0), urm = T(0);  // u~ = -dt y~ + sum_r z~_r x_r, distributed: my own dof's leg entry | root entry `lane` (lanes 6, 7: zero)
   T u_init = T(0), urm_init = T(0);
+  T sw_mu = T(0), sw_rest = T(0), sw_cap = T(0), sw_hip = T(0);  // the sweep's constants (main_sweep_consts)
   int na = 0, NA = 0;
 
   // the root body's frame and the root's revolute axes from the six sines / cosines (kinematics.hpp:64-97; tds_kernels.hip
@@ -982,6 +983,18 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     urm_init = urm;
     OCT_STAMP(5, u);
   };
+  // the sweep's constants, once per step, behind the forward dynamics (a scheduling boundary in between: nothing of the
+  // forward dynamics is live beside them).  The impulse cap comes from a pinned integer: as a literal it is materialised in
+  // every normal row, and a pinned double is canonicalised in front of every minimum.
+  auto main_sweep_consts = [&]() {
+    OCT_SYNC();
+    sw_mu = CT[TB::SC + TB::FRICTION];
+    sw_rest = CT[TB::SC + TB::RESTITUTION];
+    sw_hip = (T)(lane & ~1);
+    int cap = 100000;
+    asm volatile("" : "+v"(cap));
+    sw_cap = (T)cap;
+  };
   // (two-wavefront build, behind barrier (2)) the largest contact count for the main wavefront, the root block's factors for the helper
   auto main_get_count = [&]() { NA = __builtin_amdgcn_readfirstlane((int)sm[in_dim + 3]); };
   auto help_get_factors = [&]() {
@@ -997,17 +1010,27 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //      environment with fewer contacts has zero rows in its empty slots).  Rows are solved a WINDOW of eight sweep
   //      positions at a time — lane == row, by the helper — and consumed by the main wavefront's sweep; two window buffers:
   //      the helper solves window w + 1 while the main wavefront sweeps window w.
-  // window wi of the sweep: Gauss-Seidel iteration wi / nwin, sweep positions w0 .. w0 + 7, row buffer wi & 1; lane == row.
+  // A window of the sweep: sweep positions w0 .. w0 + 7 of a Gauss-Seidel iteration, in the row buffer at offset bo (the two
+  // buffers take turns); lane == row.  Both wavefronts walk the windows in the same two nested loops (iterations, then w0 in
+  // steps of eight up to 3 NA) and carry w0 and bo along: one barrier per window, no division by the run-time window count.
   // Three stages, each as early as its inputs exist (two-wavefront build: all by the helper, beside the main wavefront's chain):
   //   rows_geom  the contact's Jacobian row along the row's direction and the right-hand side c_r from the velocities BEFORE
   //              the step (the kinematics only);
   //   rows_leg   the contact's leg block of z~ = D^-1/2 L^-1 J^T (the leg factors: published at barrier (1b));
   //   rows_root  the root block, G and 1 / (G + cfm) (the root block's factors: barrier (2)).
-  auto rows_geom = [&](int wi) {
+  // The row's entries of z~ pass from stage to stage in registers (RowRegs), and a slot of the row in LDS is written once, with
+  // its final value.  The first window's rows wait for the root block's factors across the visual poses: parked in their own
+  // slots of the row (rows_park) and read back in FRONT of barrier (2) (rows_fetch) — behind it the helper reads nothing
+  // but the factors.
+  struct RowRegs {
+    T z0, z1, zr[6];
+    int hl;
+    bool real;
+  };
+  auto rows_geom = [&](int w0, int bo, RowRegs &rw) {
       OCT_MARK("rows_geom");
-      const int nr = 3 * NA, nwin = (nr + 7) >> 3;
-      const int w0 = (wi % nwin) * 8;
-      T *const row = E + O.win + (wi & 1) * (8 * OctLds::ZW) + lane * OctLds::ZW;
+      const int nr = 3 * NA;
+      T *const row = E + O.win + bo + lane * OctLds::ZW;
       const T *const cpx = E + O.cp;
       const T *const swl = E + O.swl;
       const int s = w0 + lane;
@@ -1050,26 +1073,25 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // rel_vel = vel_a - vel_b = -J qd:  b_n = -(1 + e) n.rel_vel - erp dist / dt,  b_t = -t.rel_vel  (the dt qdd share of
       // the velocity: see main_fd)
       const T crow = tk == 0 ? (T(1) + CT[TB::SC + TB::RESTITUTION]) * vrow - CT[TB::SC + TB::ERP_OVER_DT] * dist : vrow;
-      row[0] = z0;
-      row[1] = z1;
+      rw.z0 = z0;
+      rw.z1 = z1;
 #pragma unroll
-      for (int rr = 0; rr < 6; ++rr) row[2 + rr] = real ? zr[rr] : T(0);
+      for (int rr = 0; rr < 6; ++rr) rw.zr[rr] = real ? zr[rr] : T(0);
+      rw.hl = hl;  // (a contact of the root body: z0 = z1 = 0, whatever leg rows_leg reads)
+      rw.real = real;
       row[8] = T(0);
       row[9] = T(0);
       row[OctLds::Z_B] = real ? crow : T(0);
-      row[OctLds::Z_A] = real ? T(1) : T(0);
       row[OctLds::Z_HL] = on_leg ? (T)hl : T(-2);
       OCT_MARK("rows_geom_end");
   };
-  auto rows_leg = [&](int wi) {
+  auto rows_leg = [&](int bo, RowRegs &rw) {
       OCT_MARK("rows_leg");
-      T *const row = E + O.win + (wi & 1) * (8 * OctLds::ZW) + lane * OctLds::ZW;
+      T *const row = E + O.win + bo + lane * OctLds::ZW;
       const T *const lcw = E + O.lcw;
-      T z0 = row[0], z1 = row[1], zr[6];
-#pragma unroll
-      for (int rr = 0; rr < 6; ++rr) zr[rr] = row[2 + rr];
-      const T hlv = row[OctLds::Z_HL];
-      const int hl = hlv >= T(0) ? (int)hlv : 0;  // (a contact of the root body: z0 = z1 = 0, whatever leg is read)
+      const T z0 = rw.z0;
+      T z1 = rw.z1;
+      const int hl = rw.hl;
       T lch[6], lca[6];
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
@@ -1081,18 +1103,32 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // forward substitution L z = J^T, leaves first: the contact's leg, its share of the root rows; z~_leg = D^-1/2 z
       z1 -= lf0 * z0;
 #pragma unroll
-      for (int rr = 0; rr < 6; ++rr) row[2 + rr] = zr[rr] - (lch[rr] * z0 + lca[rr] * z1);
-      row[0] = z0 * lf1;
-      row[1] = z1 * lf2;
+      for (int rr = 0; rr < 6; ++rr) rw.zr[rr] = rw.zr[rr] - (lch[rr] * z0 + lca[rr] * z1);
+      rw.z0 = z0 * lf1;
+      rw.z1 = z1 * lf2;
+      row[0] = rw.z0;
+      row[1] = rw.z1;
   };
-  auto rows_root = [&](int wi) {
+  auto rows_park = [&](const RowRegs &rw) {
+      T *const row = E + O.win + lane * OctLds::ZW;
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr) row[2 + rr] = rw.zr[rr];
+  };
+  auto rows_fetch = [&](RowRegs &rw) {
+      const T *const row = E + O.win + lane * OctLds::ZW;
+      rw.z0 = row[0];
+      rw.z1 = row[1];
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr) rw.zr[rr] = row[2 + rr];
+  };
+  auto rows_root = [&](int bo, const RowRegs &rw) {
       OCT_MARK("rows_root");
-      T *const row = E + O.win + (wi & 1) * (8 * OctLds::ZW) + lane * OctLds::ZW;
-      const T z0 = row[0], z1 = row[1];
+      T *const row = E + O.win + bo + lane * OctLds::ZW;
+      const T z0 = rw.z0, z1 = rw.z1;
       T zr[6];
 #pragma unroll
-      for (int rr = 0; rr < 6; ++rr) zr[rr] = row[2 + rr];
-      const bool real = row[OctLds::Z_A] != T(0);
+      for (int rr = 0; rr < 6; ++rr) zr[rr] = rw.zr[rr];
+      const bool real = rw.real;
       static_for<1, 6>([&](auto rc) {
         constexpr int rr = decltype(rc)::value;
         static_for<0, rr>([&](auto cc) {
@@ -1118,22 +1154,26 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //      entry j (lanes 6, 7: the row's zero slots) — so that z~_r . u~ is one multiply, one fma and ONE 8-lane sum; the clamp
   //      runs redundantly on every lane; the normal rows and the friction rows of a window are separate loops (no selects on
   //      the row's kind), the first Gauss-Seidel iteration a separate instance (x starts from 0: no G x_old, no read of the
-  //      previous impulse).  A row's operands are requested while the row before is processed (two register sets, the loop
-  //      unrolled by two: no copies).
-  auto main_sweep = [&](int wi) {
+  //      previous impulse).  The window's eight positions are UNROLLED: the row index is a compile-time constant, every row's
+  //      LDS addresses are immediate offsets off four base registers per window (the row buffer, my leg entry, my root entry,
+  //      the window's impulses), and what is left of the loop is two wave-uniform compares per row — past the window's last
+  //      row? a normal row? (normal rows come first in a window).  A row's operands are requested while the row before is
+  //      processed (two register sets, taken in turn by the row's parity: no copies); a friction row asks for its normal
+  //      row's impulse at its own top, behind the store of the row before (NA = 1: that row IS its normal row).  The model's
+  //      constants of the sweep (sw_mu, sw_rest) are read once per step (main_sweep_consts).
+  auto main_sweep = [&](auto firstc, int w0, int bo) {
+      constexpr bool FIRST = decltype(firstc)::value;
       OCT_MARK("sweep");
-      const int nr = 3 * NA, nwin = (nr + 7) >> 3;
-      const int pit = wi / nwin;
-      const int w0 = (wi - pit * nwin) * 8;
-      const T *const Zs = E + O.win + (wi & 1) * (8 * OctLds::ZW);
-      T *const xs = E + O.xs;
-      const T my_hip = (T)(lane & ~1);
-      const T mu = CT[TB::SC + TB::FRICTION], rest = CT[TB::SC + TB::RESTITUTION];
-      const int wn = nr - w0 < 8 ? nr - w0 : 8;
-      const int k_n = NA - w0 < 0 ? 0 : (NA - w0 < wn ? NA - w0 : wn);  // rows 0 .. k_n - 1 of the window are normal rows
+      const T *const Zs = E + O.win + bo;
+      T *const xw = E + O.xs + w0;  // the window's impulses
+      const T my_hip = sw_hip, mu = sw_mu, rest = sw_rest;
+      // rows 0 .. wn - 1 of the window exist, rows 0 .. k_n - 1 are normal rows, rows k_t2 .. are second tangents (compared with
+      // the row index 0 .. 7 only: no clamping)
+      const int wn = 3 * NA - w0, k_n = NA - w0, k_t2 = 2 * NA - w0;
+      const T *const xs1 = xw - NA, *const xs2 = xw - 2 * NA;  // the impulse of a first / second tangent row's normal row
       struct Ops { T zs, zm, b, a, g, hl, sd, xo; };
-      auto request = [&](int k, Ops &o, auto firstc, auto normalc) {
-        constexpr bool FIRST = decltype(firstc)::value, NORMAL = decltype(normalc)::value;
+      auto request = [&](auto kc, Ops &o) {
+        constexpr int k = decltype(kc)::value;
         const T *const row = Zs + k * OctLds::ZW;
         o.zs = row[pos];        // my dof's leg entry, if the row's contact sits on my leg
         o.zm = row[2 + lane];   // my root entry (lanes 6, 7: zero)
@@ -1142,12 +1182,12 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         o.hl = row[OctLds::Z_HL];
         if constexpr (!FIRST) {
           o.g = row[OctLds::Z_G];
-          o.xo = xs[w0 + k];
+          o.xo = xw[k];
         }
-        if constexpr (!NORMAL) o.sd = xs[w0 + k - ((w0 + k >= 2 * NA) ? 2 : 1) * NA];  // the impulse of the contact's normal row
       };
-      auto process = [&](int k, const Ops &o, auto firstc, auto normalc) {
-        constexpr bool FIRST = decltype(firstc)::value, NORMAL = decltype(normalc)::value;
+      auto process = [&](auto kc, const Ops &o, auto normalc) {
+        constexpr int k = decltype(kc)::value;
+        constexpr bool NORMAL = decltype(normalc)::value;
         const T zl = o.hl == my_hip ? o.zs : T(0);
         T jw;
         // (a normal row's b_r carries (1 + e) J (dt qdd): the e-fold of z~_r . (dt y~) = -z~_r . u~_init on top of what u~ holds)
@@ -1158,7 +1198,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         else xn = (o.b - (jw - o.g * o.xo)) * o.a;
         if constexpr (NORMAL) {
           xn = max_t<T>(xn, T(0));
-          xn = min_t<T>(xn, T(100000));
+          xn = min_t<T>(xn, sw_cap);
         } else {
           const T hi = mu * max_t<T>(o.sd, T(0));  // where_lt(s, 0, 0, s)
           xn = max_t<T>(xn, -hi);
@@ -1169,32 +1209,31 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         else dx = xn - o.xo;
         u += zl * dx;
         urm += o.zm * dx;
-        xs[w0 + k] = xn;  // (every lane the same value to the same slot)
+        xw[k] = xn;  // (every lane the same value to the same slot)
       };
-      auto run = [&](int k0, int k1, auto firstc, auto normalc) {  // rows k0 .. k1 - 1
-        if (k0 >= k1) return;
-        Ops A, B;
-        request(k0, A, firstc, normalc);
-        for (int k = k0; k < k1; k += 2) {
-          request(k + 1 < k1 ? k + 1 : k, B, firstc, normalc);
-          process(k, A, firstc, normalc);
-          if (k + 1 < k1) {
-            request(k + 2 < k1 ? k + 2 : k + 1, A, firstc, normalc);
-            process(k + 1, B, firstc, normalc);
+      Ops ops[2];
+      auto rows = [&](auto self, auto kc) -> void {
+        constexpr int k = decltype(kc)::value;
+        if constexpr (k < 8) {
+          if (k >= wn) return;
+          Ops &cur = ops[k & 1];
+          // (the next row's operands in front of the branch on the row's kind: requested inside both arms, the arms' loads
+          //  into the same registers cost a wait each)
+          if constexpr (k < 7) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
+          if (k < k_n) {
+            process(kc, cur, std::true_type{});
+          } else {
+            cur.sd = (k >= k_t2 ? xs2 : xs1)[k];
+            process(kc, cur, std::false_type{});
           }
+          self(self, std::integral_constant<int, k + 1>{});
         }
       };
-      if (pit == 0) {
-        run(0, k_n, std::true_type{}, std::true_type{});
-        run(k_n, wn, std::true_type{}, std::false_type{});
-      } else {
-        run(0, k_n, std::false_type{}, std::true_type{});
-        run(k_n, wn, std::false_type{}, std::false_type{});
-      }
+      request(std::integral_constant<int, 0>{}, ops[0]);
+      rows(rows, std::integral_constant<int, 0>{});
       OCT_SYNC();
       OCT_MARK("sweep_end");
   };
-  auto windows = [&]() -> int { return NA > 0 ? pgs_iters * ((3 * NA + 7) >> 3) : 0; };
 
   // (the step's done flag on every lane of the environment, for main_pool: under the Ant's rule it never passes through LDS)
   bool done_reg = false, done_in_reg = false;
@@ -1488,14 +1527,21 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       OCT_BAR();  // (2)
       main_get_count();
       main_fd();
-      const int nw = windows();
+      main_sweep_consts();
       // (the first window's root stage stays with the helper although the main wavefront holds the factors in registers: doing
       //  it here measured 1.6 k cycles on the chain against 1.1 k of waiting for the helper's)
-      for (int wi = 0; wi < nw; ++wi) {
-        OCT_BAR();
-        if (wi == 0) OCT_STAMP(12, tid);
-        main_sweep(wi);
-        if (wi == 0) OCT_STAMP(13, u);
+      // (the window loops of the two wavefronts must agree — a barrier each: pgs_iters is the table's, NA the helper's)
+      const int nr = 3 * NA;
+      int bo = 0;
+      for (int pit = 0; pit < pgs_iters; ++pit) {
+        for (int w0 = 0; w0 < nr; w0 += 8) {
+          OCT_BAR();
+          if ((pit | w0) == 0) OCT_STAMP(12, tid);
+          if (pit == 0) main_sweep(std::true_type{}, w0, bo);
+          else main_sweep(std::false_type{}, w0, bo);
+          if ((pit | w0) == 0) OCT_STAMP(13, u);
+          bo = 8 * OctLds::ZW - bo;
+        }
       }
       main_fin();
       main_pool();
@@ -1503,25 +1549,36 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     } else {
       OCT_BAR();  // (1)
       help_np();
-      if (NA > 0) rows_geom(0);
+      RowRegs rw = {};
+      if (NA > 0) rows_geom(0, 0, rw);
       OCT_BAR();  // (1b)
-      if (NA > 0) rows_leg(0);
-      help_poses();
-      OCT_BAR();  // (2)
-      const int nw = windows();
-      if (nw > 0) {
-        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(3);  // (the stretch the main wavefront waits for)
-        help_get_factors();
-        rows_root(0);
-        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+      if (NA > 0) {
+        rows_leg(0, rw);
+        rows_park(rw);
       }
-      for (int wi = 0; wi < nw; ++wi) {
-        if (wi > 0) {
-          rows_geom(wi);
-          rows_leg(wi);
-          rows_root(wi);
-        }
+      help_poses();
+      if (NA > 0) rows_fetch(rw);
+      OCT_BAR();  // (2)
+      // (the same windows as the main wavefront's two loops, the first one — the stretch the main wavefront waits for: nothing
+      //  but the factors' reads, the root stage and the barrier — taken out in front: there is one exactly when NA > 0 and
+      //  pgs_iters > 0, as in the main wavefront's loops)
+      if (NA > 0 && pgs_iters > 0) {
+        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(3);
+        help_get_factors();
+        rows_root(0, rw);
+        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         OCT_BAR();
+        const int nr = 3 * NA;
+        int bo = 8 * OctLds::ZW;
+        for (int pit = 0; pit < pgs_iters; ++pit) {
+          for (int w0 = pit == 0 ? 8 : 0; w0 < nr; w0 += 8) {
+            rows_geom(w0, bo, rw);
+            rows_leg(bo, rw);
+            rows_root(bo, rw);
+            OCT_BAR();
+            bo = 8 * OctLds::ZW - bo;
+          }
+        }
       }
       OCT_BAR();  // (0)
       help_rec();
@@ -1535,13 +1592,20 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_SYNC();
     main_dyn2();
     main_fd();
-    const int nw = windows();
-    for (int wi = 0; wi < nw; ++wi) {
-      rows_geom(wi);
-      rows_leg(wi);
-      rows_root(wi);
-      OCT_SYNC();
-      main_sweep(wi);
+    main_sweep_consts();
+    const int nr = 3 * NA;
+    int bo = 0;
+    for (int pit = 0; pit < pgs_iters; ++pit) {
+      for (int w0 = 0; w0 < nr; w0 += 8) {
+        RowRegs rw;
+        rows_geom(w0, bo, rw);
+        rows_leg(bo, rw);
+        rows_root(bo, rw);
+        OCT_SYNC();
+        if (pit == 0) main_sweep(std::true_type{}, w0, bo);
+        else main_sweep(std::false_type{}, w0, bo);
+        bo = 8 * OctLds::ZW - bo;
+      }
     }
     main_fin();
     main_pool();
