@@ -8,6 +8,13 @@
 // strides (in scalars, odd) of the per-link LDS records of the two sweep groups
 #define TDS_S1 13  // X_world rot(9) trans(3), odd stride; (v | a0) only in the side records of branching links
 #define TDS_S2 17  // f or F(6) | Ic(10), odd stride
+// Gram form of the contact solve (tds_gram_solve): the 16 x 16 (+1) buffer in the place of the two sweep groups
+#define TDS_GRAM_STRIDE 17  // odd row stride of the 16 x 16 (+1) buffer
+#define TDS_GRAM_ZEROS (16 * TDS_GRAM_STRIDE)  // 16 zeros behind the buffer: what masked operand lanes read
+// Whether the generalised force of the PD block waits in an LDS slot per link (TdsLds::tau) for phase F instead of being
+// carried in registers through every sweep: the 18-dof kernels, and the two-wavefront workgroups of the narrow kernels.
+// (What the layout grants and what the straight-line builds use; the step-loop builds carry it in registers.)
+constexpr bool tds_parks_tau(int ndp, bool w2) { return w2 ? ndp <= 16 : (ndp > 16 && ndp < 24); }
 
 // Per-environment LDS layout, offsets in units of the compute scalar T (see tds_make_lds_layout).
 struct TdsLds {
@@ -165,7 +172,7 @@ typedef int (*tds_alt_launch_fn)(const void *d_model, const void *h_model, const
                                  void *y_out, const void *actions, void *x_feedback, void *obs_out, void *ovf, int n_envs,
                                  hipStream_t stream, const TdsStepCtl *ctl, int form, int *lanes_ndp_key);
 
-// na_cap: contacts whose rows stay in LDS (<= 0: all); w2: the layout of the two-wavefront workgroups (the LDS groups
+// (tds_layout.hip) na_cap: contacts whose rows stay in LDS (<= 0: all); w2: the layout of the two-wavefront workgroups (the LDS groups
 // that alias each other in the one-wave layout laid out one after the other, + hand-over slots)
 template <typename T>
 TdsLds tds_make_lds_layout(const DevModel<T> &m, int na_cap, int lanes_per_env, bool w2 = false);
@@ -214,4 +221,4 @@ inline int tds_kernel_max_dynamic_lds(int lanes_per_env, int ndp, int bytes, int
                    : tds_kernel_max_dynamic_lds_impl<T, TR, 0>(lanes_per_env, ndp, bytes);
 }
 
-int tds_padded_dof(int nd, int lanes_per_env = 0);
+int tds_padded_dof(int nd, int lanes_per_env = 0);  // (tds_layout.hip)

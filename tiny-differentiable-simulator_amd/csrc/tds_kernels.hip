@@ -42,18 +42,12 @@
 #include "tds_kernels.h"
 #include "tds_lanes.h"
 #include "tds_step_shared.h"
-// two-wavefront workgroups of the narrow kernels: the generalised force of the PD block waits in LDS for phase F
-// (0: carried in registers)
-#ifndef TDS_PARK_W2
-#define TDS_PARK_W2 1
-#endif
-#ifndef TDS_PARK_LOOP
-#define TDS_PARK_LOOP 0
-#endif
-
-
 
 namespace {
+
+// the main wavefront of a two-wavefront workgroup runs at this priority, and so does the helper during its row solves
+// (see the top of the kernel and the helper's stretch in front of barrier (3))
+constexpr int TDS_MAIN_PRIO = 3;
 
 // ------------------------------------------------------------------------------------------
 // constraint-row helpers.  SLAB = false: every row of the wavefront's environments fits the LDS
@@ -75,9 +69,6 @@ namespace {
 // a flat load + wait per poll.  These go to the LDS address space explicitly: ds_read / ds_write, lgkmcnt only.
 // (the main wavefront's polls; the helper's stay volatile generic loads: as DS reads that build spilled and lost 5 % —
 //  tools/experiments/r05_not_kept.txt)
-#ifndef TDS_LDS_PUBLISH
-#define TDS_LDS_PUBLISH 1
-#endif
 #define TDS_AS3 __attribute__((address_space(3)))
 // (loaded pointers — kernel-argument fields, pointer-table entries — are declared global memory by tds_global(): tds_step_shared.h)
 template <int WHO = 1, typename T>
@@ -87,8 +78,7 @@ __device__ __forceinline__ T tds_lds_poll(const T *p) {  // WHO: 1 the main wave
 }
 template <typename T>
 __device__ __forceinline__ void tds_lds_flag(T *p, T v) {
-  if constexpr (TDS_LDS_PUBLISH != 0) *(volatile TDS_AS3 T *)p = v;
-  else *(volatile T *)p = v;
+  *(volatile TDS_AS3 T *)p = v;
 }
 template <bool SLAB, typename T, int G, int NDP, bool SPLIT = false>
 __device__ __forceinline__ void tds_row_solve(int lane, int NA, int na, int nd, int ZR, int OVR, int NCPp,
@@ -451,15 +441,11 @@ __device__ __forceinline__ T tds_pgs_lds(int lane, int NA, int ZR, int iters, T 
 // all that is required is that the compiler keeps the program order of the LDS accesses.  A real
 // __syncthreads() would also wait for every outstanding GLOBAL store (the early y writes), which
 // single-wave-per-SIMD occupancy cannot hide.
-#ifdef TDS_FULL_BARRIER
-#define TDS_WAVE_SYNC() __syncthreads()
-#else
 #define TDS_WAVE_SYNC()                                        \
   do {                                                         \
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     \
     __builtin_amdgcn_wave_barrier();                           \
   } while (0)
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Gram form of the contact solve on the matrix cores (two-wavefront workgroups, 16 lanes per environment, double).
@@ -477,8 +463,6 @@ __device__ __forceinline__ T tds_pgs_lds(int lane, int NA, int ZR, int iters, T 
 // reference's order: normals, tangents 1, tangents 2), different association of the sums.
 // Needs 3 NA <= 15 (rows on 16 lanes, one column left for y~) and every row in LDS.
 // ------------------------------------------------------------------------------------------
-#define TDS_GRAM_STRIDE 17  // odd row stride of the 16 x 16 (+1) buffer
-#define TDS_GRAM_ZEROS (16 * TDS_GRAM_STRIDE)  // 16 zeros behind the buffer: what masked operand lanes read
 // v_max_f64 / v_min_f64 as they are (fmax / fmin would first canonicalise both operands: two more instructions on a
 // path whose instruction count is its latency)
 __device__ __forceinline__ double tds_vmax(double a, double b) {
@@ -611,142 +595,6 @@ __device__ __forceinline__ double tds_gram_solve(double *sm, const TdsLds &L, in
 // the step kernel
 // ------------------------------------------------------------------------------------------
 
-// ------------------------------------------------------------------------------------------
-// Gram form of the contact solve on the matrix cores (two-wavefront workgroups, 16 lanes per environment, double).
-//
-// Once the row store holds z~_r = D^-1/2 L^-1 J_r^T (phase K) everything the projected Gauss-Seidel needs is inner
-// products of those rows:  A_rs = z~_r . z~_s  (= J_r M^-1 J_s^T)  and the acceleration part of the right-hand sides
-// z~_r . y~.  v_mfma_f64_4x4x4_4b_f64 computes four independent 4x4x4 products per instruction; its operand map
-// (probed: tools/ubench/mfma_f64_4x4x4.hip) is   A: lane = 16 k + 4 blk + i,  B: lane = 16 k + 4 blk + j,
-// D: lane = 16 i + 4 blk + j   — block blk takes the environment in lane group blk, the operands come straight out of
-// the environments' LDS regions, and [Z~ | y~] [Z~ | y~]^T lands in a per-environment 16 x 16 buffer with ~50 matrix
-// instructions instead of ~12 cross-lane reductions per sweep and 12 more for the right-hand sides.
-// The sweep then runs with lane == row and NO reduction at all: every lane keeps its row's  res_s = sum_r A_sr x_r
-// up to date (one FMA per updated row, the update broadcast by DPP), so the dependent chain per row is
-// sub, mul, max, min, broadcast, fma.  Same iteration as tds_pgs_sweep (mb_constraint_solver.hpp:101-142, rows in the
-// reference's order: normals, tangents 1, tangents 2), different association of the sums.
-// Needs 3 NA <= 15 (rows on 16 lanes, one column left for y~) and every row in LDS.
-// ------------------------------------------------------------------------------------------
-#define TDS_GRAM_STRIDE 17  // odd row stride of the 16 x 16 (+1) buffer
-#define TDS_GRAM_ZEROS (16 * TDS_GRAM_STRIDE)  // 16 zeros behind the buffer: what masked operand lanes read
-template <int NDP>
-__device__ __forceinline__ double tds_gram_solve(double *sm, const TdsLds &L, int lane, int NA, int na, int ZR, int NCPp,
-                                                 int iters, double mu, double dt, double erp_dt, double rest,
-                                                 long long *stamp = nullptr, int stamp_at = 0) {
-  using T = double;
-  // (diagnostic: one timestamp inside this function, selected by TDS_GRAM_STAMP_AT)
-  auto mark = [&](int at) {
-    if (stamp != nullptr && at == stamp_at) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(0);
-      if (blockIdx.x == 0 && threadIdx.x == 0) *stamp = (long long)__builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  constexpr int NDs = NDP + 1;
-  constexpr int GS = TDS_GRAM_STRIDE;
-  const int wl = threadIdx.x & 63;
-  const int grp = wl >> 4;
-  const int nr = 3 * NA;          // rows 0..nr-1; column nr carries y~
-  const int NTr = (nr + 3) >> 2;  // row tiles
-  const int NTc = (nr + 4) >> 2;  // column tiles (incl. the y~ column)
-  {
-    // ---- [Z~ | y~] [Z~ | y~]^T on the matrix cores
-    const int kq = wl >> 4, blk = (wl >> 2) & 3, ij = wl & 3;
-    const int eb = blk * L.stride;
-    const int zero_at = eb + L.Xw + TDS_GRAM_ZEROS;
-    int base[4], base3[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int c = 4 * t + ij;  // row of [Z~ | y~] this lane feeds in tile t
-      const int at = c < nr ? eb + L.Z + c * NDs : (c == nr ? eb + L.dinv + 3 * NDP : zero_at);
-      base[t] = at + kq;
-      base3[t] = (12 + kq < NDP) ? base[t] : zero_at;  // (k tile 3 runs past the padded dof count)
-    }
-    T op[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      if (t < NTc) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (4 * k >= NDP) op[t][k] = T(0);
-          else if (4 * k + 3 < NDP) op[t][k] = sm[base[t] + 4 * k];
-          else op[t][k] = sm[base3[t] + (12 + kq < NDP ? 4 * k : 0)];
-        }
-      }
-    const int out = eb + L.Xw + kq * GS + ij;  // D: row 4 I + (lane >> 4), column 4 J + (lane & 3) of block blk
-#pragma unroll
-    for (int I = 0; I < 4; ++I)
-      if (I < NTr) {
-#pragma unroll
-        for (int J = 0; J < 4; ++J)
-          if (J < NTc) {
-            T acc = T(0);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (4 * k < NDP) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(op[I][k], op[J][k], acc, 0, 0, 0);
-            sm[out + 4 * I * GS + 4 * J] = acc;
-          }
-      }
-  }
-  TDS_WAVE_SYNC();
-  mark(1);
-  // ---- lane == row
-  T *const E = sm + grp * L.stride;
-  const T *const Gm = E + L.Xw;
-  const T *const rws = E + L.rows;
-  const T *const cpx = E + L.cp;
-  const int s = lane;
-  const int t = (s >= NA ? 1 : 0) + (s >= 2 * NA ? 1 : 0);
-  const int a = s - t * NA;
-  const bool row = s < nr && a < na;
-  const int sc = s < nr ? s : 0;
-  T Acol[15];
-#pragma unroll
-  for (int r = 0; r < 15; ++r) Acol[r] = r < nr ? Gm[s * GS + r] : T(0);
-  // right-hand side: J_r . qd+ = J_r . qd + dt z~_r . y~ (see tds_row_rhs_finish)
-  const T vrow = rws[sc] + dt * Gm[s * GS + nr];
-  const T b = !row ? T(0) : (t == 0 ? (T(1) + rest) * vrow - erp_dt * cpx[3 * NCPp + a] : vrow);
-  const T ar = row ? rws[ZR + sc] : T(0);
-  const T gr = row ? rws[2 * ZR + sc] : T(0);
-  T x = T(0), res = T(0);
-  T lo = T(0), hi = t == 0 ? T(100000) : T(0);
-  mark(2);
-  for (int it = 0; it < iters; ++it) {
-    static_for<0, 15>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      if (r < nr) {  // wave-uniform
-        const T delta = res - gr * x;  // sum over the OTHER rows (G_rr x_r taken out again)
-        T xn = (b - delta) * ar;
-        xn = max_t<T>(xn, lo);
-        xn = min_t<T>(xn, hi);
-        const T dxr = dpp_bcast<r>(xn - x);
-        res += Acol[r] * dxr;
-        x = s == r ? xn : x;
-        if (r < NA) {  // a normal row: its impulse bounds the two friction rows of the same contact
-          const T xr_n = dpp_bcast<r>(xn);
-          if (t != 0 && a == r) {
-            const T h = mu * (xr_n > T(0) ? xr_n : T(0));  // where_lt(s, 0, 0, s)
-            lo = -h;
-            hi = h;
-          }
-        }
-      }
-    });
-  }
-  mark(3);
-  // u~ = sum_r z~_r x_r, lane == dof
-  const T *const Zs = E + L.Z;
-  const int dcl = lane < NDP ? lane : NDP - 1;
-  T u = T(0);
-  static_for<0, 15>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r < nr) u += Zs[r * NDs + dcl] * dpp_bcast<r>(x);
-  });
-  return lane < NDP ? u : T(0);
-}
-
-
 // The by-value kernel arguments L (LDS layout) and ctl (what the launch does) as the STEP-LOOP builds read them.  Taken
 // from the function parameters, every field the loop body uses — and every boolean derived from one — is loop-invariant:
 // the compiler loads them all in front of the loop and keeps them live across it, ~60 kernel-argument dwords and ~40
@@ -776,9 +624,6 @@ __device__ __forceinline__ P tds_ka_val(P param, const TDS_AS4 char *at) {  // a
   if constexpr (ON) return *(const TDS_AS4 P *)at;
   else return param;
 }
-#ifndef TDS_KA_RELOAD
-#define TDS_KA_RELOAD 1
-#endif
 
 // per-group state machine of the in-kernel step loop
 #define TDS_MODE_IDLE 0
@@ -907,11 +752,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   // The main wavefront is the workgroup's critical path, the helper has slack: where a main and a helper wavefront (of
   // different workgroups: one of each per SIMD when 1024 two-wave workgroups are resident) share a SIMD, the arbiter
   // issues the main one first.  Measured (same process, experiment slots, profiles/r04_ab_slots_ant4096.txt): Ant x 4096
-  // ring launches 14.01 -> 13.72 us per step (priority 3; -DTDS_MAIN_PRIO=0 leaves the default arbitration).
-#ifndef TDS_MAIN_PRIO
-#define TDS_MAIN_PRIO 3
-#endif
-  if constexpr (W2 && TDS_MAIN_PRIO > 0) {
+  // ring launches 14.01 -> 13.72 us per step (priority TDS_MAIN_PRIO against the default arbitration).
+  if constexpr (W2) {
     if (wv == 0) __builtin_amdgcn_s_setprio(TDS_MAIN_PRIO);
   }
 
@@ -1041,36 +883,22 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   // (the model pointer is laundered as a GLOBAL-address-space pointer: laundered as a generic one — round 4 — the address
   //  space was lost with the provenance and every model constant of a step-loop build came in through a FLAT load, which
   //  counts on vmcnt AND lgkmcnt and returns out of order with the DS instructions: every LDS wait behind one became
-  //  lgkmcnt(0).  -DTDS_MDL_GLOBAL=0: the generic pointer, 1: global, 2 (default): constant address space, see below;
-  //  same-process A/B, Ant x 4096 / x 8192, us per step: 12.10 / 21.02 -> 12.04 / 20.56 -> 11.58 / 19.91)
-#ifndef TDS_MDL_GLOBAL
-#define TDS_MDL_GLOBAL 2
-#endif
-  // (TDS_MDL_GLOBAL = 2: the CONSTANT address space — the model is read-only for the kernel — so that loads at uniform
+  //  lgkmcnt(0).  Generic -> global -> constant address space, same-process A/B, Ant x 4096 / x 8192, us per step:
+  //  12.10 / 21.02 -> 12.04 / 20.56 -> 11.58 / 19.91)
+  // (the CONSTANT address space — the model is read-only for the kernel — so that loads at uniform
   //  addresses through the laundered pointer are scalar loads again (the header fields every iteration starts with: as
   //  vector loads a round trip to L2 at the top of every step), as they are in the straight-line builds, whose pointer is the
   //  `const __restrict__` kernel argument itself)
-#if TDS_MDL_GLOBAL == 2
-#define TDS_MDL_AS 4
-#else
-#define TDS_MDL_AS 1
-#endif
-  const __attribute__((address_space(TDS_MDL_AS))) DevModel<T> *mdl_g = (const __attribute__((address_space(TDS_MDL_AS))) DevModel<T> *)mdl_arg;
-  const DevModel<T> *mdl_f = mdl_arg;
+  const TDS_AS4 DevModel<T> *mdl_g = (const TDS_AS4 DevModel<T> *)mdl_arg;
   // (the 32-dof build is at one wavefront per SIMD whatever is done and fares better with the lane constants
   //  hoisted into AGPR copies — 256 + 130 registers, no scratch, against 256 + 256 + 876 B of scratch: only the
   //  model pointer is laundered there)
-  if constexpr (TDS_MDL_GLOBAL != 0) {
-    if constexpr (LOOP && NDP < 32) asm volatile("" : "+v"(lane_l), "+v"(grp_l), "+s"(mdl_g));
-    if constexpr (LOOP && NDP >= 32) asm volatile("" : "+s"(mdl_g));
-  } else {
-    if constexpr (LOOP && NDP < 32) asm volatile("" : "+v"(lane_l), "+v"(grp_l), "+s"(mdl_f));
-    if constexpr (LOOP && NDP >= 32) asm volatile("" : "+s"(mdl_f));
-  }
-  const DevModel<T> *const mdl = TDS_MDL_GLOBAL != 0 ? (const DevModel<T> *)mdl_g : mdl_f;
+  if constexpr (LOOP && NDP < 32) asm volatile("" : "+v"(lane_l), "+v"(grp_l), "+s"(mdl_g));
+  if constexpr (LOOP && NDP >= 32) asm volatile("" : "+s"(mdl_g));
+  const DevModel<T> *const mdl = (const DevModel<T> *)mdl_g;
   const int lane = lane_l, grp = grp_l;
   // ---- the kernel arguments of this iteration (step-loop builds: read through a laundered segment pointer, see TdsKaRef)
-  constexpr bool KA = LOOP && TDS_KA_RELOAD != 0;
+  constexpr bool KA = LOOP;
   const TDS_AS4 char *ka_seg = (const TDS_AS4 char *)__builtin_amdgcn_kernarg_segment_ptr();
   if constexpr (KA) asm volatile("" : "+s"(ka_seg));
   using TdsKA = TdsKernArgs<T, TR>;
@@ -1078,18 +906,14 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   typename TdsKaRef<KA, TdsStepCtl>::type ctl = TdsKaRef<KA, TdsStepCtl>::get(ctl_arg, ka_seg + __builtin_offsetof(TdsKA, ctl));
   // (likewise the pointer parameters and the environment count: taken from the parameters, every `!= nullptr` of the loop body
   //  is a launch-invariant condition the compiler evaluates in front of the loop and keeps — two SGPRs each — in lanes of a
-  //  spill register: 48 SGPR spills, 97 v_readlane per iteration in the headline build.  -DTDS_KA_PTRS=0: the parameters)
-#ifndef TDS_KA_PTRS
-#define TDS_KA_PTRS 1
-#endif
-  constexpr bool KP = KA && TDS_KA_PTRS != 0;
-  const TR *const ka_x_in = tds_ka_val<KP, const TR *>(x_in, ka_seg + __builtin_offsetof(TdsKA, x_in));
-  TR *const ka_y_out = tds_ka_val<KP, TR *>(y_out, ka_seg + __builtin_offsetof(TdsKA, y_out));
-  const TR *const ka_actions = tds_ka_val<KP, const TR *>(actions, ka_seg + __builtin_offsetof(TdsKA, actions));
-  TR *const ka_x_feedback = tds_ka_val<KP, TR *>(x_feedback, ka_seg + __builtin_offsetof(TdsKA, x_feedback));
-  TR *const ka_obs_out = tds_ka_val<KP, TR *>(obs_out, ka_seg + __builtin_offsetof(TdsKA, obs_out));
-  T *const ka_ovf = tds_ka_val<KP, T *>(ovf, ka_seg + __builtin_offsetof(TdsKA, ovf));
-  const int ka_n_envs = tds_ka_val<KP, int>(n_envs, ka_seg + __builtin_offsetof(TdsKA, n_envs));
+  //  spill register: 48 SGPR spills, 97 v_readlane per iteration in the headline build)
+  const TR *const ka_x_in = tds_ka_val<KA, const TR *>(x_in, ka_seg + __builtin_offsetof(TdsKA, x_in));
+  TR *const ka_y_out = tds_ka_val<KA, TR *>(y_out, ka_seg + __builtin_offsetof(TdsKA, y_out));
+  const TR *const ka_actions = tds_ka_val<KA, const TR *>(actions, ka_seg + __builtin_offsetof(TdsKA, actions));
+  TR *const ka_x_feedback = tds_ka_val<KA, TR *>(x_feedback, ka_seg + __builtin_offsetof(TdsKA, x_feedback));
+  TR *const ka_obs_out = tds_ka_val<KA, TR *>(obs_out, ka_seg + __builtin_offsetof(TdsKA, obs_out));
+  T *const ka_ovf = tds_ka_val<KA, T *>(ovf, ka_seg + __builtin_offsetof(TdsKA, ovf));
+  const int ka_n_envs = tds_ka_val<KA, int>(n_envs, ka_seg + __builtin_offsetof(TdsKA, n_envs));
   const TR *const x_in = tds_global(ka_x_in);
   TR *__restrict__ const y_out = tds_global(ka_y_out);
   const TR *__restrict__ const actions = tds_global(ka_actions);
@@ -1123,14 +947,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   const T *const CW = sm + EPW * L.stride;
   // (read through an LDS-address-space pointer: as generic pointers the compiler merged "table or model" into ONE flat load
   //  through a selected pointer — table reads that went the flat path, out of order with the DS instructions)
-#ifndef TDS_CW_LDS
-#define TDS_CW_LDS 1
-#endif
-#if TDS_CW_LDS
   const TDS_AS3 T *const CWl = (const TDS_AS3 T *)CW;
-#else
-  const T *const CWl = CW;
-#endif
   int parent, level, jt, di;
   unsigned cw_hi = 0u;
   if (cwt) {
@@ -1218,20 +1035,10 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   // runs A - C, in what used to be the helper's idle wait for barrier (1) — not between its narrowphase and its Jacobian
   // rows, where every store instruction lengthened its path to barrier (2): with the records also going to seven peers
   // (the peer-store exchange of an 8-GPU run) that was 12 % of the step (profiles/r05_peer_store_cost_one_gpu.txt).
-  // Round 4's form (-DTDS_FLUSH_EARLY=0): no barrier, the main wavefront polls the helper's "poses are out" flag.
+  // (Round 4 had no barrier here: the main wavefront polled the helper's "poses are out" flag.)
   // (lgkmcnt only: neither wavefront waits for its outstanding global stores here)
-#ifndef TDS_FLUSH_EARLY
-#define TDS_FLUSH_EARLY 1
-#endif
   if constexpr (W2 && LOOP) {
-    if constexpr (TDS_FLUSH_EARLY != 0) {
-      if (tds_iter > 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {
-      if (main_wave && tds_iter > 0) {  // the helper has read X_world of the previous step (its late visual poses, see there)
-        const T *const pf = sm + grp * L.stride + L.xrec + in_dim + 4;
-        while (__any(tds_lds_poll(pf) != T(2))) __builtin_amdgcn_s_sleep(1);
-      }
-    }
+    if (tds_iter > 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
   const bool chain_child = (cflags & 1) != 0;      // my parent is lane - 1
   const bool has_chain_child = (cflags & 2) != 0;  // lane + 1 is my child and hands over by DPP
@@ -1978,14 +1785,12 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
       if constexpr (LOOP) {  // (TDS_RING_SIGNAL_LATE: the records stored in the iteration before this one)
         if (ctl.ring_flags & TDS_RING_SIGNAL_LATE) signal_progress(2);
       }
-      if constexpr (LOOP && TDS_FLUSH_EARLY != 0) flush_prev_records();  // (behind barrier (0): see there)
+      if constexpr (LOOP) flush_prev_records();  // (behind barrier (0): see there)
       // (the helper's side of barrier (1) does not wait for its global stores — the previous step's records, and in the
       //  peer-store exchange the rows to every peer, issued just above: __syncthreads() is `s_waitcnt vmcnt(0) lgkmcnt(0)`
-      //  + s_barrier, i.e. it held the barrier until the slowest of those stores was acknowledged.  -DTDS_LIGHT_BARRIER1=0)
-#ifndef TDS_LIGHT_BARRIER1
-#define TDS_LIGHT_BARRIER1 1
-#endif
-      if constexpr (LOOP && TDS_LIGHT_BARRIER1 != 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      //  + s_barrier, i.e. it held the barrier until the slowest of those stores was acknowledged:
+      //  tools/experiments/r05_not_kept.txt)
+      if constexpr (LOOP) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       else __syncthreads();  // (1) the main wavefront has written the x record, X_world and the motion axes
       TDS_STAMP(2);
       T *const cpx = E + L.cp;
@@ -2008,7 +1813,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
       if constexpr (!LOOP) {
         if (L.gram_ok) phase_M1();
       }
-      if constexpr (!(LOOP && TDS_FLUSH_EARLY != 0)) flush_prev_records();
+      if constexpr (!LOOP) flush_prev_records();
       if (pack_y && !(DEFER && ring_y)) {  // tail of the y record: up_dot_world_z, zero padding
         TR *const yo = y_step;
         int tail = nq + nd;
@@ -2038,14 +1843,14 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
       //  at barrier (3) once it had priority everywhere, profiles/r04f_ant4096_f64_phases.txt.  From the Jacobian rows or
       //  the narrowphase on instead: 12.99 / 13.29 against 12.71, no priorities at all 13.58,
       //  profiles/r04_ab_slots9_helper_from.txt)
-      if constexpr (TDS_MAIN_PRIO > 0) __builtin_amdgcn_s_setprio(TDS_MAIN_PRIO);
+      __builtin_amdgcn_s_setprio(TDS_MAIN_PRIO);
       if (contacts_h && split_ok)
         tds_row_solve<false, T, G, NDP, true>(lane, NA_h, na_h, nd, ZR, OVR, NCPp, Zs, rws, xs, xr + nq, cpx, E + L.Lp,
                                              E + L.dinv, nullptr, nullptr, pf_cfm, pf_erp_dt, pf_rest,
                                              L.gram_ok ? nullptr : xr + in_dim + 4, dt,
                                              PIPE ? xr + in_dim + 5 : nullptr, PIPE ? E + L.Lh : nullptr);
       TDS_STAMP(7);
-      if constexpr (TDS_MAIN_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       if constexpr (LOOP) {  // (the records this wavefront stored behind the visual poses)
         if (!(ctl.ring_flags & TDS_RING_SIGNAL_LATE) || last_run) signal_progress();
       }
@@ -2082,7 +1887,6 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   //  tau is first needed, was tried for the 18-dof kernels, whose 12 B of scratch are tau carried through the sweeps: the
   //  allocator then spilled 20 B elsewhere — measured with tools/kernel_resources.sh, not kept)
   T tau = T(0);
-  constexpr bool LATE_PD = false;
   auto compute_tau = [&]() {
     if (step_mode == TDS_STEP_LOCOMOTION) {
       const int ai = act_i;
@@ -2155,11 +1959,11 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     }
 
   };
-  if constexpr (!LATE_PD) compute_tau();
+  compute_tau();
   // 18-dof straight-line kernels (Laikago): tau would be the one value carried in registers from here through every
-  // sweep to phase F — it waits in LDS instead (a slot of its own per link)
-  constexpr bool PARK_TAU = (!LOOP && ((!W2 && NDP > 16 && NDP < 24) || (W2 && NDP <= 16 && TDS_PARK_W2))) ||
-                            (LOOP && W2 && NDP <= 16 && TDS_PARK_LOOP);
+  // sweep to phase F — it waits in LDS instead (a slot of its own per link); likewise in the two-wavefront workgroups of
+  // the narrow kernels.  The step-loop builds carry it in registers.
+  constexpr bool PARK_TAU = !LOOP && tds_parks_tau(NDP, W2);
   if constexpr (PARK_TAU) {
     if (isl) E[L.tau + li] = tau;
   }
@@ -3111,21 +2915,13 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
           // diagonal are written too and never read)
           // (volatile stores: kept in program order — data, then flag — without a scheduling barrier in the middle of
           //  the factorisation)
-          if constexpr (TDS_LDS_PUBLISH != 0) {
-            // (volatile stores into the LDS address space: kept in program order — data, then flag — without a scheduling
-            //  barrier in the middle of the factorisation, as ds_write instructions)
-            volatile TDS_AS3 T *const Lh = (volatile TDS_AS3 T *)(E + L.Lh + (lane < 16 ? lane : 16) * (NDP / 2));  // (row 16: lanes beyond the rows)
+          // (volatile stores into the LDS address space: kept in program order — data, then flag — without a scheduling
+          //  barrier in the middle of the factorisation, as ds_write instructions)
+          volatile TDS_AS3 T *const Lh = (volatile TDS_AS3 T *)(E + L.Lh + (lane < 16 ? lane : 16) * (NDP / 2));  // (row 16: lanes beyond the rows)
 #pragma unroll
-            for (int j = 0; j <= k; ++j) Lh[j] = Mr[j];
-            // (flag by lane 0, the other lanes hit a scratch slot of their own: an address select, no branch)
-            *(volatile TDS_AS3 T *)(lane == 0 ? xr + in_dim + 5 : dvec + 2 * NDP + (lane < NDP ? lane : NDP - 1)) = T(1);
-          } else {
-            volatile T *const Lh = E + L.Lh + (lane < 16 ? lane : 16) * (NDP / 2);  // (row 16: lanes beyond the rows)
-#pragma unroll
-            for (int j = 0; j <= k; ++j) Lh[j] = Mr[j];
-            // (flag by lane 0, the other lanes hit a scratch slot of their own: an address select, no branch)
-            *(volatile T *)(lane == 0 ? xr + in_dim + 5 : dvec + 2 * NDP + (lane < NDP ? lane : NDP - 1)) = T(1);
-          }
+          for (int j = 0; j <= k; ++j) Lh[j] = Mr[j];
+          // (flag by lane 0, the other lanes hit a scratch slot of their own: an address select, no branch)
+          *(volatile TDS_AS3 T *)(lane == 0 ? xr + in_dim + 5 : dvec + 2 * NDP + (lane < NDP ? lane : NDP - 1)) = T(1);
         }
       } else {
         // wider systems: every lane publishes its column-k entry once, all lanes read the column
@@ -3187,7 +2983,6 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     //         lanes to the dof lanes through the (now free) column scratch of dvec.
     T *const rhsx = dvec + 2 * NDP;
     if (lane < NDP) rhsx[lane] = T(0);
-    if constexpr (LATE_PD) compute_tau();
     if constexpr (LOOP) {
       // (action replay: the NEXT step's action block, requested at the top of this step, goes into the action slots of
       //  the record — nobody reads them any more in this step: the PD block has long turned them into tau)
@@ -3845,99 +3640,71 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
-// host side: LDS layout + launch
+// host side: the builds of the kernel, launch, LDS ceiling  (the LDS layout itself: tds_layout.hip)
 // ------------------------------------------------------------------------------------------
-// padded dof count = template parameter NDP of the kernel.  Besides the coarse widths (8/16/24/32) the
-// widths of the two benchmark robots are instantiated exactly for their natural lane count
-// (Ant: 14 dof on 16 lanes, Laikago: 18 dof on 32 lanes): LDL^T and the row solves scale with NDP^2.
-#if !defined(TDS_ONLY_F32) && !defined(TDS_ONLY_MIX) && (!defined(TDS_ONLY_KIND) || TDS_ONLY_KIND == 0) && !defined(TDS_ALT)
-int tds_padded_dof(int nd, int lanes) {
-  if (lanes == 16 && nd > 8 && nd <= 14) return 14;
-  if (lanes == 32 && nd > 16 && nd <= 18) return 18;
-  return nd <= 8 ? 8 : (nd <= 16 ? 16 : (nd <= 24 ? 24 : 32));
-}
-#endif
-
 // register-pressure experiments compile ONE (lanes, padded dof) instantiation: -DTDS_DEBUG_ONLY=3218
 #ifndef TDS_DEBUG_ONLY
 #define TDS_DEBUG_ONLY 0
 #endif
 constexpr bool tds_instantiate(int key) { return TDS_DEBUG_ONLY == 0 || TDS_DEBUG_ONLY == key; }
 
-template <typename T>
-TdsLds tds_make_lds_layout(const DevModel<T> &m, int na_cap, int lanes_per_env, bool w2) {
-  TdsLds L;
-  memset(&L, 0, sizeof(L));
-  const int nl = m.num_links;
-  const int ndp = tds_padded_dof(m.dof_qd, lanes_per_env);
-  L.NLp = nl;
-  L.NDP = ndp;
-  L.NDs = ndp + 1;  // odd row stride: lane == row accesses hit distinct LDS banks
-  const int ncp = m.has_plane ? m.num_cp : 0;
-  L.NCPp = ncp > 0 ? ncp : 1;
-  // two-body worlds: the contacts between the bodies are a second pass through the same row store
-  const int npc = m.num_bodies >= 2 ? m.num_pc : 0;
-  L.NPCp = npc > 0 ? npc : 1;
-  const int nct = ncp > npc ? ncp : npc;  // contacts of the larger pass
-  if (na_cap <= 0 || na_cap > nct) na_cap = nct;
-  L.zrows = 3 * na_cap;            // constraint rows kept in LDS
-  L.ovrows = 3 * nct - L.zrows;    // surplus rows per environment (global scratch slab)
-  int o = 0;
-  // persistent for the whole step
-  L.xrec = o; o += m.input_dim + 4 + (w2 ? 4 : 0);  // + x_{t-1}, the done flag, the reward and the "records are out" flag of
-                                                    //   the step loop (two-wavefront layout: + 2 .. + 5 are the contact counts
-                                                    //   and flags handed between the wavefronts)
-  // two pairs with disjoint lifetimes share their storage:
-  //   swd  (world motion axes per dof: phases C..J)  |  rows (b, 1/(G+cfm), G per constraint row: K..L)
-  //   cp   (contact points: phases I..K)             |  xrow (impulses x of all rows: L)
-  {
-    const int a = 6 * L.NDs, b = 3 * L.zrows;
-    if (npc > 0) {  // (the second contact pass builds its rows from the motion axes after the first one's row scalars)
-      L.swd = o; o += a;
-      L.rows = o; o += b;
-    } else {
-      L.swd = o; L.rows = o; o += a > b ? a : b;
+// (every build of a (T, TR) has the kernel's parameter list)
+template <typename T, typename TR>
+using TdsStepKernelFn = void (*)(const DevModel<T> *, TdsLds, const TR *, TR *, const TR *, TR *, TR *, T *, long long *,
+                                 TdsStepCtl, int);
+
+// THE BUILD TABLE: which tds_step_kernel<T, TR, G, NDP, PROF, LP, KIND, W2> exist for a (T, TR, KIND, G, NDP), written
+// once.  f(kernel, stamped, loop, two_waves) is called for one build after the other until it returns true (a
+// two-wavefront build runs 128 threads per workgroup, every other one 64).  Whatever is not listed here is never
+// instantiated; the kernel's static_assert has the last word on what may be.
+//   * straight-line and step-loop build, one wavefront per workgroup: every key.  Step loop: below 24 padded dof the
+//     two-wavefronts-per-SIMD compilation (LP = 2), from there on the one-wavefront one (LP = 1) — the straight-line build
+//     is itself at one wavefront per SIMD there, the other compilation would spill hundreds of registers.
+//     (Round 4: compiled without MachineLICM the LP = 2 compilation of the kernels up to 14 padded dof holds no scratch —
+//      245 VGPR — and is taken at ANY grid size; the LP = 1 compilation of <double, double, 16, 8> does not terminate
+//      when built without the pass — profiles/r04_diag_loop_hang.txt.  Round 6: below 24 padded dof LP = 1 is no longer
+//      instantiated at all — the robots whose batch sizes made it worth its build time, 14 and 18 dof, run in kernels of
+//      their own: tds_oct.hip, tds_quad.hip.  Option loop_occ = 1 is refused there by tds_api.hip: launch(),
+//      TDS_ERR_UNSUPPORTED, and tests/test_options.py runs the 8-dof loop launches under a watchdog.)
+//   * two wavefronts per workgroup, straight-line and step loop: plain kernels up to 14 padded dof (round 6: at 16 / 18
+//     dof they carried 130 - 180 B of scratch per lane, profiles/r06_kernel_resources_f64_k0.txt).
+//   * phase stamps (a diagnostic: profiles/*_phases.txt): plain kernels with double records, straight-line form, one- and
+//     two-wavefront; -DTDS_PROF_LOOP (a profiling build outside the library) adds the stamped two-wavefront step loop.
+template <typename T, typename TR, int KIND, int G, int NDP, typename F>
+bool tds_builds_of(F &f) {
+  constexpr int LP_LOOP = NDP < 24 ? 2 : 1;
+  constexpr bool TWO_WAVES = KIND == 0 && NDP <= 14;
+  constexpr bool STAMPS = KIND == 0 && sizeof(T) == 8 && sizeof(TR) == 8;
+  if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND>, false, false, false)) return true;
+  if (f(tds_step_kernel<T, TR, G, NDP, false, LP_LOOP, KIND>, false, true, false)) return true;
+  if constexpr (TWO_WAVES) {
+    if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND, true>, false, false, true)) return true;
+    if (f(tds_step_kernel<T, TR, G, NDP, false, 1, KIND, true>, false, true, true)) return true;
+  }
+  if constexpr (STAMPS) {
+    if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND>, true, false, false)) return true;
+    if constexpr (TWO_WAVES) {
+      if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND, true>, true, false, true)) return true;
+#ifdef TDS_PROF_LOOP
+      if (f(tds_step_kernel<T, TR, G, NDP, true, 1, KIND, true>, true, true, true)) return true;
+#endif
     }
   }
-  {
-    const int a = ncp ? 5 * L.NCPp : 0, b = 3 * nct;
-    L.cp = o; L.xrow = o; o += a > b ? a : b;
+  return false;
+}
+// ... of the key (lanes per environment, padded dof): -1 no such key in this unit, 1 f took a build, 0 it took none
+template <typename T, typename TR, int KIND, typename F>
+int tds_visit_builds(int lanes_per_env, int ndp, F f) {
+  switch (lanes_per_env * 100 + ndp) {
+#define TDS_CASE(GG, NN) \
+  case GG * 100 + NN:    \
+    if constexpr (tds_instantiate(GG * 100 + NN)) return tds_builds_of<T, TR, KIND, GG, NN>(f) ? 1 : 0; else return -1;
+    TDS_CASE(16, 8) TDS_CASE(16, 14) TDS_CASE(32, 18) TDS_CASE(16, 16) TDS_CASE(32, 8) TDS_CASE(32, 16) TDS_CASE(32, 24)
+    TDS_CASE(32, 32) TDS_CASE(64, 8) TDS_CASE(64, 16)
+#undef TDS_CASE
+    default:
+      return -1;
   }
-  L.pc = o;
-  if (npc > 0) o += 17 * L.NPCp;  // contact list of the pairs: lives from the narrowphase to the second pass
-  L.Lp = o;   o += (ndp * (ndp - 1)) / 2;
-  L.Lh = o;   // two-wavefront pipeline (narrow kernels): row-major copy of the first ndp/2 columns of L, 16 + 1 rows
-  if (w2 && ndp <= 16) o += 17 * (ndp / 2);  // (+ one row for the lanes of wider groups that own no row)
-  L.dinv = o; o += (w2 ? 4 : 3) * ndp;  // 1/D | sqrt(1/D) | column scratch of the wide LDL^T / rhs exchange (| y~)
-  L.tau = o;
-  if ((ndp > 16 && ndp < 24) || (w2 && ndp <= 16 && TDS_PARK_W2)) o += nl;  // (the generalised forces wait here from the PD block to phase F)
-  // three phase groups share one region:
-  //   1. kinematics sweep:   per-link records [X_world(12) | v(6)]              stride TDS_S1
-  //   2. composite sweep:    per-link records [f or F(6) | Ic(10)] stride TDS_S2
-  //   3. constraint rows:    Z[zrows][NDs]
-  const int u = o;
-  int g1 = u;
-  L.Xw = g1; g1 += TDS_S1 * L.NLp;
-  L.v = g1; g1 += TDS_S1 * m.num_lc_slots;
-  // (two-wavefront workgroups: the helper wavefront reads X_world and writes the rows while the main one sweeps the
-  //  inertias — the three groups are laid out one after the other)
-  int g2 = w2 ? g1 : u;
-  L.IA = g2; L.pA = g2; L.F = g2; L.Ic = g2 + 6; L.a = g2; g2 += TDS_S2 * L.NLp;
-  int g3 = w2 ? g2 : u;
-  L.Z = g3; g3 += L.zrows * L.NDs;
-  // Gram form of the contact solve (tds_gram_solve): its 16 x 17 buffer + 16 zeros reuse the two sweep groups
-  // Opt-in (TDS_HIP_GRAM=1): measured 0.4k of 32k cycles better than the z~ sweep at Ant x 4096 (profiles/r02d_gram_mfma.txt),
-  // and an environment's low-order bits then depend on whether its wavefront-mates push NA past 5 (sweep) or not (Gram).
-  L.gram_ok = (tds_opt_now_flag(TDS_OPT_GRAM) && w2 && lanes_per_env == 16 && ndp <= 16 && m.num_bodies < 2 &&
-               L.Z - L.Xw >= TDS_GRAM_ZEROS + 16) ? 1 : 0;
-  o = g1 > g2 ? g1 : g2;
-  o = o > g3 ? o : g3;
-  o = (o + 1) & ~1;  // keep 16-byte alignment of every env region for T = double
-  L.stride = o;
-  L.in_dim = m.input_dim;
-  L.adim = m.action_dim;
-  L.nqnd = m.dof_q + m.dof_qd;
-  return L;
 }
 
 template <typename T, typename TR, int KIND>
@@ -3950,189 +3717,68 @@ int tds_launch_step_impl(const DevModel<T> *d_model, const DevModel<T> &h_model,
   // (+ the workgroup's constant table of the step-loop launches, TdsLds::cw)
   const size_t shmem = (size_t)L.stride * epw * sizeof(T) + (size_t)L.cw * lanes_per_env * sizeof(T);
   (void)h_model;
-#ifdef TDS_PROF_LOOP
-#define TDS_PROF_LOOP_LAUNCH(GG, NN)                                                                         \
-    if constexpr (KIND == 0 && NN <= 14) {                                                                    \
-      if (two_waves && !simple && prof) {                                                                    \
-        hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, (NN < 24 ? NN : 8), true, 1, 0, true>), dim3(blocks), dim3(128), shmem, \
-                           stream, d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs); \
-        break;                                                                                               \
-      }                                                                                                      \
-    }
-#else
-#define TDS_PROF_LOOP_LAUNCH(GG, NN)
-#endif
-#define TDS_LAUNCH(GG, NN)                                                                                   \
-  do {                                                                                                       \
-    if constexpr (KIND == 0 && NN <= 14) {                                                                    \
-      if (two_waves && simple && !prof) {                                                                    \
-        hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, (NN < 24 ? NN : 8), false, 0, 0, true>), dim3(blocks), dim3(128), shmem, \
-                           stream, d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs); \
-        break;                                                                                               \
-      }                                                                                                      \
-      if constexpr (PROF_BUILDS) {                                                                           \
-        if (two_waves && simple && prof) {                                                                   \
-          hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, (NN < 24 ? NN : 8), true, 0, 0, true>), dim3(blocks), dim3(128), shmem, \
-                             stream, d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs); \
-          break;                                                                                             \
-        }                                                                                                    \
-      }                                                                                                      \
-    }                                                                                                        \
-    TDS_PROF_LOOP_LAUNCH(GG, NN)                                                                             \
-    if constexpr (KIND == 0 && NN <= 14) {                                                                    \
-      if (two_waves && !simple && !prof) {                                                                   \
-        hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, (NN < 24 ? NN : 8), false, 1, 0, true>), dim3(blocks), dim3(128), shmem, \
-                           stream, d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs); \
-        break;                                                                                               \
-      }                                                                                                      \
-    }                                                                                                        \
-    if (prof) {                                                                                              \
-      if constexpr (PROF_BUILDS)                                                                             \
-        hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, NN, true, 0, 0>), dim3(blocks), dim3(64), shmem, stream, \
-                           d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs);   \
-      else return -2;                                                                                        \
-    } else if (simple)                                                                                         \
-      hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, NN, false, 0, KIND>), dim3(blocks), dim3(64), shmem, stream, \
-                         d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs);     \
-    else if constexpr (NN < 24)                                                                              \
-      hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, NN, false, 2, KIND>), dim3(blocks), dim3(64), shmem, stream, \
-                         d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs);     \
-    else                                                                                                     \
-      hipLaunchKernelGGL((tds_step_kernel<T, TR, GG, NN, false, 1, KIND>), dim3(blocks), dim3(64), shmem, stream, \
-                         d_model, L, x_in, y_out, actions, x_feedback, obs_out, ovf, prof, ctl, n_envs);     \
-  } while (0)
-  // the phase-stamp builds exist for the plain kernels with double records only (a diagnostic: profiles/*_phases.txt)
-  constexpr bool PROF_BUILDS = KIND == 0 && sizeof(T) == 8 && sizeof(TR) == 8;
-  if (prof && !PROF_BUILDS) return -2;
   // straight-line kernel when the launch is exactly one normal step without any reset
   const bool simple = ctl.nsub == 1 && ctl.reset_mode == TDS_RESET_NONE && ctl.policy == nullptr &&
                       ctl.obs_ring == nullptr && ctl.y_ring == nullptr;  // (record rings: the step-loop builds write them)
-  // step-loop build: above one wavefront per SIMD (256 CUs x 4 SIMDs) the two-wavefronts-per-SIMD compilation wins
-  // (option loop_occ = 1 / 2 forces either: TDS_FORM_LOOP_OCC*)
-  const int loop_force = (form & TDS_FORM_LOOP_OCC2) ? 2 : ((form & TDS_FORM_LOOP_OCC1) ? 1 : 0);
-  // (>= 24 padded dof: the straight-line build is itself at one wavefront per SIMD; the two-wave loop build would
-  //  spill hundreds of registers there)
-  // (round 4: compiled without MachineLICM the two-wavefronts-per-SIMD compilation of the kernels up to 14 padded dof
-  //  holds no scratch — 245 VGPR — and is taken at ANY grid size: the one-wavefront-per-SIMD compilation (256 VGPR + 20
-  //  AGPR copies) buys nothing there any more, and its <double, double, 16, 8> instantiation does not terminate when
-  //  built without the pass — profiles/r04_diag_loop_hang.txt.  Round 5: that compilation is no longer INSTANTIATED
-  //  below 14 padded dof — nothing can launch it; option loop_occ = 1 is refused there by tds_api.hip: launch(),
-  //  TDS_ERR_UNSUPPORTED, and tests/test_options.py runs the 8-dof loop launches under a watchdog)
-  // (round 6: below 24 padded dof only the two-wavefronts-per-SIMD compilation is instantiated — the robots whose batch
-  //  sizes made the other one worth its build time, 14 and 18 dof, run in kernels of their own: tds_oct.hip, tds_quad.hip)
-  (void)loop_force;
-  const int key = lanes_per_env * 100 + L.NDP;
-  switch (key) {
-#define TDS_CASE(GG, NN) \
-  case GG * 100 + NN:    \
-    if constexpr (tds_instantiate(GG * 100 + NN)) TDS_LAUNCH(GG, NN); else return -1; \
-    break;
-    TDS_CASE(16, 8) TDS_CASE(16, 14) TDS_CASE(32, 18) TDS_CASE(16, 16) TDS_CASE(32, 8) TDS_CASE(32, 16) TDS_CASE(32, 24)
-    TDS_CASE(32, 32) TDS_CASE(64, 8) TDS_CASE(64, 16)
-#undef TDS_CASE
-    default:
-      return -1;
-  }
-#undef TDS_LAUNCH
+  const bool stamped = prof != nullptr;
+  // (the step-loop compilation follows from the key — see the table; TDS_FORM_LOOP_OCC* have nothing left to choose from)
+  auto launch = [&](bool loop, bool w2) {
+    return tds_visit_builds<T, TR, KIND>(lanes_per_env, L.NDP, [&](TdsStepKernelFn<T, TR> kernel, bool kstamped, bool kloop, bool kw2) {
+      if (kstamped != stamped || kloop != loop || kw2 != w2) return false;
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kw2 ? 128 : 64), shmem, stream, d_model, L, x_in, y_out, actions,
+                         x_feedback, obs_out, ovf, prof, ctl, n_envs);
+      return true;
+    });
+  };
+  // the two-wavefront build where the key has one, else the one-wavefront build; a stamped launch that has no step-loop
+  // build takes the stamped straight-line one
+  int r = launch(!simple, two_waves);
+  if (r == 0 && two_waves) r = launch(!simple, false);
+  if (r == 0 && stamped && !simple) r = launch(false, false);
+  if (r < 0) return -1;
+  if (r == 0) return -2;  // (phase stamps: plain kernels with double records only)
   return (int)hipGetLastError();
 }
 
+// raises the dynamic-LDS ceiling of EVERY build of the key: whatever the launcher can pick
 template <typename T, typename TR, int KIND>
 int tds_kernel_max_dynamic_lds_impl(int lanes_per_env, int ndp, int bytes) {
   hipError_t e = hipSuccess;
-#define TDS_ATTR(GG, NN)                                                                                        \
-  do {                                                                                                          \
-    e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, false, 0, KIND>,                         \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                                 \
-    if constexpr (NN >= 24) {                                                                                   \
-      if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, false, 1, KIND>,                     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                             \
-    } else {                                                                                                    \
-      if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, false, 2, KIND>,                     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                             \
-    }                                                                                                           \
-    if constexpr (KIND == 0 && sizeof(T) == 8 && sizeof(TR) == 8) {                                             \
-      if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, true, 0, 0>,                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                             \
-    }                                                                                                           \
-    if constexpr (KIND == 0 && NN <= 14) {                                                                       \
-      if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, false, 0, 0, true>,                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                             \
-      if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute((const void *)tds_step_kernel<T, TR, GG, NN, false, 1, 0, true>,                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);                             \
-    }                                                                                                           \
-  } while (0)
-  switch (lanes_per_env * 100 + ndp) {
-#define TDS_CASE(GG, NN) \
-  case GG * 100 + NN:    \
-    if constexpr (tds_instantiate(GG * 100 + NN)) TDS_ATTR(GG, NN); \
-    break;
-    TDS_CASE(16, 8) TDS_CASE(16, 14) TDS_CASE(32, 18) TDS_CASE(16, 16) TDS_CASE(32, 8) TDS_CASE(32, 16) TDS_CASE(32, 24)
-    TDS_CASE(32, 32) TDS_CASE(64, 8) TDS_CASE(64, 16)
-#undef TDS_CASE
-    default: return -1;
-  }
-#undef TDS_ATTR
-  return (int)e;
+  const int r = tds_visit_builds<T, TR, KIND>(lanes_per_env, ndp, [&](TdsStepKernelFn<T, TR> kernel, bool, bool, bool) {
+    e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e != hipSuccess;
+  });
+  return r < 0 ? -1 : (int)e;
 }
 
-// The file is compiled fifteen times (csrc/Makefile): -DTDS_ONLY_F64 / -DTDS_ONLY_F32 / -DTDS_ONLY_MIX pick the build
+// The file is compiled twelve times (csrc/Makefile): -DTDS_ONLY_F64 / -DTDS_ONLY_F32 / -DTDS_ONLY_MIX pick the build
 // (compute scalar, record scalar) = (double, double) / (float, float) / (double, float), -DTDS_ONLY_KIND=0..4 the
 // kernel kind (plain / floating base / spherical joints / several bodies / several bodies with floating bases), so
-// that the parts of the kernel set build in parallel.
-// (tds_make_lds_layout and tds_padded_dof live in the KIND 0 units.)
+// that the parts of the kernel set build in parallel.  Without either, every build / every kind.
 #define TDS_INSTANTIATE(TT, TR, KV)                                                                                     \
   template int tds_launch_step_impl<TT, TR, KV>(const DevModel<TT> *, const DevModel<TT> &, const TdsLds &, int,       \
                                                 const TR *, TR *, const TR *, TR *, TR *, TT *, int, hipStream_t,     \
                                                 const TdsStepCtl &, long long *, int);                                 \
   template int tds_kernel_max_dynamic_lds_impl<TT, TR, KV>(int, int, int);
-#if !defined(TDS_ONLY_KIND)
-#define TDS_ALL_KINDS 1
-#define TDS_ONLY_KIND -1
-#endif
 #if !defined(TDS_ONLY_F64) && !defined(TDS_ONLY_F32) && !defined(TDS_ONLY_MIX)
 #define TDS_ONLY_F64 1
 #define TDS_ONLY_F32 1
 #define TDS_ONLY_MIX 1
 #endif
-#if TDS_ONLY_KIND == 0 || defined(TDS_ALL_KINDS)
-#define TDS_INSTANTIATE_K0(TT, TR) TDS_INSTANTIATE(TT, TR, 0)
+#ifdef TDS_ONLY_KIND
+#define TDS_INSTANTIATE_KINDS(TT, TR) TDS_INSTANTIATE(TT, TR, TDS_ONLY_KIND)
 #else
-#define TDS_INSTANTIATE_K0(TT, TR)
-#endif
-#if TDS_ONLY_KIND == 1 || defined(TDS_ALL_KINDS)
-#define TDS_INSTANTIATE_K1(TT, TR) TDS_INSTANTIATE(TT, TR, 1)
-#else
-#define TDS_INSTANTIATE_K1(TT, TR)
-#endif
-#if TDS_ONLY_KIND == 2 || defined(TDS_ALL_KINDS)
-#define TDS_INSTANTIATE_K2(TT, TR) TDS_INSTANTIATE(TT, TR, 2)
-#else
-#define TDS_INSTANTIATE_K2(TT, TR)
-#endif
-#if TDS_ONLY_KIND == 3 || defined(TDS_ALL_KINDS)
-#define TDS_INSTANTIATE_K3(TT, TR) TDS_INSTANTIATE(TT, TR, 3)
-#else
-#define TDS_INSTANTIATE_K3(TT, TR)
-#endif
-#if TDS_ONLY_KIND == 4 || defined(TDS_ALL_KINDS)
-#define TDS_INSTANTIATE_K4(TT, TR) TDS_INSTANTIATE(TT, TR, 4)
-#else
-#define TDS_INSTANTIATE_K4(TT, TR)
-#endif
 #define TDS_INSTANTIATE_KINDS(TT, TR) \
-  TDS_INSTANTIATE_K0(TT, TR) TDS_INSTANTIATE_K1(TT, TR) TDS_INSTANTIATE_K2(TT, TR) TDS_INSTANTIATE_K3(TT, TR) \
-  TDS_INSTANTIATE_K4(TT, TR)
-#if defined(TDS_ONLY_F64)
-#if (TDS_ONLY_KIND == 0 || defined(TDS_ALL_KINDS)) && !defined(TDS_ALT)
-template TdsLds tds_make_lds_layout<double>(const DevModel<double> &, int, int, bool);
+  TDS_INSTANTIATE(TT, TR, 0) TDS_INSTANTIATE(TT, TR, 1) TDS_INSTANTIATE(TT, TR, 2) TDS_INSTANTIATE(TT, TR, 3) TDS_INSTANTIATE(TT, TR, 4)
 #endif
+#ifdef TDS_ONLY_F64
 TDS_INSTANTIATE_KINDS(double, double)
+#endif
+#ifdef TDS_ONLY_MIX
+TDS_INSTANTIATE_KINDS(double, float)
+#endif
+#ifdef TDS_ONLY_F32
+TDS_INSTANTIATE_KINDS(float, float)
 #endif
 #ifdef TDS_ALT
 // the slot's entry point (tds_kernels.h: EXPERIMENT SLOTS); *lanes_ndp_key = the one instantiation this unit holds
@@ -4147,13 +3793,4 @@ extern "C" int TDS_ALT_PASTE(tds_alt_launch_, TDS_ALT)(const void *d_model, cons
                                                  (double *)x_feedback, (double *)obs_out, (double *)ovf, n_envs, stream, *ctl,
                                                  nullptr, form);
 }
-#endif
-#if defined(TDS_ONLY_MIX)
-TDS_INSTANTIATE_KINDS(double, float)
-#endif
-#if defined(TDS_ONLY_F32)
-#if TDS_ONLY_KIND == 0 || defined(TDS_ALL_KINDS)
-template TdsLds tds_make_lds_layout<float>(const DevModel<float> &, int, int, bool);
-#endif
-TDS_INSTANTIATE_KINDS(float, float)
 #endif

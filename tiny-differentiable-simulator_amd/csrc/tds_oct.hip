@@ -178,15 +178,14 @@ struct OctKernArgs {
 // the constants of the model as the kernel reads them: one table in LDS behind the environments' regions, copied from
 // DevModel::oct_tab (laid out by tds_build_oct_table on the host: tds_device_model.h, TDS_OCT_*) at the top of a launch
 using TB = TdsOctTab;
+// wavefront priorities of the two-wavefront builds: 1 = the main wavefront at priority 3, the helper at 0 (see the top of the step)
+constexpr int TDS_OCT_PRIO = 1;
 
+// record stores: plain stores (as non-temporal stores they changed nothing: tools/experiments/r06_not_kept.txt)
+#define OCT_ST(v, p) (*(p) = (v))
 // barrier between the two wavefronts of a workgroup (W2: LDS writes done, then s_barrier — neither wavefront waits for its
 // outstanding global stores); a compiler-level fence in the one-wave build, where the LDS executes a wavefront's
 // instructions in order
-#ifdef TDS_OCT_NT
-#define OCT_ST(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define OCT_ST(v, p) (*(p) = (v))
-#endif
 #define OCT_BAR()                                                                        \
   do {                                                                                   \
     if constexpr (W2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    \
@@ -281,9 +280,6 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // Two wavefronts per SIMD (BUILD 2): where a main wavefront shares its SIMD with a helper, the main one — the step's
   // instruction stream — issues first (Ant x 8192, same box: 7.93 / 8.09e8 -> 8.42 / 8.37e8 env-steps/s; no effect at one
   // wavefront per SIMD)
-#ifndef TDS_OCT_PRIO
-#define TDS_OCT_PRIO 1
-#endif
   if constexpr (W2 && TDS_OCT_PRIO != 0) {
     if (BUILD != 4 && wv == 0) __builtin_amdgcn_s_setprio(3);
     else __builtin_amdgcn_s_setprio(0);  // (a helper one step in front of a refill pass's wavefronts on its SIMD: measured, nothing)
@@ -1563,10 +1559,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       //  but the factors' reads, the root stage and the barrier — taken out in front: there is one exactly when NA > 0 and
       //  pgs_iters > 0, as in the main wavefront's loops)
       if (NA > 0 && pgs_iters > 0) {
-        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(3);
         help_get_factors();
         rows_root(0, rw);
-        if constexpr (TDS_OCT_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         OCT_BAR();
         const int nr = 3 * NA;
         int bo = 8 * OctLds::ZW;
