@@ -697,6 +697,51 @@ int tds_hip_inverse_dynamics_host(const tds_model_t *model, int n, const double 
 int tds_hip_point_jacobian_host(const tds_model_t *model, int n, const double *q, int link, const double *point,
                                 int is_local, double *jac);
 
+/* Batched contact query: what the step forward_zero(x) does about its plane contacts, for n records x [n][input_dim]
+   (f64, the record of tds_hip_jvp / tds_hip_jacobian / tds_hip_step_host), per environment.  n_c is the model's number
+   of plane contact points, a constant of the model: every point of every geometry (sphere 1, capsule 2, box 8, in
+   the order of the model's geometries; the reference keeps all points), 0 without a plane: tds_hip_contact_layout.
+   Scope and refusals are those of tds_hip_jacobian (one articulated body, 1-DoF and fixed joints, f64 handles; the
+   same messages).  Any n >= 1, independent of num_envs; the handle's resident state is not touched.  Enqueued on the
+   handle's stream as one launch with no host wait except where the work buffer (shared with tds_hip_jvp and
+   tds_hip_dynamics) grows.  Only the outputs whose pointers are non-NULL are computed and written:
+     contacts  [n][n_c][10]          world_normal_on_b (3) | world_point_on_b (3) | world_point_on_a (3) | distance
+                                     (the plane is body a, the robot body b; world.hpp:206-282)
+     jac       [n][n_c][3][dof_qd]   point_jacobian2(robot, link_b, world_point_on_b) (jacobian.hpp:13-90)
+     rows      [n][3 n_c][dof_qd]    the solver's J: normal rows, friction-1 rows, friction-2 rows
+                                     (mb_constraint_solver.hpp:278-388); exactly zero for a separated point
+                                     (distance >= 0)
+     rhs       [n][3 n_c]            the solver's b, at the velocities qd_pre
+     delassus  [n][3 n_c][3 n_c]     A = J M^-1 J^T + cfm 1, both triangles
+     impulse   [n][3 n_c]            p after the model's pgs_iterations sweeps of PGS, in row order
+     force     [n][n_c][3]           the world-frame force on the robot at world_point_on_b:
+                                     -(N p_n + t1 p_f1 + t2 p_f2) / dt, N, t1, t2 as tds_hip_contact_layout gives them
+     qd_pre    [n][dof_qd]           the velocities the solver reads: qd + dt qdd after PD or torque actuation and
+                                     forward dynamics
+     qd_post   [n][dof_qd]           qd_pre - M^-1 J^T p: the qd part of forward_zero(x)
+   An environment whose M is not positive definite has NaN in rows .. qd_post (contacts and jac stay valid).  With
+   n_c = 0 only qd_pre and qd_post have any extent. */
+typedef struct {  /* device pointers (tds_hip_contacts) or host pointers (tds_hip_contacts_host), each may be NULL */
+  void *contacts;
+  void *jac;
+  void *rows;
+  void *rhs;
+  void *delassus;
+  void *impulse;
+  void *force;
+  void *qd_pre;
+  void *qd_post;
+} tds_contact_out_t;
+int tds_hip_contacts(tds_hip_sim_t *sim, int n, const void *x_dev, const tds_contact_out_t *out);
+/* The same template on the CPU (host arrays, needs no GPU): the checker.  Returns TDS_ERR_INVALID_ARG where some
+   environment's M was not positive definite, after writing every output. */
+int tds_hip_contacts_host(const tds_model_t *model, int n, const double *x, const tds_contact_out_t *out);
+/* n_c, and per contact point its link (-1: the base) and the index of its geometry; dirs [9]: the contact normal
+   N = world_normal_on_b and the two friction directions t1, t2 of the rows (the same for every point: they follow
+   from the plane's normal).  Each pointer may be NULL.  A refused model gives minus its TDS_ERR_* code (and
+   tds_hip_last_error). */
+int tds_hip_contact_layout(const tds_model_t *model, int32_t *link, int32_t *geom, double *dirs);
+
 /* Batched inverse kinematics (the reference's TinyInverseKinematics::compute of src/tiny_inverse_kinematics.h:140-247,
    for n environments at once): from q_init [n][dof_q], move the actuated coordinates until the k body points (link
    links[j], point body_points[j][3] in the link's own frame; the same for every environment) reach

@@ -147,6 +147,10 @@ def lib():
         L.tds_hip_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 3 + [DP]
         L.tds_hip_inverse_dynamics_host.argtypes = [P, C.c_int] + [C.c_void_p] * 4
         L.tds_hip_point_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        CP = C.POINTER(ContactOut)
+        L.tds_hip_contacts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, CP]
+        L.tds_hip_contacts_host.argtypes = [P, C.c_int, C.c_void_p, CP]
+        L.tds_hip_contact_layout.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p]
         IP = C.POINTER(IkOptions)
         L.tds_hip_ik_default_options.argtypes = [IP]
         L.tds_hip_ik_default_options.restype = None
@@ -164,6 +168,14 @@ class DynOut(C.Structure):
 
 
 DYN_OUTPUTS = ("x_world", "mass_matrix", "bias", "qdd")
+
+
+CONTACT_OUTPUTS = ("contacts", "jac", "rows", "rhs", "delassus", "impulse", "force", "qd_pre", "qd_post")
+
+
+class ContactOut(C.Structure):
+    """tds_contact_out_t: the outputs of a contact query, each pointer NULL where the output is not wanted"""
+    _fields_ = [(k, C.c_void_p) for k in CONTACT_OUTPUTS]
 
 
 class IkOptions(C.Structure):
@@ -227,6 +239,35 @@ def _dyn_want(want):
     for k in want:
         if k not in DYN_OUTPUTS:
             raise ValueError(f"unknown dynamics output {k!r} (one of {DYN_OUTPUTS})")
+    return want
+
+
+def contact_layout(m: _model.Model) -> dict:
+    """The model's plane contact points (tds_hip_contact_layout): n_c, per point its link [n_c] (-1: the base) and
+    the index of its geometry [n_c] (int32), and the directions of the solver's rows: normal, t1, t2 [3] each"""
+    import numpy as np
+
+    nc = lib().tds_hip_contact_layout(C.byref(m), None, None, None)
+    if nc < 0:
+        _check(-nc)
+    link, geom, dirs = np.zeros(nc, dtype=np.int32), np.zeros(nc, dtype=np.int32), np.zeros(9)
+    lib().tds_hip_contact_layout(C.byref(m), link.ctypes.data, geom.ctypes.data, dirs.ctypes.data)
+    return {"n_c": nc, "link": link, "geom": geom, "normal": dirs[0:3], "t1": dirs[3:6], "t2": dirs[6:9]}
+
+
+def contact_shapes(m: _model.Model, n: int) -> dict:
+    """shapes of the outputs of a contact query over n records"""
+    nd, nc = m.dof_qd, contact_layout(m)["n_c"]
+    return {"contacts": (n, nc, 10), "jac": (n, nc, 3, nd), "rows": (n, 3 * nc, nd), "rhs": (n, 3 * nc),
+            "delassus": (n, 3 * nc, 3 * nc), "impulse": (n, 3 * nc), "force": (n, nc, 3), "qd_pre": (n, nd),
+            "qd_post": (n, nd)}
+
+
+def _contact_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for k in want:
+        if k not in CONTACT_OUTPUTS:
+            raise ValueError(f"unknown contact output {k!r} (one of {CONTACT_OUTPUTS})")
     return want
 
 
@@ -318,6 +359,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
+    "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
 ]
@@ -496,6 +538,28 @@ def point_jacobian_host(m: _model.Model, q, link: int, point, local: bool = Fals
     _check(lib().tds_hip_point_jacobian_host(C.byref(m), n, q.ctypes.data, int(link), ptp, int(bool(local)),
                                              jac.ctypes.data))
     return jac
+
+
+def contacts_host(m: _model.Model, x, want=CONTACT_OUTPUTS, out=None):
+    """The contact query on the CPU (tds_hip_contacts_host; the checker of HipSim.contacts, needs no GPU).
+
+    x [N, input_dim] float64: the records of step_host.  Returns a dict of the wanted CONTACT_OUTPUTS (shapes:
+    contact_shapes).  out: a dict of arrays to write into.  An environment whose M is not positive definite has NaN in
+    rows .. qd_post; the call then raises after writing (pass `out` to see what it wrote)."""
+    import numpy as np
+
+    want = _contact_want(want)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n = x.shape[0]
+    shapes = contact_shapes(m, n)
+    res = {}
+    for k in want:
+        a = out[k] if out is not None and k in out else np.zeros(shapes[k], dtype=np.float64)
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shapes[k], k
+        res[k] = a
+    o = ContactOut(**{k: v.ctypes.data for k, v in res.items()})
+    _check(lib().tds_hip_contacts_host(C.byref(m), n, x.ctypes.data, C.byref(o)))
+    return res
 
 
 def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points=None, q_reference=None,
@@ -1262,6 +1326,33 @@ class HipSim:
         _check(lib().tds_hip_point_jacobian(self.h, n, C.c_void_p(q.data_ptr()), int(link), ptp, int(bool(local)),
                                             C.c_void_p(jac.data_ptr())))
         return jac
+
+    # -- the contact query: points, Jacobians, rows, Delassus matrix, impulses, forces -----------------------------
+    def contacts(self, x, want=CONTACT_OUTPUTS, out=None):
+        """What the step forward_zero(x) does about its plane contacts at the records x [N, input_dim]: the wanted
+        CONTACT_OUTPUTS (shapes: contact_shapes(model, N)) as a dict of tensors on the handle's device.  out: a dict of
+        tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
+        import torch
+
+        want = _contact_want(want)
+        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
+        x = x.contiguous()
+        n = x.shape[0]
+        shapes = contact_shapes(self.model, n)
+        res = {}
+        for k in want:
+            t = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float64, device=x.device)
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k]
+            res[k] = t
+        # (an output without extent, n_c = 0, has no storage: it still counts as asked for)
+        nothing = torch.empty(1, dtype=torch.float64, device=x.device)
+        o = ContactOut(**{k: (t if t.numel() else nothing).data_ptr() for k, t in res.items()})
+        _check(lib().tds_hip_contacts(self.h, n, C.c_void_p(x.data_ptr()), C.byref(o)))
+        return res
+
+    def contact_forces(self, x):
+        """force [N, n_c, 3]: the world-frame contact force on the robot at each contact point of the step from x"""
+        return self.contacts(x, want=("force",))["force"]
 
     def inverse_kinematics(self, q_init, links, targets, body_points=None, q_reference=None, method="pinv", out=None,
                            **options):
