@@ -50,7 +50,7 @@
 #ifndef TDS_OCT_PROF_WG
 #define TDS_OCT_PROF_WG 3
 #endif
-__device__ unsigned long long tds_oct_prof_buf[32];
+__device__ unsigned long long tds_oct_prof_buf[64];
 // (shader clock, 100 MHz real-time clock) at the top of the first 32 iterations of the stamped workgroup's main wavefront: the
 // shader clock's frequency step by step (tools/oct_clock_ramp.py)
 __device__ unsigned long long tds_oct_prof_clk[64];
@@ -65,8 +65,31 @@ __device__ int tds_oct_prof_iter = 500;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "+v"(p_)::"memory");        \
     if (prof_on) prof_t[k] = t_;                                                                \
   } while (0)
+// a barrier with the clock in front of it and behind it (stamps k, k + 1): who arrives first and how long it waits
+// (tools/oct_profile.py); the window barriers behind the first one add their waits up in stamp k + 2
+#define OCT_BAR_T(k)       \
+  do {                     \
+    OCT_STAMP(k, tid);     \
+    OCT_BAR();             \
+    OCT_STAMP((k) + 1, tid); \
+  } while (0)
+#define OCT_BAR_W(k, first)                                                                     \
+  do {                                                                                          \
+    unsigned long long a_, b_;                                                                  \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(a_), "+v"(tid)::"memory");       \
+    OCT_BAR();                                                                                  \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(b_), "+v"(tid)::"memory");       \
+    if (prof_on && (first)) {                                                                   \
+      prof_t[k] = a_;                                                                           \
+      prof_t[(k) + 1] = b_;                                                                     \
+    } else if (prof_on) {                                                                       \
+      prof_t[(k) + 2] += b_ - a_;                                                               \
+    }                                                                                           \
+  } while (0)
 #else
 #define OCT_STAMP(k, pin) do { } while (0)
+#define OCT_BAR_T(k) OCT_BAR()
+#define OCT_BAR_W(k, first) OCT_BAR()
 #endif
 
 // -DTDS_OCT_MARKS: "; OCTMARK <name>" comment lines in the assembly at the phase boundaries (tools/oct_isa_phases.py counts the
@@ -216,6 +239,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   }
 #endif
   constexpr bool W2 = BUILD >= 2;
+  // BATCH_SCHUR: the Schur sums' operands requested a pass at a time, the root block's arithmetic across them (main_dyn2).  The
+  // step-loop build for one wavefront per SIMD only — the benchmark's: build 2 pays for the operands' registers with scratch
+  // (16-32 B), the straight-line form of build 3 with two more registers, and the one-wavefront build plays both roles in one
+  // stream: nothing waits for its main part (profiles/oct_kernel_resources_lds.txt).  Same arithmetic either way, term by term.
+  constexpr bool BATCH_SCHUR = LOOP && BUILD == 3;
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -287,7 +315,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   (void)is_main;
   (void)is_help;
 #ifdef TDS_OCT_PROF
-  unsigned long long prof_t[26];
+  unsigned long long prof_t[56] = {};  // 0 .. 13 phases, 24 .. 35 the main wavefront's barriers, 40 .. 51 the helper's
   const bool prof_on = blockIdx.x == TDS_OCT_PROF_WG && it == tds_oct_prof_iter;
   if (it == 0 && tid == 0 && blockIdx.x < 2048) {
     unsigned long long c_;
@@ -871,49 +899,116 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   auto main_dyn2 = [&]() {
     OCT_MARK("main_schur");
-    // the sums sum_lanes L_c[r] W[r'] of the Schur complement, entry e = r (r + 1) / 2 + r' on lane e mod 8 (three passes)
-    {
-      const T *const lcw = E + O.lcw;
-      const T *const wl = E + O.xs;
-      T *const Ssum = E + O.fac;
-      const int code = (int)CL[TB::SCHUR];  // (which entries this lane sums: table)
-#pragma unroll
-      for (int pass = 0; pass < 3; ++pass) {
-        const int rc = (code >> (6 * pass)) & 63;
-        const int r = rc >> 3, rp = rc & 7;
-        const int e = (r * (r + 1)) / 2 + rp;
-        T acc = T(0);
-#pragma unroll
-        for (int l = 0; l < 8; ++l) acc += lcw[l * OctLds::LCW + r] * wl[l * 6 + rp];
-        Ssum[e] = acc;
-      }
-    }
-    OCT_MARK("main_Rblock");
     const T ax3[6] = {T(1), T(0), T(0), pA3[0], pA3[1], pA3[2]}, ax4[6] = {A4[0], A4[1], A4[2], pA4[0], pA4[1], pA4[2]},
             ax5[6] = {A5[0], A5[1], A5[2], pA5[0], pA5[1], pA5[2]};
-    // the root block R[r][r'] = s_r . (It s_r') in registers (packed lower triangle, r (r + 1) / 2 + r'): the prismatic
-    // axes are unit vectors, It e_k = (h x e_k | m e_k)
     T Sm[21];
-    {
+    // the root block R[r][r'] = s_r . (It s_r') in registers (packed lower triangle, r (r + 1) / 2 + r'): the prismatic
+    // axes are unit vectors, It e_k = (h x e_k | m e_k).  In three parts, one per revolute axis (the first with the prismatic rows)
+    T F3[6], F4[6];
+    auto root_block_a1 = [&]() {
       const T m = It[9];
-      T F3[6], F4[6], F5[6];
       times_inertia(It, ax3, F3);
-      times_inertia(It, ax4, F4);
-      times_inertia(It, ax5, F5);
       Sm[0] = m;
       Sm[1] = T(0); Sm[2] = m;
       Sm[3] = T(0); Sm[4] = T(0); Sm[5] = m;
       Sm[6] = F3[3]; Sm[7] = F3[4]; Sm[8] = F3[5]; Sm[9] = dot6(ax3, F3);
+    };
+    auto root_block_a2 = [&]() {
+      times_inertia(It, ax4, F4);
       Sm[10] = F4[3]; Sm[11] = F4[4]; Sm[12] = F4[5]; Sm[13] = dot6(ax4, F3); Sm[14] = dot6(ax4, F4);
+    };
+    auto root_block_b = [&]() {
+      T F5[6];
+      times_inertia(It, ax5, F5);
       Sm[15] = F5[3]; Sm[16] = F5[4]; Sm[17] = F5[5]; Sm[18] = dot6(ax5, F3); Sm[19] = dot6(ax5, F4); Sm[20] = dot6(ax5, F5);
+    };
+    // the sums sum_lanes L_c[r] W[r'] of the Schur complement, entry e = r (r + 1) / 2 + r' on lane e mod 8 (three passes)
+    {
+      const T *const lcw = E + O.lcw;
+      const T *const wl = E + O.xs;  // (W = L_c D in the impulses' slots: every read of it stands here, behind barrier (1b) and in
+                                     //  front of barrier (2), in either order of the reads; the sweep's impulses come behind (2))
+      T *const Ssum = E + O.fac;
+      const int code = (int)CL[TB::SCHUR];  // (which entries this lane sums: table)
+      if constexpr (BATCH_SCHUR) {
+        // A pass's 16 operands are requested in one batch and a third of the root block — f64 arithmetic that depends on no
+        // LDS value: the rows of one revolute axis — runs while they arrive.  In the loop below a pass's reads were three
+        // exposed round trips, and the root block sat behind the last pass, where it covered nothing.  (Two passes' operands
+        // at once, or all three, cost the one-wavefront-per-SIMD build 28 / 72 accumulation registers' worth of copies and
+        // the other build scratch.)  The three FMA chains are those of the loop below, term by term.
+        T la[3][8], wa[3][8];
+        int ee[3];
+        auto ask = [&](auto pc) {
+          constexpr int pass = decltype(pc)::value;
+          const int rc = (code >> (6 * pass)) & 63;
+          const int r = rc >> 3, rp = rc & 7;
+          ee[pass] = (r * (r + 1)) / 2 + rp;
+#pragma unroll
+          for (int l = 0; l < 8; ++l) {
+            la[pass][l] = lcw[l * OctLds::LCW + r];
+            wa[pass][l] = wl[l * 6 + rp];
+          }
+        };
+        auto sum = [&](auto pc) {
+          constexpr int pass = decltype(pc)::value;
+          T acc = T(0);
+#pragma unroll
+          for (int l = 0; l < 8; ++l) acc += la[pass][l] * wa[pass][l];
+          Ssum[ee[pass]] = acc;
+        };
+        // (fences stand where arithmetic must not slide in front of a request or behind its sums.  None separates sum(p)
+        //  from ask(p + 1): both sit between two fences, the back end issues the eight reads first because they have no
+        //  operand to wait for — tools/oct_isa_phases.py's exposed-wait column shows it if that ever changes)
+        ask(std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+        root_block_a1();
+        __builtin_amdgcn_sched_barrier(0);
+        sum(std::integral_constant<int, 0>{});
+        ask(std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        root_block_a2();
+        __builtin_amdgcn_sched_barrier(0);
+        sum(std::integral_constant<int, 1>{});
+        ask(std::integral_constant<int, 2>{});
+        __builtin_amdgcn_sched_barrier(0);
+        root_block_b();
+        __builtin_amdgcn_sched_barrier(0);
+        sum(std::integral_constant<int, 2>{});
+      } else {
+#pragma unroll
+        for (int pass = 0; pass < 3; ++pass) {
+          const int rc = (code >> (6 * pass)) & 63;
+          const int r = rc >> 3, rp = rc & 7;
+          const int e = (r * (r + 1)) / 2 + rp;
+          T acc = T(0);
+#pragma unroll
+          for (int l = 0; l < 8; ++l) acc += lcw[l * OctLds::LCW + r] * wl[l * 6 + rp];
+          Ssum[e] = acc;
+        }
+      }
     }
-    OCT_SYNC();
+    OCT_MARK("main_Rblock");
+    if constexpr (!BATCH_SCHUR) {
+      root_block_a1();
+      root_block_a2();
+      root_block_b();
+    }
+    OCT_SYNC();  // (the sums of every lane are in LDS, in front of any lane's read of them: a wavefront's LDS operations execute in order)
     OCT_MARK("main_ldl6");
     // ... the Schur complement, factorised redundantly on every lane: Ls (strictly lower, row-major packed), 1 / D
     {
       const T *const Ssum = E + O.fac;
+      if constexpr (BATCH_SCHUR) {
+        // (the 21 sums requested in one batch: one round trip, not one per pair of them)
+        T ss[21];
 #pragma unroll
-      for (int e = 0; e < 21; ++e) Sm[e] -= Ssum[e];
+        for (int e = 0; e < 21; ++e) ss[e] = Ssum[e];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 21; ++e) Sm[e] -= ss[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 21; ++e) Sm[e] -= Ssum[e];
+      }
       static_for<0, 6>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         const T rs = rsqrt_full<T>(Sm[(k * (k + 1)) / 2 + k]);
@@ -1516,11 +1611,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   if constexpr (W2) {
     if (wv == 0) {
       main_kin();
-      OCT_BAR();  // (1)
+      OCT_BAR_T(24);  // (1)
       main_dyn();
-      OCT_BAR();  // (1b)
+      OCT_BAR_T(26);  // (1b)
       main_dyn2();
-      OCT_BAR();  // (2)
+      OCT_BAR_T(28);  // (2)
       main_get_count();
       main_fd();
       main_sweep_consts();
@@ -1531,7 +1626,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       int bo = 0;
       for (int pit = 0; pit < pgs_iters; ++pit) {
         for (int w0 = 0; w0 < nr; w0 += 8) {
-          OCT_BAR();
+          OCT_BAR_W(30, (pit | w0) == 0);
           if ((pit | w0) == 0) OCT_STAMP(12, tid);
           if (pit == 0) main_sweep(std::true_type{}, w0, bo);
           else main_sweep(std::false_type{}, w0, bo);
@@ -1541,27 +1636,27 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       }
       main_fin();
       main_pool();
-      OCT_BAR();  // (0)
+      OCT_BAR_T(34);  // (0)
     } else {
-      OCT_BAR();  // (1)
+      OCT_BAR_T(40);  // (1)
       help_np();
       RowRegs rw = {};
       if (NA > 0) rows_geom(0, 0, rw);
-      OCT_BAR();  // (1b)
+      OCT_BAR_T(42);  // (1b)
       if (NA > 0) {
         rows_leg(0, rw);
         rows_park(rw);
       }
       help_poses();
       if (NA > 0) rows_fetch(rw);
-      OCT_BAR();  // (2)
+      OCT_BAR_T(44);  // (2)
       // (the same windows as the main wavefront's two loops, the first one — the stretch the main wavefront waits for: nothing
       //  but the factors' reads, the root stage and the barrier — taken out in front: there is one exactly when NA > 0 and
       //  pgs_iters > 0, as in the main wavefront's loops)
       if (NA > 0 && pgs_iters > 0) {
         help_get_factors();
         rows_root(0, rw);
-        OCT_BAR();
+        OCT_BAR_W(46, true);
         const int nr = 3 * NA;
         int bo = 8 * OctLds::ZW;
         for (int pit = 0; pit < pgs_iters; ++pit) {
@@ -1569,12 +1664,12 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             rows_geom(w0, bo, rw);
             rows_leg(bo, rw);
             rows_root(bo, rw);
-            OCT_BAR();
+            OCT_BAR_W(46, false);
             bo = 8 * OctLds::ZW - bo;
           }
         }
       }
-      OCT_BAR();  // (0)
+      OCT_BAR_T(50);  // (0)
       help_rec();
     }
   } else {
@@ -1610,6 +1705,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 #ifdef TDS_OCT_PROF
   if (prof_on && (tid & 63) == 0) {
     // (main: stamps 0 .. 7 into buf[0 .. 7]; helper: stamps 8 .. 11 and the window stamp 10 into buf[8 .. 11]; one-wave: all)
+    // (barriers: the main wavefront's stamps 24 .. 35, the helper's 40 .. 51 — OCT_BAR_T / OCT_BAR_W; 16 .. 23 the per-row slots
+    //  of tools/oct_profile.py's row line, which no build sets at present)
 #pragma unroll
     for (int k = 16; k < 24; ++k)
       if (is_main) tds_oct_prof_buf[k] = prof_t[k];
@@ -1617,6 +1714,12 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     for (int k = 0; k < 14; ++k)
       if (((k < 8 || k >= 12) && is_main) || (k >= 8 && k < 12 && is_help)) tds_oct_prof_buf[k] = prof_t[k];
     if (is_help) tds_oct_prof_buf[15] = (unsigned long long)NA;
+#pragma unroll
+    for (int k = 24; k < 36; ++k)
+      if (is_main) tds_oct_prof_buf[k] = prof_t[k];
+#pragma unroll
+    for (int k = 40; k < 52; ++k)
+      if (is_help) tds_oct_prof_buf[k] = prof_t[k];
   }
 #endif
   if constexpr (LOOP) {
@@ -1660,8 +1763,8 @@ extern "C" int tds_oct_prof_workgroups(unsigned long long *out, int n_wg) {
 extern "C" int tds_oct_prof_clocks(unsigned long long *out64) {
   return hipMemcpyFromSymbol(out64, HIP_SYMBOL(tds_oct_prof_clk), 64 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
 }
-extern "C" int tds_oct_prof_read(unsigned long long *out32, int iter) {  // iter >= 0: which iteration the NEXT launches stamp
-  if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(tds_oct_prof_buf), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;
+extern "C" int tds_oct_prof_read(unsigned long long *out64, int iter) {  // iter >= 0: which iteration the NEXT launches stamp
+  if (out64 && hipMemcpyFromSymbol(out64, HIP_SYMBOL(tds_oct_prof_buf), 64 * sizeof(unsigned long long)) != hipSuccess) return -1;
   if (iter >= 0 && hipMemcpyToSymbol(HIP_SYMBOL(tds_oct_prof_iter), &iter, sizeof(int)) != hipSuccess) return -1;
   return 0;
 }

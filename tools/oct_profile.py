@@ -42,7 +42,7 @@ def main():
     y_ring = torch.zeros((slots, n, 160), dtype=torch.float64, device="cuda")
     L = hip_backend.lib()
     L.tds_oct_prof_read.argtypes = [C.c_void_p, C.c_int]
-    buf = (C.c_ulonglong * 32)()
+    buf = (C.c_ulonglong * 64)()
     assert L.tds_oct_prof_read(None, it) == 0
     for rep in range(3):
         sim.step_many_rings(actions, 1000, obs_ring, y_ring)
@@ -53,7 +53,7 @@ def main():
     ev1.record()
     torch.cuda.synchronize()
     assert L.tds_oct_prof_read(buf, -1) == 0
-    t = [int(buf[k]) for k in range(32)]
+    t = [int(buf[k]) for k in range(64)]
     print(f"ant x {n}: 1000-step ring launch {ev0.elapsed_time(ev1) * 1e3 / 1000:.2f} us per step (stamped build, option oct_w2 = {w2}); "
           f"iteration {it} of workgroup 3: NA = {t[15]}")
     print(f"  main wavefront, top of the step -> end of its step: {t[7] - t[0]} cycles")
@@ -65,6 +65,28 @@ def main():
         print("    rows of the first window, end of each row's chain after the window was solved: " + " ".join(str(t[16 + k] - t[12]) for k in range(8)))
     print("  helper (cycles relative to the main wavefront's top of step):")
     print(f"    narrowphase done at {t[8] - t[0]}, visual poses out at {t[9] - t[0]}, last row window solved at {t[10] - t[0]}, records out at {t[11] - t[0]}")
+    if w2:
+        barriers(t)
+
+
+BARRIERS = ["(1) kinematics in LDS", "(1b) leg factors, couplings", "(2) root factors, contact list", "first row window", "(0) state, reward, done"]
+
+
+def barriers(t):
+    """Per barrier of the two-wavefront build: arrival of both wavefronts (cycles from the main wavefront's top of step), who was
+    first and how long it waited for the other (stamps 24 + 2 b / 40 + 2 b in front of the barrier, + 1 behind it; the window
+    barriers behind the first one add up in stamps 32 / 48)."""
+    print("  barriers: main wavefront arrives | helper arrives | first to arrive, its wait for the other | released (main, helper)")
+    for b, name in enumerate(BARRIERS):
+        km, kh = 24 + 2 * b + (2 if b == 4 else 0), 40 + 2 * b + (2 if b == 4 else 0)
+        if t[km] == 0 or t[kh] == 0:
+            print(f"    {name}: not passed in this iteration")
+            continue
+        am, ah = t[km] - t[0], t[kh] - t[0]
+        who = "main" if am <= ah else "helper"
+        print(f"    {name:34s} {am:6d} | {ah:6d} | {who:6s} waits {abs(ah - am):5d} | {t[km + 1] - t[0]:6d} {t[kh + 1] - t[0]:6d}")
+    print(f"    later row windows, time inside their barriers in all: main wavefront {t[32]}, helper {t[48]}")
+    print("    (a stamp costs the wavefront that takes it ~40-60 cycles: a clock read and its wait)")
 
 
 if __name__ == "__main__":
