@@ -45,8 +45,13 @@ def some_link(m):
     return max(joints) if joints else -1
 
 
-@pytest.mark.parametrize("n", [1, 7, 4096])
-@pytest.mark.parametrize("name", MODELS)
+# n: one lane, a ragged wave, one lane past a wave (more than one workgroup), a full grid; and on the smallest model
+# 16 384 + 37 environments, past the lanes of a launch: the grid's stride and its ragged tail
+LANE_CAP = 16384
+CASES = [(name, n) for name in MODELS for n in (1, 7, 65, 4096)] + [("cartpole", LANE_CAP + 37)]
+
+
+@pytest.mark.parametrize("name,n", CASES)
 def test_device_matches_host(name, n, built):
     m = tds_amd.load_model(name)
     x = records(name, n)
@@ -59,7 +64,12 @@ def test_device_matches_host(name, n, built):
     d = {k: v.cpu().numpy() for k, v in sim.dynamics(cu(q), cu(qd), cu(tau), want=wanted(m)).items()}
     jw = sim.point_jacobian(cu(q), link, cu(pts)).cpu().numpy()
     jl = sim.point_jacobian(cu(q), link, cu(pts), local=True).cpu().numpy()
-    idx = np.arange(n) if n <= 64 else np.random.default_rng(1).choice(n, 64, replace=False)
+    if n <= 65:
+        idx = np.arange(n)
+    elif n <= LANE_CAP:
+        idx = np.random.default_rng(1).choice(n, 64, replace=False)
+    else:  # every row past the cap and a sample below it
+        idx = np.concatenate([np.random.default_rng(1).choice(LANE_CAP, 27, replace=False), np.arange(LANE_CAP, n)])
     h = hb.dynamics_host(m, q[idx], qd[idx], tau[idx], want=wanted(m))
     worst = 0.0
     for k in wanted(m):

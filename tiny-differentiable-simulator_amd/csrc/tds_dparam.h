@@ -86,12 +86,8 @@ inline int tds_param_check_sel(const tds_model_t *m, int p, const tds_param_t *p
 
 // the host entry points' model checks: class (refusals as for the Jacobians), blob indices, selection
 inline int tds_param_host_prepare(const tds_model_t *m, int p, const tds_param_t *params, int *cls) {
-  const char *why = "";
-  *cls = tds_jvp_pick(m, &why);
-  if (*cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
-  const int rc = tds_hip_model_check(m);
-  if (rc) return rc;
-  return tds_param_check_sel(m, p, params);
+  const int rc = tds_diff_host_check(m, cls);
+  return rc ? rc : tds_param_check_sel(m, p, params);
 }
 
 }  // namespace

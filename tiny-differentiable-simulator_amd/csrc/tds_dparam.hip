@@ -170,7 +170,7 @@ int tds_vjp_param_launch(tds_hip_sim *s, TdsVjpParamArgs a, const tds_param_t *p
   const long long n_lanes = tds_vjp_lanes(a.n);
   const size_t sel = (size_t)a.p * sizeof(tds_param_t);
   const TdsVjpLayout<TdsVjpParamLane<B>> lay(n_lanes, s->model.input_dim + a.p, sel);
-  int rc = tds_jvp_tmp(s, lay.total);
+  int rc = tds_work_buffer(s, lay.total);
   if (rc) return rc;
   // the selection after the overflow flag's slot, copied with a blocking copy: earlier calls on the stream may still
   // read the work buffer
@@ -201,18 +201,16 @@ int tds_hip_jvp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const 
     return fail(TDS_ERR_INVALID_ARG, "tds_hip_jvp_params: NULL or empty argument%s");
   if (p == 0 && k > 0) return tds_hip_jvp(s, n, x_dev, k, v_dev, y_dev, jv_dev);  // the plain path
   DeviceGuard guard(s->device);
-  int cls, rc = tds_jvp_prepare(s, &cls);
+  int cls, rc = tds_diff_prepare(s, &cls);
   if (rc) return rc;
   if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
   // work buffer: the lanes' work objects (k = 0: of the double step) | the selection
-  size_t ws;
-  switch (cls) {
-    case 0: ws = k ? tds_jvp_param_ws_bytes<TdsBoundS>(n, k) : tds_param_y_ws_bytes<TdsBoundS>(n); break;
-    case 1: ws = k ? tds_jvp_param_ws_bytes<TdsBoundA>(n, k) : tds_param_y_ws_bytes<TdsBoundA>(n); break;
-    default: ws = k ? tds_jvp_param_ws_bytes<TdsBoundL>(n, k) : tds_param_y_ws_bytes<TdsBoundL>(n); break;
-  }
+  const size_t ws = tds_with_bound(cls, [&](auto b) {
+    using B = typename decltype(b)::type;
+    return k ? tds_jvp_param_ws_bytes<B>(n, k) : tds_param_y_ws_bytes<B>(n);
+  });
   const size_t sel = (size_t)p * sizeof(tds_param_t);
-  if ((rc = tds_jvp_tmp(s, ws + sel))) return rc;
+  if ((rc = tds_work_buffer(s, ws + sel))) return rc;
   tds_param_t *d_sel = (tds_param_t *)((char *)s->d_diff_tmp + ws);
   if (p > 0) {  // a blocking copy: earlier calls on the stream may still read the work buffer
     TDS_HIP_TRY(hipStreamSynchronize(s->stream));
@@ -221,16 +219,13 @@ int tds_hip_jvp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const 
   const TdsJvpParamArgs a = {(const tds_model_t *)s->d_diff_model, n, k, p, (const double *)x_dev,
                              (const double *)theta_dev, (const double *)v_dev, d_sel, (double *)y_dev,
                              (double *)jv_dev};
-  if (k == 0) switch (cls) {  // y only: the double step
-      case 0: return tds_param_y_launch<TdsBoundS>(s, a, s->d_diff_tmp);
-      case 1: return tds_param_y_launch<TdsBoundA>(s, a, s->d_diff_tmp);
-      default: return tds_param_y_launch<TdsBoundL>(s, a, s->d_diff_tmp);
-    }
-  switch (cls) {
-    case 0: return tds_jvp_param_launch<TdsBoundS>(s, a, s->d_diff_tmp);
-    case 1: return tds_jvp_param_launch<TdsBoundA>(s, a, s->d_diff_tmp);
-    default: return tds_jvp_param_launch<TdsBoundL>(s, a, s->d_diff_tmp);
-  }
+  if (k == 0)  // y only: the double step
+    return tds_with_bound(cls, [&](auto b) {
+      return tds_param_y_launch<typename decltype(b)::type>(s, a, s->d_diff_tmp);
+    });
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_jvp_param_launch<typename decltype(b)::type>(s, a, s->d_diff_tmp);
+  });
 }
 
 int tds_hip_vjp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const tds_param_t *params_host,
@@ -239,18 +234,16 @@ int tds_hip_vjp_params(tds_hip_sim_t *s, int n, const void *x_dev, int p, const 
     return fail(TDS_ERR_INVALID_ARG, "tds_hip_vjp_params: NULL or empty argument%s");
   if (p == 0) return tds_hip_vjp(s, n, x_dev, k, w_dev, y_dev, wj_dev);  // the plain path
   DeviceGuard guard(s->device);
-  int cls, rc = tds_jvp_prepare(s, &cls);
+  int cls, rc = tds_diff_prepare(s, &cls);
   if (rc) return rc;
   if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
   TdsVjpParamArgs a;
   static_cast<TdsVjpArgs &>(a) = {(const tds_model_t *)s->d_diff_model, n, k, (const double *)x_dev,
                                   (const double *)w_dev, (double *)y_dev, (double *)wj_dev, nullptr};
   a.p = p, a.params = nullptr, a.theta = (const double *)theta_dev;
-  switch (cls) {
-    case 0: return tds_vjp_param_launch<TdsBoundS>(s, a, params_host);
-    case 1: return tds_vjp_param_launch<TdsBoundA>(s, a, params_host);
-    default: return tds_vjp_param_launch<TdsBoundL>(s, a, params_host);
-  }
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_vjp_param_launch<typename decltype(b)::type>(s, a, params_host);
+  });
 }
 
 int tds_hip_jvp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
@@ -261,11 +254,7 @@ int tds_hip_jvp_params_host(const tds_model_t *model, int n, const double *x, in
   int cls, rc = tds_param_host_prepare(model, p, params, &cls);
   if (rc) return rc;
   const TdsJvpParamArgs a = {model, n, k, p, x, theta, v, params, y, jv};
-  switch (cls) {
-    case 0: return tds_jvp_param_host_impl<TdsBoundS>(a);
-    case 1: return tds_jvp_param_host_impl<TdsBoundA>(a);
-    default: return tds_jvp_param_host_impl<TdsBoundL>(a);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_jvp_param_host_impl<typename decltype(b)::type>(a); });
 }
 
 int tds_hip_vjp_params_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
@@ -278,11 +267,9 @@ int tds_hip_vjp_params_host(const tds_model_t *model, int n, const double *x, in
   TdsVjpParamArgs a;
   static_cast<TdsVjpArgs &>(a) = {model, n, k, x, w, y, wj, nullptr};
   a.p = p, a.params = params, a.theta = theta;
-  switch (cls) {
-    case 0: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundS>>(a, tape_cap, tape_len);
-    case 1: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundA>>(a, tape_cap, tape_len);
-    default: return tds_vjp_host_run<TdsVjpParamLane<TdsBoundL>>(a, tape_cap, tape_len);
-  }
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_vjp_host_run<TdsVjpParamLane<typename decltype(b)::type>>(a, tape_cap, tape_len);
+  });
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@ struct TdsIkParams {
 #define TDS_IK_PICK(a, k, s, c) \
   ((k) == 0 ? (a)[c] : (k) == 1 ? (a)[(s) + (c)] : (k) == 2 ? (a)[2 * (s) + (c)] : (a)[3 * (s) + (c)])
 
+// (the 16384 states of a full launch, tds_query.h: 140 MB of the handle's work buffer for Laikago's four feet)
 struct TdsIkLayout {
   TdsDynLayout d;  // q, pt, xp, xw, base, jac only
   int tgt, qref, J, A, F, e, z, y, dg, total;

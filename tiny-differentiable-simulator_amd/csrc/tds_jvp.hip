@@ -120,20 +120,12 @@ int tds_jvp_launch(tds_hip_sim *s, const TdsJvpArgs &a, void *ws) {
 }
 
 size_t tds_jvp_ws(int cls, int n, int kdirs) {
-  switch (cls) {
-    case 0: return tds_jvp_ws_bytes<TdsBoundS>(n, kdirs);
-    case 1: return tds_jvp_ws_bytes<TdsBoundA>(n, kdirs);
-    default: return tds_jvp_ws_bytes<TdsBoundL>(n, kdirs);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_jvp_ws_bytes<typename decltype(b)::type>(n, kdirs); });
 }
 
 int tds_jvp_dispatch(tds_hip_sim *s, int cls, const TdsJvpArgs &a) {
   void *ws = s->d_diff_tmp;  // the lanes' work objects lie at the front of the work buffer
-  switch (cls) {
-    case 0: return tds_jvp_launch<TdsBoundS>(s, a, ws);
-    case 1: return tds_jvp_launch<TdsBoundA>(s, a, ws);
-    default: return tds_jvp_launch<TdsBoundL>(s, a, ws);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_jvp_launch<typename decltype(b)::type>(s, a, ws); });
 }
 
 int tds_jac_check_sel(const tds_model_t *m, int n_rows, const int *rows, int n_cols, const int *cols) {
@@ -182,7 +174,7 @@ namespace tds_internal {
 
 // the work buffer holds at least `need` bytes.  Launches on the handle's stream use it one after the other; only a
 // buffer that has to grow is replaced, after the host waits for the earlier calls on the stream.
-int tds_jvp_tmp(tds_hip_sim *s, size_t need) {
+int tds_work_buffer(tds_hip_sim *s, size_t need) {
   if (need > s->diff_tmp_bytes) {
     TDS_HIP_TRY(hipStreamSynchronize(s->stream));
     if (s->d_diff_tmp) TDS_HIP_TRY(hipFree(s->d_diff_tmp));
@@ -194,7 +186,7 @@ int tds_jvp_tmp(tds_hip_sim *s, size_t need) {
 }
 
 // the handle's checks and its device copy of the model blob
-int tds_jvp_prepare(tds_hip_sim *s, int *cls) {
+int tds_diff_prepare(tds_hip_sim *s, int *cls) {
   if (s->dtype != TDS_DTYPE_F64) return fail(TDS_ERR_UNSUPPORTED, "step Jacobians: f64 handles only%s");
   const char *why = "";
   *cls = tds_jvp_pick(&s->model, &why);
@@ -213,9 +205,9 @@ extern "C" {
 int tds_hip_jvp(tds_hip_sim_t *s, int n, const void *x_dev, int k, const void *v_dev, void *y_dev, void *jv_dev) {
   if (!s || !x_dev || !v_dev || !jv_dev || n < 1 || k < 1) return fail(TDS_ERR_INVALID_ARG, "tds_hip_jvp: NULL or empty argument%s");
   DeviceGuard guard(s->device);
-  int cls, rc = tds_jvp_prepare(s, &cls);
+  int cls, rc = tds_diff_prepare(s, &cls);
   if (rc) return rc;
-  if ((rc = tds_jvp_tmp(s, tds_jvp_ws(cls, n, k)))) return rc;
+  if ((rc = tds_work_buffer(s, tds_jvp_ws(cls, n, k)))) return rc;
   TdsJvpArgs a = {(const tds_model_t *)s->d_diff_model, n, k, (const double *)x_dev, (const double *)v_dev,
                   nullptr, nullptr, 0, 0, (double *)y_dev, (double *)jv_dev};
   return tds_jvp_dispatch(s, cls, a);
@@ -227,7 +219,7 @@ int tds_hip_jacobian(tds_hip_sim_t *s, int n, const void *x_dev, int n_rows, con
   if (accumulate < TDS_JAC_ACCUMULATE_NONE || accumulate > TDS_JAC_ACCUMULATE_MEAN)
     return fail(TDS_ERR_INVALID_ARG, "tds_hip_jacobian: unknown accumulation method%s");
   DeviceGuard guard(s->device);
-  int cls, rc = tds_jvp_prepare(s, &cls);
+  int cls, rc = tds_diff_prepare(s, &cls);
   if (rc) return rc;
   if (!rows_host) n_rows = s->model.output_dim;
   if (!cols_host) n_cols = s->model.input_dim;
@@ -236,7 +228,7 @@ int tds_hip_jacobian(tds_hip_sim_t *s, int n, const void *x_dev, int n_rows, con
   const size_t ws = tds_jvp_ws(cls, n, n_cols);
   const size_t sel_bytes = ((size_t)(n_rows + n_cols) * sizeof(int) + 255) & ~(size_t)255;
   const size_t per_env = (size_t)n * n_rows * n_cols;
-  if ((rc = tds_jvp_tmp(s, ws + sel_bytes + (accumulate ? per_env * sizeof(double) : 0)))) return rc;
+  if ((rc = tds_work_buffer(s, ws + sel_bytes + (accumulate ? per_env * sizeof(double) : 0)))) return rc;
   int *d_rows = (int *)((char *)s->d_diff_tmp + ws), *d_cols = d_rows + n_rows;
   // a selection is copied with a blocking copy: earlier calls on the stream may still read the previous one
   if (rows_host || cols_host) TDS_HIP_TRY(hipStreamSynchronize(s->stream));
@@ -260,10 +252,7 @@ int tds_hip_jacobian_host(const tds_model_t *model, int n, const double *x, int 
   if (!model || !x || n < 1 || (!y && !jac)) return fail(TDS_ERR_INVALID_ARG, "tds_hip_jacobian_host: NULL or empty argument%s");
   if (accumulate < TDS_JAC_ACCUMULATE_NONE || accumulate > TDS_JAC_ACCUMULATE_MEAN)
     return fail(TDS_ERR_INVALID_ARG, "tds_hip_jacobian_host: unknown accumulation method%s");
-  const char *why = "";
-  const int cls = tds_jvp_pick(model, &why);
-  if (cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
-  int rc = tds_hip_model_check(model);  // indices of the blob in range (the handle's model passed it at creation)
+  int cls, rc = tds_diff_host_check(model, &cls);
   if (rc) return rc;
   if (!rows) n_rows = model->output_dim;
   if (!cols) n_cols = model->input_dim;
@@ -274,11 +263,9 @@ int tds_hip_jacobian_host(const tds_model_t *model, int n, const double *x, int 
     per_env.resize((size_t)n * n_rows * n_cols);
     dst = per_env.data();
   }
-  switch (cls) {
-    case 0: rc = tds_jac_host_impl<TdsBoundS>(model, n, x, n_rows, rows, n_cols, cols, y, dst); break;
-    case 1: rc = tds_jac_host_impl<TdsBoundA>(model, n, x, n_rows, rows, n_cols, cols, y, dst); break;
-    default: rc = tds_jac_host_impl<TdsBoundL>(model, n, x, n_rows, rows, n_cols, cols, y, dst); break;
-  }
+  rc = tds_with_bound(cls, [&](auto b) {
+    return tds_jac_host_impl<typename decltype(b)::type>(model, n, x, n_rows, rows, n_cols, cols, y, dst);
+  });
   if (rc || !jac || !accumulate) return rc;
   const size_t len = (size_t)n_rows * n_cols;
   for (size_t j = 0; j < len; ++j) {
@@ -291,12 +278,9 @@ int tds_hip_jacobian_host(const tds_model_t *model, int n, const double *x, int 
 
 int tds_hip_jacobian_tangents(const tds_model_t *model) {
   const char *why = "";
-  switch (tds_jvp_pick(model, &why)) {
-    case 0: return TdsJvpK<TdsBoundS>::K;
-    case 1: return TdsJvpK<TdsBoundA>::K;
-    case 2: return TdsJvpK<TdsBoundL>::K;
-    default: return fail(0, "%s", why);
-  }
+  const int cls = tds_jvp_pick(model, &why);
+  if (cls < 0) return fail(0, "%s", why);
+  return tds_with_bound(cls, [](auto b) { return TdsJvpK<typename decltype(b)::type>::K; });
 }
 
 }  // extern "C"

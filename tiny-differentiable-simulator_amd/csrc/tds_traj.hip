@@ -167,7 +167,7 @@ template <class B, int K>
 int tds_traj_run(tds_hip_sim *s, TdsTrajArgs ta, const tds_param_t *params_host) {
   ta.items = (long long)ta.a.n * (K > 0 ? (ta.a.kdirs + K - 1) / K : 1);
   const TdsTrajLayout lay = tds_traj_layout<B, K>(ta, ta.a.p);
-  int rc = tds_jvp_tmp(s, lay.total);
+  int rc = tds_work_buffer(s, lay.total);
   if (rc) return rc;
   char *ws = (char *)s->d_diff_tmp;
   ta.carry = (double *)(ws + lay.lanes_bytes);
@@ -252,16 +252,12 @@ int tds_hip_trajectory_jvp(tds_hip_sim_t *s, int n, int steps, int every, const 
   if (rc) return rc;
   DeviceGuard guard(s->device);
   int cls;
-  if ((rc = tds_jvp_prepare(s, &cls))) return rc;
+  if ((rc = tds_diff_prepare(s, &cls))) return rc;
   if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
   const TdsTrajArgs ta = tds_traj_args(&s->model, (const tds_model_t *)s->d_diff_model, n, steps, every,
                                        (const double *)x0_dev, (const double *)u_dev, p, (const double *)theta_dev, k,
                                        (const double *)v_dev, (double *)s_dev, (double *)js_dev);
-  switch (cls) {
-    case 0: return tds_traj_dispatch<TdsBoundS>(s, ta, params_host);
-    case 1: return tds_traj_dispatch<TdsBoundA>(s, ta, params_host);
-    default: return tds_traj_dispatch<TdsBoundL>(s, ta, params_host);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_traj_dispatch<typename decltype(b)::type>(s, ta, params_host); });
 }
 
 int tds_hip_trajectory_jvp_host(const tds_model_t *model, int n, int steps, int every, const double *x0,
@@ -274,11 +270,7 @@ int tds_hip_trajectory_jvp_host(const tds_model_t *model, int n, int steps, int 
   if ((rc = tds_param_host_prepare(model, p, params, &cls))) return rc;
   TdsTrajArgs ta = tds_traj_args(model, model, n, steps, every, x0, u, p, theta, k, v, s, js);
   ta.a.params = params;
-  switch (cls) {
-    case 0: return tds_traj_host_impl<TdsBoundS>(ta);
-    case 1: return tds_traj_host_impl<TdsBoundA>(ta);
-    default: return tds_traj_host_impl<TdsBoundL>(ta);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_traj_host_impl<typename decltype(b)::type>(ta); });
 }
 
 }  // extern "C"

@@ -85,7 +85,7 @@ template <class B>
 int tds_vjp_launch(tds_hip_sim *s, const TdsVjpArgs &a) {
   const long long n_lanes = tds_vjp_lanes(a.n);
   const TdsVjpLayout<TdsVjpLane<B>> lay(n_lanes, s->model.input_dim);
-  int rc = tds_jvp_tmp(s, lay.total);
+  int rc = tds_work_buffer(s, lay.total);
   if (rc) return rc;
   return tds_vjp_run(s, a, lay, n_lanes, TdsVjpRecordPlain{});
 }
@@ -106,30 +106,21 @@ extern "C" {
 int tds_hip_vjp(tds_hip_sim_t *s, int n, const void *x_dev, int k, const void *w_dev, void *y_dev, void *wj_dev) {
   if (!s || !x_dev || !w_dev || !wj_dev || n < 1 || k < 1) return fail(TDS_ERR_INVALID_ARG, "tds_hip_vjp: NULL or empty argument%s");
   DeviceGuard guard(s->device);
-  int cls, rc = tds_jvp_prepare(s, &cls);
+  int cls, rc = tds_diff_prepare(s, &cls);
   if (rc) return rc;
   TdsVjpArgs a = {(const tds_model_t *)s->d_diff_model, n, k, (const double *)x_dev, (const double *)w_dev,
                   (double *)y_dev, (double *)wj_dev, nullptr};
-  switch (cls) {
-    case 0: return tds_vjp_launch<TdsBoundS>(s, a);
-    case 1: return tds_vjp_launch<TdsBoundA>(s, a);
-    default: return tds_vjp_launch<TdsBoundL>(s, a);
-  }
+  return tds_with_bound(cls, [&](auto b) { return tds_vjp_launch<typename decltype(b)::type>(s, a); });
 }
 
 int tds_hip_vjp_host_tape(const tds_model_t *model, int n, const double *x, int k, const double *w, double *y,
                           double *wj, int tape_cap, int *tape_len) {
   if (!model || !x || !w || !wj || n < 1 || k < 1) return fail(TDS_ERR_INVALID_ARG, "tds_hip_vjp_host: NULL or empty argument%s");
-  const char *why = "";
-  const int cls = tds_jvp_pick(model, &why);
-  if (cls < 0) return fail(TDS_ERR_UNSUPPORTED, "%s", why);
-  const int rc = tds_hip_model_check(model);  // indices of the blob in range (the handle's model passed it at creation)
+  int cls, rc = tds_diff_host_check(model, &cls);
   if (rc) return rc;
-  switch (cls) {
-    case 0: return tds_vjp_host_impl<TdsBoundS>(model, n, x, k, w, y, wj, tape_cap, tape_len);
-    case 1: return tds_vjp_host_impl<TdsBoundA>(model, n, x, k, w, y, wj, tape_cap, tape_len);
-    default: return tds_vjp_host_impl<TdsBoundL>(model, n, x, k, w, y, wj, tape_cap, tape_len);
-  }
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_vjp_host_impl<typename decltype(b)::type>(model, n, x, k, w, y, wj, tape_cap, tape_len);
+  });
 }
 
 int tds_hip_vjp_host(const tds_model_t *model, int n, const double *x, int k, const double *w, double *y, double *wj) {

@@ -211,6 +211,13 @@ def ik_options(method="pinv", **options) -> IkOptions:
     return o
 
 
+_IK_DTYPES = {"iterations": "int32", "status": "int32"}  # of an inverse-kinematics call's outputs, the others float64
+
+
+def _ik_shapes(m, n):
+    return {"q": (n, m.dof_q), "iterations": (n,), "status": (n,), "residual": (n,)}
+
+
 def _ik_targets(links, body_points):
     """links [K] and body_points [K, 3] (None: the links' origins) as the C arrays of an inverse-kinematics call"""
     import numpy as np
@@ -495,6 +502,47 @@ def _host_rows(a, n, width):
     return a, a.ctypes.data
 
 
+def _host_outputs(shapes, want, out=None, struct=None, dtypes={}):
+    """The wanted outputs of a host query: C-contiguous arrays of `shapes` (float64 where `dtypes` names no other),
+    those `out` holds and new zeros for the rest; with them `struct` (a ctypes class, optional) filled with their
+    addresses"""
+    import numpy as np
+
+    res = {}
+    for k in want:
+        dt = np.dtype(dtypes.get(k, "float64"))
+        a = out[k] if out is not None and k in out else np.zeros(shapes[k], dtype=dt)
+        assert a.dtype == dt and a.flags.c_contiguous and a.shape == shapes[k], k
+        res[k] = a
+    return res, struct and struct(**{k: a.ctypes.data for k, a in res.items()})
+
+
+def _dev_records(a, width, what, n=None):
+    """a checked as a CUDA float64 tensor [N, width] (N = n where given), contiguous"""
+    import torch
+
+    assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.shape[1] == width, what
+    assert n is None or a.shape[0] == n, what
+    return a.contiguous()
+
+
+def _dev_outputs(shapes, want, out, device, struct=None, dtypes={}):
+    """The wanted outputs of a device query: contiguous CUDA tensors of `shapes` (float64 where `dtypes` names no
+    other), those `out` holds and new ones on `device` for the rest; with them `struct` (a ctypes class, optional)
+    filled with their addresses"""
+    import torch
+
+    res = {}
+    for k in want:
+        dt = getattr(torch, dtypes.get(k, "float64"))
+        t = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=dt, device=device)
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shapes[k], k
+        res[k] = t
+    # (an output without extent, n_c = 0, has no storage: it still counts as asked for)
+    nothing = None if all(t.numel() for t in res.values()) else torch.empty(1, dtype=torch.float64, device=device)
+    return res, struct and struct(**{k: (t if t.numel() else nothing).data_ptr() for k, t in res.items()})
+
+
 def dynamics_host(m: _model.Model, q, qd=None, tau=None, want=DYN_OUTPUTS):
     """The dynamics queries on the CPU (tds_hip_dynamics_host; the checker of HipSim.dynamics, needs no GPU).
 
@@ -507,8 +555,7 @@ def dynamics_host(m: _model.Model, q, qd=None, tau=None, want=DYN_OUTPUTS):
     n = q.shape[0]
     qd, qdp = _host_rows(qd, n, m.dof_qd)
     tau, taup = _host_rows(tau, n, dyn_tau_dim(m))
-    res = {k: np.zeros(dyn_shapes(m, n)[k], dtype=np.float64) for k in want}
-    out = DynOut(**{k: v.ctypes.data for k, v in res.items()})
+    res, out = _host_outputs(dyn_shapes(m, n), want, struct=DynOut)
     _check(lib().tds_hip_dynamics_host(C.byref(m), n, q.ctypes.data, qdp, taup, C.byref(out)))
     return res
 
@@ -551,13 +598,7 @@ def contacts_host(m: _model.Model, x, want=CONTACT_OUTPUTS, out=None):
     want = _contact_want(want)
     x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
     n = x.shape[0]
-    shapes = contact_shapes(m, n)
-    res = {}
-    for k in want:
-        a = out[k] if out is not None and k in out else np.zeros(shapes[k], dtype=np.float64)
-        assert a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shapes[k], k
-        res[k] = a
-    o = ContactOut(**{k: v.ctypes.data for k, v in res.items()})
+    res, o = _host_outputs(contact_shapes(m, n), want, out, struct=ContactOut)
     _check(lib().tds_hip_contacts_host(C.byref(m), n, x.ctypes.data, C.byref(o)))
     return res
 
@@ -580,8 +621,8 @@ def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points
     targets = np.ascontiguousarray(np.broadcast_to(targets, (n, k, 3)))
     qr, qrp = _host_rows(q_reference, n, m.dof_q)
     o = ik_options(method, **options)
-    res = {"q": np.zeros((n, m.dof_q)), "iterations": np.zeros(n, dtype=np.int32), "status": np.zeros(n, dtype=np.int32),
-           "residual": np.zeros(n)}
+    shapes = _ik_shapes(m, n)
+    res, _ = _host_outputs(shapes, shapes, dtypes=_IK_DTYPES)
     _check(lib().tds_hip_inverse_kinematics_host(C.byref(m), n, q_init.ctypes.data, k, lp, pp, targets.ctypes.data, qrp,
                                                  C.byref(o), res["q"].ctypes.data, res["iterations"].ctypes.data,
                                                  res["status"].ctypes.data, res["residual"].ctypes.data))
@@ -1257,12 +1298,9 @@ class HipSim:
 
     # -- dynamics queries: kinematics, mass matrix, bias, forward and inverse dynamics, point Jacobians -----------
     def _dyn_rows(self, a, n, width, what):
-        import torch
-
         if a is None or width == 0:
             return None, None
-        assert a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (n, width), what
-        a = a.contiguous()
+        a = _dev_records(a, width, what, n)
         return a, C.c_void_p(a.data_ptr())
 
     def dynamics(self, q, qd=None, tau=None, want=DYN_OUTPUTS, out=None):
@@ -1270,21 +1308,12 @@ class HipSim:
         qdd [N, dof_qd] at the states q [N, dof_q], qd [N, dof_qd] (None: zero), as a dict of tensors on the handle's
         device.  tau [N, dyn_tau_dim(model)] (None: zero) are the torques of qdd, the unconstrained forward dynamics.
         out: a dict of tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
-        import torch
-
         want = _dyn_want(want)
-        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
-        q = q.contiguous()
+        q = _dev_records(q, self.model.dof_q, "q")
         n = q.shape[0]
         qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
         tau, taup = self._dyn_rows(tau, n, dyn_tau_dim(self.model), "tau")
-        shapes = dyn_shapes(self.model, n)
-        res = {}
-        for k in want:
-            t = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float64, device=q.device)
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k]
-            res[k] = t
-        o = DynOut(**{k: t.data_ptr() for k, t in res.items()})
+        res, o = _dev_outputs(dyn_shapes(self.model, n), want, out, q.device, struct=DynOut)
         _check(lib().tds_hip_dynamics(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, C.byref(o)))
         return res
 
@@ -1304,8 +1333,7 @@ class HipSim:
         """tau [N, dof_qd] = ID(q, qd, qdd) (None: zero), without springs or dampers; fixed base only (async)"""
         import torch
 
-        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
-        q = q.contiguous()
+        q = _dev_records(q, self.model.dof_q, "q")
         n = q.shape[0]
         qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
         qdd, qddp = self._dyn_rows(qdd, n, self.model.dof_qd, "qdd")
@@ -1318,8 +1346,7 @@ class HipSim:
         are given in the link's own frame (async)"""
         import torch
 
-        assert q.is_cuda and q.dtype == torch.float64 and q.dim() == 2 and q.shape[1] == self.model.dof_q
-        q = q.contiguous()
+        q = _dev_records(q, self.model.dof_q, "q")
         n = q.shape[0]
         point, ptp = self._dyn_rows(point, n, 3, "point")
         jac = torch.empty((n, 3, self.model.dof_qd), dtype=torch.float64, device=q.device)
@@ -1332,21 +1359,10 @@ class HipSim:
         """What the step forward_zero(x) does about its plane contacts at the records x [N, input_dim]: the wanted
         CONTACT_OUTPUTS (shapes: contact_shapes(model, N)) as a dict of tensors on the handle's device.  out: a dict of
         tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
-        import torch
-
         want = _contact_want(want)
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        x = x.contiguous()
+        x = _dev_records(x, self.input_dim, "x")
         n = x.shape[0]
-        shapes = contact_shapes(self.model, n)
-        res = {}
-        for k in want:
-            t = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float64, device=x.device)
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k]
-            res[k] = t
-        # (an output without extent, n_c = 0, has no storage: it still counts as asked for)
-        nothing = torch.empty(1, dtype=torch.float64, device=x.device)
-        o = ContactOut(**{k: (t if t.numel() else nothing).data_ptr() for k, t in res.items()})
+        res, o = _dev_outputs(contact_shapes(self.model, n), want, out, x.device, struct=ContactOut)
         _check(lib().tds_hip_contacts(self.h, n, C.c_void_p(x.data_ptr()), C.byref(o)))
         return res
 
@@ -1366,24 +1382,17 @@ class HipSim:
         status or residual has those not computed.  Any N; f64 handles only (async)."""
         import torch
 
-        assert q_init.is_cuda and q_init.dtype == torch.float64 and q_init.dim() == 2 and q_init.shape[1] == self.model.dof_q
-        q_init = q_init.contiguous()
+        q_init = _dev_records(q_init, self.model.dof_q, "q_init")
         n = q_init.shape[0]
         k, links, pts, lp, pp = _ik_targets(links, body_points)
         assert targets.is_cuda and targets.dtype == torch.float64 and tuple(targets.shape) == (n, k, 3), "targets"
         targets = targets.contiguous()
         q_reference, qrp = self._dyn_rows(q_reference, n, self.model.dof_q, "q_reference")
         o = ik_options(method, **options)
-        shapes = {"q": ((n, self.model.dof_q), torch.float64), "iterations": ((n,), torch.int32),
-                  "status": ((n,), torch.int32), "residual": ((n,), torch.float64)}
-        res = {}
-        for name, (shape, dt) in shapes.items():
-            if out is not None and name not in out:
-                assert name != "q", "out must hold q"
-                continue
-            t = out[name] if out is not None else torch.empty(shape, dtype=dt, device=q_init.device)
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
+        assert out is None or "q" in out, "out must hold q"
+        shapes = _ik_shapes(self.model, n)
+        res, _ = _dev_outputs(shapes, [name for name in shapes if out is None or name in out], out,
+                              q_init.device, dtypes=_IK_DTYPES)
         ptr = {name: C.c_void_p(t.data_ptr()) for name, t in res.items()}
         _check(lib().tds_hip_inverse_kinematics(self.h, n, C.c_void_p(q_init.data_ptr()), k, lp, pp,
                                                 C.c_void_p(targets.data_ptr()), qrp, C.byref(o), ptr["q"],
