@@ -848,6 +848,15 @@ int tds_hip_single_step_kernel(const tds_hip_sim_t *sim, int *lanes_per_env, int
 int tds_hip_launch_plan_host(const tds_model_t *model, int dtype, int num_envs, int num_cus, int lds_per_cu, const int *req,
                              int n_req, int *out, int n_out);
 
+/* The window barriers of one step of the 8-lane kernel's two-wavefront builds, asked on the CPU (csrc/tds_oct_windows.h: the
+   rule both wavefronts' loops follow), for a wavefront whose environments have at most `max_contacts` contacts, under
+   `pgs_iterations` Gauss-Seidel iterations and option oct_long_window = `long_window_option`.  out[TDS_OCT_WINDOW_PLAN_INTS]:
+   barriers the main wavefront takes, barriers the helper takes (a workgroup hangs where they differ), 1 if the first
+   window of the first iteration runs on through the second window's rows.  Returns TDS_OCT_WINDOW_PLAN_INTS, or an error
+   code. */
+#define TDS_OCT_WINDOW_PLAN_INTS 3
+int tds_hip_oct_window_plan_host(int max_contacts, int pgs_iterations, int long_window_option, int *out, int n_out);
+
 /* ======================================================================================
  * Multi-GPU: the global batch of environments is cut into equal contiguous shards, one per rank /
  * GPU (rank r owns environments [r N/G, (r+1) N/G)); each shard is an ordinary tds_hip_sim on its own device, the

@@ -17,6 +17,7 @@
 
 #include "tds_api_internal.h"
 #include "tds_launch_plan.h"
+#include "tds_oct_windows.h"
 
 namespace tds_internal {
 thread_local char g_err[512] = "";
@@ -263,6 +264,7 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
   if (opts && !opts->rings && opts->y_stride > 0) ctl.y_stride = opts->y_stride;
   else if (!y_stride_set) ctl.y_stride = s->model.output_dim;  // (the kernels read the stride as it is: never 0)
   ctl.flags |= ctl_flags;
+  if (s->opt.get(TDS_OPT_OCT_LONG_WINDOW, 1) != 0) ctl.flags |= TDS_CTL_OCT_LONG_WINDOW;
   ctl.nsub = nsub;
   ctl.reset_mode = reset_mode;
   ctl.settle_steps = s->model.settle_steps < 0 ? 0 : s->model.settle_steps;
@@ -2087,6 +2089,7 @@ int tds_hip_profile_phases(tds_hip_sim_t *s, long long *cycles_host, int n) {
   memset(&ctl, 0, sizeof(ctl));
   ctl.nsub = 1;
   ctl.y_stride = s->model.output_dim;
+  if (s->opt.get(TDS_OPT_OCT_LONG_WINDOW, 1) != 0) ctl.flags |= TDS_CTL_OCT_LONG_WINDOW;
   if (s->opt.is_set(TDS_OPT_GRAM_STAMP_AT)) ctl.flags |= (int)s->opt.v[TDS_OPT_GRAM_STAMP_AT] << 8;  // (stamp 10 inside tds_gram_solve)
   // (profiling builds of the kernels, -DTDS_PROF_LOOP: the stamps of iteration K / 2 of a K-step launch of the two-wavefront
   //  step-loop kernel — TDS_HIP_PROF_LOOP=K; the library's own kernels have no such build and ignore the request)
@@ -2237,6 +2240,15 @@ int tds_hip_launch_plan_host(const tds_model_t *model, int dtype, int num_envs, 
   }
   delete s;
   return rc;
+}
+
+int tds_hip_oct_window_plan_host(int max_contacts, int pgs_iterations, int long_window_option, int *out, int n_out) {
+  if (!out || n_out < TDS_OCT_WINDOW_PLAN_INTS || max_contacts < 0 || pgs_iterations < 0)
+    return fail(TDS_ERR_INVALID_ARG, "window plan: bad arguments");
+  out[0] = tds_oct_main_barriers(max_contacts, pgs_iterations, long_window_option);
+  out[1] = tds_oct_help_barriers(max_contacts, pgs_iterations);
+  out[2] = tds_oct_long_window(max_contacts, pgs_iterations, long_window_option) ? 1 : 0;
+  return TDS_OCT_WINDOW_PLAN_INTS;
 }
 
 }  // extern "C"

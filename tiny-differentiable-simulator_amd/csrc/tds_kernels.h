@@ -45,6 +45,9 @@ struct TdsLds {
 #define TDS_RESET_AUTO 1    // re-initialise + settle the environments whose last step ends with done
 #define TDS_RESET_FORCED 2  // re-initialise + settle the environments selected by mask (NULL = all)
 #define TDS_CTL_RESET_CALL 8
+// 8-lane kernel (tds_oct.hip), two-wavefront builds: the first row window of a step runs on through a short second one
+// (option oct_long_window, default on; tds_oct_windows.h)
+#define TDS_CTL_OCT_LONG_WINDOW 4
 struct TdsStepCtl {
   int nsub;                   // normal steps in this launch (0 for a pure reset launch)
   int reset_mode;             // TDS_RESET_*
@@ -69,6 +72,7 @@ struct TdsStepCtl {
   int flags;                  // bit 0: the first step observes the raw base x, y (state fresh from reset())
                               // TDS_CTL_RESET_CALL: the launch is tds_hip_reset (the environment's own reset():
                               // its observation keeps the base x, y where the model says so), not an auto-reset
+                              // TDS_CTL_OCT_LONG_WINDOW: see there
   // step-loop launches only: per-step RECORD RINGS (tds_hip_step_many_rings).  With a ring set, EVERY step of the launch
   // does the whole output work of step_forward_original + VectorizedEnvironment::step — visual poses, y record,
   // reward / done, observation (locomotion_contact_simulation.h:273-303, ars_vectorized_environment.h:240-289) — and

@@ -42,6 +42,7 @@
 #include "tds_device_model.h"
 #include "tds_kernels.h"
 #include "tds_lanes.h"
+#include "tds_oct_windows.h"
 #include "tds_step_shared.h"
 
 // Phase stamps (a build of its own: -DTDS_OCT_PROF, tools/oct_profile.sh): workgroup TDS_OCT_PROF_WG writes the shader clock
@@ -1252,8 +1253,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //      processed (two register sets, taken in turn by the row's parity: no copies); a friction row asks for its normal
   //      row's impulse at its own top, behind the store of the row before (NA = 1: that row IS its normal row).  The model's
   //      constants of the sweep (sw_mu, sw_rest) are read once per step (main_sweep_consts).
-  auto main_sweep = [&](auto firstc, int w0, int bo) {
+  //      The LONG first window (tds_oct_windows.h; two-wavefront builds, first iteration, 8 < 3 NA <= 12: `lw`, wave-uniform):
+  //      the chain runs on from position 7 through positions 8 .. 3 NA - 1 — rows of the second buffer, which lies behind
+  //      the first: the same immediate offsets off the same bases — instead of returning to the window loop for a window of
+  //      one to four rows.  They are second-tangent rows (8 >= 2 NA): the friction arm with xs2 only.  The second window's
+  //      barrier is taken in position 7, in front of the request for position 8's operands.
+  auto main_sweep = [&](auto firstc, int w0, int bo, bool lw) {
       constexpr bool FIRST = decltype(firstc)::value;
+      constexpr int KMAX = (FIRST && W2) ? 12 : 8;
       OCT_MARK("sweep");
       const T *const Zs = E + O.win + bo;
       T *const xw = E + O.xs + w0;  // the window's impulses
@@ -1315,8 +1322,26 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             process(kc, cur, std::true_type{});
           } else {
             cur.sd = (k >= k_t2 ? xs2 : xs1)[k];
+            if constexpr (k == 7 && KMAX > 8) {
+              // (the second window's barrier, in the friction arm: a long window's position 7 is a friction row — 3 NA <= 12,
+              //  so k_n = NA <= 4.  Behind the request for the normal row's impulse the barrier's wait for the LDS is the one
+              //  this row sits out anyway; it completes the position's own operand reads — the last reads of the first buffer —
+              //  in front of the barrier, and position 8's operands then arrive under the whole of this row's arithmetic)
+              if (lw) {
+                OCT_BAR_W(30, false);
+                request(std::integral_constant<int, 8>{}, ops[0]);
+              }
+            }
             process(kc, cur, std::false_type{});
           }
+          self(self, std::integral_constant<int, k + 1>{});
+        } else if constexpr (k < KMAX) {
+          // positions 8 .. 11 of a long first window (position 8 exists whenever the window is long)
+          if (k == 8 ? !lw : k >= wn) return;
+          Ops &cur = ops[k & 1];
+          if constexpr (k + 1 < KMAX) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
+          cur.sd = xs2[k];
+          process(kc, cur, std::false_type{});
           self(self, std::integral_constant<int, k + 1>{});
         }
       };
@@ -1622,16 +1647,22 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // (the first window's root stage stays with the helper although the main wavefront holds the factors in registers: doing
       //  it here measured 1.6 k cycles on the chain against 1.1 k of waiting for the helper's)
       // (the window loops of the two wavefronts must agree — a barrier each: pgs_iters is the table's, NA the helper's)
+      // (tds_oct_windows.h: the rule both loops follow, case by case)
       const int nr = 3 * NA;
+      // (pgs_iters > 0 inside its loop, where alone lw is read: the condition stays on the scalar unit — NA and the launch's flags)
+      const bool lw = tds_oct_long_window(NA, 1, ctl.flags & TDS_CTL_OCT_LONG_WINDOW);
       int bo = 0;
       for (int pit = 0; pit < pgs_iters; ++pit) {
-        for (int w0 = 0; w0 < nr; w0 += 8) {
+        for (int w0 = 0; w0 < nr;) {
+          const int nw = tds_oct_main_windows(lw, pit, w0);
           OCT_BAR_W(30, (pit | w0) == 0);
           if ((pit | w0) == 0) OCT_STAMP(12, tid);
-          if (pit == 0) main_sweep(std::true_type{}, w0, bo);
-          else main_sweep(std::false_type{}, w0, bo);
+          if (pit == 0) main_sweep(std::true_type{}, w0, bo, nw == 2);
+          else main_sweep(std::false_type{}, w0, bo, false);
           if ((pit | w0) == 0) OCT_STAMP(13, u);
-          bo = 8 * OctLds::ZW - bo;
+          // (a long window took two windows' rows and barriers: the buffers' turn comes out where it was)
+          w0 += 8 * nw;
+          if (nw == 1) bo = 8 * OctLds::ZW - bo;
         }
       }
       main_fin();
@@ -1653,14 +1684,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // (the same windows as the main wavefront's two loops, the first one — the stretch the main wavefront waits for: nothing
       //  but the factors' reads, the root stage and the barrier — taken out in front: there is one exactly when NA > 0 and
       //  pgs_iters > 0, as in the main wavefront's loops)
-      if (NA > 0 && pgs_iters > 0) {
+      if (tds_oct_help_has_windows(NA, pgs_iters)) {
         help_get_factors();
         rows_root(0, rw);
         OCT_BAR_W(46, true);
         const int nr = 3 * NA;
         int bo = 8 * OctLds::ZW;
         for (int pit = 0; pit < pgs_iters; ++pit) {
-          for (int w0 = pit == 0 ? 8 : 0; w0 < nr; w0 += 8) {
+          for (int w0 = tds_oct_help_first_w0(pit); w0 < nr; w0 += 8) {
             rows_geom(w0, bo, rw);
             rows_leg(bo, rw);
             rows_root(bo, rw);
@@ -1691,8 +1722,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         rows_leg(bo, rw);
         rows_root(bo, rw);
         OCT_SYNC();
-        if (pit == 0) main_sweep(std::true_type{}, w0, bo);
-        else main_sweep(std::false_type{}, w0, bo);
+        if (pit == 0) main_sweep(std::true_type{}, w0, bo, false);
+        else main_sweep(std::false_type{}, w0, bo, false);
         bo = 8 * OctLds::ZW - bo;
       }
     }

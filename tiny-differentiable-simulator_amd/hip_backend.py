@@ -106,6 +106,7 @@ def lib():
         L.tds_hip_shard_gathered_offset.argtypes = [C.c_int, C.c_int, C.c_int]
         L.tds_hip_launch_plan_host.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                                C.POINTER(C.c_int), C.c_int]
+        L.tds_hip_oct_window_plan_host.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.tds_hip_shard_gathered_offset.restype = C.c_longlong
         L.tds_hip_default_option.argtypes = [C.c_char_p, C.c_longlong]
         L.tds_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
@@ -358,7 +359,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_shard_local_envs", "tds_hip_shard_first_env", "tds_hip_shard_wire_bytes", "tds_hip_shard_set_block",
     "tds_hip_shard_step", "tds_hip_shard_step_many", "tds_hip_shard_step_many_prepare", "tds_hip_shard_group_step", "tds_hip_shard_flush", "tds_hip_shard_gathered", "tds_hip_shard_gathered_step",
     "tds_hip_shard_ring_plan", "tds_hip_shard_gathered_offset", "tds_hip_shard_exchange_form", "tds_hip_shard_peer_count",
-    "tds_hip_single_step_kernel", "tds_hip_launch_plan_host",
+    "tds_hip_single_step_kernel", "tds_hip_launch_plan_host", "tds_hip_oct_window_plan_host",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
@@ -418,6 +419,17 @@ def launch_plan_host(m: _model.Model, dtype: str = "f64", num_envs: int = 1, num
     for k in ("refused", "loop", "exchange_after"):
         plan[k] = bool(plan[k])
     return plan
+
+
+def oct_window_plan_host(max_contacts: int, pgs_iterations: int, long_window: int = 1):
+    """the window barriers of one step of the 8-lane kernel's two-wavefront builds (tds_hip_oct_window_plan_host; no device
+    needed): dict main_barriers / help_barriers / long_window for a wavefront with at most `max_contacts` contacts per
+    environment"""
+    out = (C.c_int * 3)()
+    rc = lib().tds_hip_oct_window_plan_host(int(max_contacts), int(pgs_iterations), int(long_window), out, 3)
+    if rc != 3:
+        _check(rc)
+    return dict(main_barriers=out[0], help_barriers=out[1], long_window=bool(out[2]))
 
 
 def default_option(key: str, value) -> None:
