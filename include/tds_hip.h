@@ -651,6 +651,43 @@ int tds_hip_trajectory_jvp_host(const tds_model_t *model, int n, int steps, int 
                                 const double *u, int p, const tds_param_t *params, const double *theta, int k,
                                 const double *v, double *s, double *js);
 
+/* Reverse-mode derivatives of the same trajectories: one cotangent gs [n][n_rec][dof_q + dof_qd] on the recorded states
+   of tds_hip_trajectory_jvp's trajectory (step 0's record, step t's record, u, theta, every and n_rec, scope, refusals
+   and the f64-only rule as there), and its gradients
+     gx0 [n][input_dim] = sum_r gs_r^T d s_r / d x0, the linear map of js' x0 columns: x0's action slots feed step 0
+                          only where u is given and every step where u is NULL, the LOCOMOTION gains every step;
+     gu [n][steps - 1][n_act], in the actions of steps 1 .. steps - 1: required where u is given and n_act > 0,
+                          ignored where u is NULL;
+     gtheta [n][p], where p > 0;
+   s [n][n_rec][dof_q + dof_qd] (optional, may be NULL) is bit for bit the k = 0 result of tds_hip_trajectory_jvp.  A
+   slot that several steps feed is accumulated with t descending, on host and device alike.  Derivative conventions as
+   above (the primal's branch, quaternions raw).  Per environment: a joint-space inertia that is not positive definite at
+   some step gives NaN in s from that record on and NaN in all of the environment's gradients; a tape past the class's
+   bound of parameter mode (tds_hip_vjp_params) gives NaN in all of its gradients and the call returns
+   TDS_ERR_UNSUPPORTED.  Argument errors as tds_hip_trajectory_jvp.
+   Device pointers (params_host: host array).  A primal pass stores the state after every step (n steps (dof_q + dof_qd)
+   doubles of the work buffer); then, per chunk of environments and window of W consecutive steps, last window first,
+   one launch records the W steps' tapes side by side and one launch sweeps them back in turn.  Option traj_vjp_lanes
+   (a multiple of 64 in [64, 16384]; unset: 4096) is the lanes of a recording launch: chunk = min(ceil(n / 64) 64,
+   traj_vjp_lanes) environments, W = max(1, min(traj_vjp_lanes / chunk, traj_steps, steps)); the results do not depend
+   on either.  Enqueued back to back on the handle's stream (the host waits where the work buffer grows and the
+   selection is copied); the call then waits for its kernels (it reads back the overflow flag).  Work buffer (shared
+   with the step derivatives): the state store, and per lane of a recording launch the parameter-mode lane's work
+   object plus 24 B per tape entry of the bound, plus 8 B per entry and environment of a chunk (11.5 GB for the Ant at
+   the unset 4096 lanes, 46 GB at 16384). */
+int tds_hip_trajectory_vjp(tds_hip_sim_t *sim, int n, int steps, int every, const void *x0_dev, const void *u_dev,
+                           int p, const tds_param_t *params_host, const void *theta_dev, const void *gs_dev,
+                           void *s_dev, void *gx0_dev, void *gu_dev, void *gtheta_dev);
+/* The same on the CPU (host arrays, needs no GPU; one tape at a time): the checker of tds_hip_trajectory_vjp.  tape_cap
+   (<= 0: the class's bound) and tape_len [n][steps] (optional: the entries each step recorded, -1 where it overflowed,
+   0 for an environment whose inertia was not positive definite) as for tds_hip_vjp_host_tape.  Returns
+   TDS_ERR_UNSUPPORTED where a tape overflowed, else TDS_ERR_INVALID_ARG where some environment's inertia was not
+   positive definite, after writing every output. */
+int tds_hip_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int every, const double *x0,
+                                const double *u, int p, const tds_param_t *params, const double *theta,
+                                const double *gs, double *s, double *gx0, double *gu, double *gtheta,
+                                int tape_cap, int *tape_len /* [n][steps], optional */);
+
 /* Batched dynamics queries (the reference's forward_kinematics, mass_matrix, forward_dynamics, point_jacobian of
    python/pytinydiffsim.inl:629-668 and inverse_dynamics of src/dynamics/inverse_dynamics.hpp, for n states at once).
    State q [n][dof_q], qd [n][dof_qd] (NULL: zero), f64 device pointers.  Scope and refusals are those of

@@ -22,6 +22,7 @@ _StepFunctionReverse = None
 _ParamStepFunction = None
 _RbRolloutFunction = None
 _TrajectoryFunction = None
+_TrajectoryReverseFunction = None
 
 
 def _function():
@@ -278,7 +279,45 @@ def _trajectory_function():
     return _TrajectoryFunction
 
 
-def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1):
+def _trajectory_reverse_function():
+    global _TrajectoryReverseFunction
+    if _TrajectoryReverseFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class TrajectoryReverseFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, z, theta, u, x0, sim, steps, every, idx, params):
+                x = x0.detach().clone()
+                if z is not None:
+                    x[:, idx] = z.detach().to(x.dtype)
+                th = None if theta is None else theta.detach()
+                ud = None if u is None else u.detach()
+                ctx.shared = th is not None and th.dim() == 1
+                ctx.has = (z is not None, th is not None, ud is not None)
+                ctx.sim, ctx.steps, ctx.every, ctx.idx, ctx.params = sim, steps, every, idx, params
+                ctx.save_for_backward(*(t for t in (x, th, ud) if t is not None))
+                return sim.trajectory_jvp(x, None, steps, every, ud, params, th)[0]
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_s):
+                saved = list(ctx.saved_tensors)
+                x = saved.pop(0)
+                th = saved.pop(0) if ctx.has[1] else None
+                ud = saved.pop(0) if ctx.has[2] else None
+                _, gx0, gu, gth = ctx.sim.trajectory_vjp(x, grad_s.to(x.dtype).contiguous(), ctx.steps, ctx.every, ud,
+                                                         ctx.params, th)
+                if ctx.shared:  # one theta for every environment: its gradient sums over them
+                    gth = gth.sum(0)
+                return ((gx0[:, ctx.idx] if ctx.has[0] else None), (gth if ctx.has[1] else None),
+                        (gu if ctx.has[2] else None)) + (None,) * 6
+
+        _TrajectoryReverseFunction = TrajectoryReverseFunction
+    return _TrajectoryReverseFunction
+
+
+def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1, mode: str = "forward"):
     """(x0, z=None, theta=None, u=None) -> s [N, n_rec, nq + nd]: the states after steps every, 2 every, .., steps of
     forward_zero chained from x0 [N, input_dim] (a HipSim, f64), with x0's entries wrt (indices into its input_dim
     entries) overwritten by z [N, len(wrt)], differentiable in z and theta.
@@ -287,9 +326,15 @@ def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1):
     (its gradient is summed over them) or [N, p].  u: None (x0's actions every step) or [N, steps - 1, n_act], the
     actions of steps 1 .. (HipSim.trajectory_jvp).  Where z or theta requires grad, the forward pass computes the
     len(wrt) + p needed columns of d s / d [z | theta] in forward mode and backward is J^T grad.  x0 and u are not
-    differentiated: x0.requires_grad and u.requires_grad raise."""
+    differentiated: x0.requires_grad and u.requires_grad raise.
+
+    mode "reverse": the forward pass is the primal alone and backward is one HipSim.trajectory_vjp, differentiable in
+    z, theta and the actions u (trajectory optimisation, policy gradients through the rollout); x0.requires_grad still
+    raises."""
     from . import hip_backend
 
+    if mode not in ("forward", "reverse"):
+        raise ValueError(f"trajectory_fn: mode must be 'forward' or 'reverse', not {mode!r}")
     p = len(params)
     sel = hip_backend.param_spec(params)
     spec = [sel[j] for j in range(p)]
@@ -303,7 +348,7 @@ def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1):
         if x0.requires_grad:
             raise ValueError("trajectory_fn: x0 is not differentiated: list the entries to differentiate in wrt and "
                              "pass them as z")
-        if u is not None and u.requires_grad:
+        if mode == "forward" and u is not None and u.requires_grad:
             raise ValueError("trajectory_fn: the actions u are not differentiated: for gradients in an action sequence "
                              "chain step_fn(sim, mode='reverse')")
         if z is None and idx:
@@ -312,10 +357,12 @@ def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1):
             raise ValueError(f"trajectory_fn: z must be [N, {len(idx)}], got {tuple(z.shape)}")
         if theta is not None and p == 0:
             raise ValueError("trajectory_fn: theta given but no params selected")
+        ix = torch.tensor(idx, dtype=torch.long, device=x0.device)
+        if mode == "reverse":
+            return _trajectory_reverse_function().apply(z, theta, u, x0, sim, int(steps), int(every), ix, spec)
         key = str(x0.device)
         if key not in cache:
             cache[key] = hip_backend.trajectory_directions(sim.input_dim, idx, p, device=x0.device)
-        ix = torch.tensor(idx, dtype=torch.long, device=x0.device)
         return fn.apply(z, theta, x0, u, sim, int(steps), int(every), ix, cache[key], spec)
 
     return f

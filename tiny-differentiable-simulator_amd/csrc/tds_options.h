@@ -67,6 +67,7 @@ enum TdsOptKey {
   TDS_OPT_SHARD_PEER_LOOPBACK,  // diagnostic: k extra "peers" mapped onto scratch rings of this rank's own GPU (the kernel-side cost of k peers, measurable on one GPU)
   // ---- step derivatives
   TDS_OPT_TRAJ_STEPS,         // articulated trajectory derivatives (tds_traj.hip): steps per launch (unset: 16; bounds a launch's duration whatever the horizon)
+  TDS_OPT_TRAJ_VJP_LANES,     // trajectory VJP (tds_traj_vjp.hip): lanes of one recording launch, a multiple of 64 in [64, 16384] (unset: 4096, the work-buffer bound of tds_hip_vjp)
   TDS_OPT_COUNT
 };
 
@@ -132,6 +133,7 @@ inline const TdsOptRow *tds_opt_rows() {
       {"shard_peer_copy", false, "TDS_HIP_SHARD_PEER_COPY"},
       {"shard_peer_loopback", false, "TDS_HIP_SHARD_PEER_LOOPBACK"},
       {"traj_steps", false, "TDS_HIP_TRAJ_STEPS"},
+      {"traj_vjp_lanes", false, "TDS_HIP_TRAJ_VJP_LANES"},
   };
   return rows;
 }

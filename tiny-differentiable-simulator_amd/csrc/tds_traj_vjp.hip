@@ -1,0 +1,471 @@
+// tds_traj_vjp.hip — reverse-mode derivatives of articulated-body trajectories on gfx950: the trajectory of
+// tds_traj.hip (forward_zero chained over `steps` steps, states recorded every `every` steps), one cotangent gs on the
+// recorded states, and its gradients in x0, in the actions u of steps 1 .. and in theta.  C ABI
+// tds_hip_trajectory_vjp / tds_hip_trajectory_vjp_host (include/tds_hip.h).
+//
+// Phase 1, the primal: the double item of tds_traj.hip (tds_traj_advance<B, 0>, every = 1) writes the state after every
+// step into a state store [n][steps][nsd] in the work buffer; s is copied out of it.
+// Phase 2, backward, per chunk of environments and per window of W consecutive steps, last window first:
+//   recording   one wavefront per (step t of the window, block of 64 environments): the lane builds step t's record
+//               from the state store (tds_traj_vjp_record) and records it over TdsRev through the parameter-mode lane
+//               of tds_dparam.hip; tape layout [wavefront][position][lane], as tds_vjp_kernels.h's.  The record of
+//               step t depends on the primal alone, so the W tapes of a window are recorded side by side;
+//   chained     one wavefront per block of 64 environments walks t from the window's last step down to its first:
+//   sweep       zero the ring and the input parts, seed lambda (+ gs at a recorded step), tds_vjp_sweep on tape
+//               (t, block), scatter the input adjoints (tds_traj_vjp_seed / _scatter, the host checker's too).  lambda
+//               [nsd][n] lives in the work buffer and so crosses window boundaries.  A sweep leaves every far part it
+//               read at zero (tds_vjp_block) and the input parts are zeroed before each sweep, so the one adjoint
+//               region of a sweeping wavefront serves all W tapes.
+// An environment belongs to one lane: the accumulations into gx0 and gtheta are plain read-modify-writes, t descending.
+// Only copies and lambda cross window and chunk boundaries: the results do not depend on W or the chunk size.
+// A last pass writes NaN gradients for the environments whose primal was NaN or whose tape overflowed.
+//
+// The unit is built without FP contraction (Makefile), as tds_traj.hip: device and host round alike.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "tds_traj.h"
+#include "tds_vjp_param.h"
+
+namespace {
+
+// lanes of one recording launch where TDS_OPT_TRAJ_VJP_LANES is unset: the work-buffer bound of tds_hip_vjp
+constexpr long long kTrajVjpLanesDefault = kVjpLanes, kTrajVjpLanesMax = 16384;
+
+struct TdsTrajVjpArgs {
+  const tds_model_t *m;
+  int n, p, steps, every, n_rec, nsd, nact;
+  const double *x0, *u, *theta, *gs;  // [n][input_dim], [n][steps - 1][nact] or NULL, [n][p] or NULL, [n][n_rec][nsd]
+  const tds_param_t *params;
+  const double *store;                // the state after step t at [n][steps][nsd]
+  double *gx0, *gu, *gtheta;          // [n][input_dim], [n][steps - 1][nact], [n][p]
+  int *overflow;                      // set where a lane's tape overflows
+};
+
+// c into an adjoint's far part / its value (device: as tds_vjp_sweep_kernel seeds and reads them)
+TDS_HD inline void tds_traj_vjp_add(double *p, double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsafeAtomicAdd(p, c);
+#else
+  *p += c;
+#endif
+}
+TDS_HD inline double tds_traj_vjp_load(const double *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return *p;
+#endif
+}
+
+// step t's record of environment env as the primal read it, in TdsRev form: x variables 0 .. input_dim - 1, theta
+// input_dim .. input_dim + p - 1 (theta NULL: the blob's values, still active).  0, or the step's -1
+template <class B>
+TDS_HD inline int tds_traj_vjp_record(const TdsTrajVjpArgs &a, TdsVjpParamLane<B> &L, int env, int t) {
+  const tds_model_t *m = a.m;
+  const int nin = m->input_dim, nsd = a.nsd;
+  const double *xe = a.x0 + (size_t)env * nin;
+  const double *st = t > 0 ? a.store + ((size_t)env * a.steps + (t - 1)) * nsd : xe;
+  const double *ut = t > 0 && a.u ? a.u + ((size_t)env * (a.steps - 1) + (t - 1)) * a.nact : xe + nsd;
+  for (int i = 0; i < nin; ++i) L.x[i] = TdsRev(i < nsd ? st[i] : i < nsd + a.nact ? ut[i - nsd] : xe[i], i);
+  tds_param_seed(m, L.P);
+  for (int j = 0; j < a.p; ++j) {
+    const double th = a.theta ? a.theta[(size_t)env * a.p + j] : tds_param_slot(L.P, a.params[j], 0)->v;
+    tds_param_set(L.P, a.params[j], TdsRev(th, nin + j));
+  }
+  tds_rev_cursor(tds_rev_lane()) = 0;
+  return tds_diff_step_view(m, TdsOverlayView<TdsRev, B>{&L.P}, L.w, L.x, L.y);
+}
+
+// seeds of step t's sweep: adj[y_i] += lambda_i (+ gs_i where step t is recorded), i < nsd.  yi: the variable indices
+// of y's first nsd entries, lam: lambda, adj: the lane's adjoints; entry i at [i * stride]
+TDS_HD inline void tds_traj_vjp_seed(const TdsTrajVjpArgs &a, int env, int t, const int *yi, long long ys,
+                                     const double *lam, long long ls, double *adj, long long as) {
+  const bool rec = (t + 1) % a.every == 0;
+  const double *g = a.gs + ((size_t)env * a.n_rec + (rec ? (t + 1) / a.every - 1 : 0)) * a.nsd;
+  for (int i = 0; i < a.nsd; ++i) {
+    const int v = yi[i * ys];
+    if (v < 0) continue;  // a constant
+    double c = lam[i * ls];
+    if (rec) c += g[i];
+    tds_traj_vjp_add(adj + v * as, c);
+  }
+}
+
+// the input adjoints of step t's sweep: the state part is the next lambda (t = 0: gx0's state part); the action part is
+// gu[t - 1] (t = 0, or u NULL: added to gx0's action slots); gains and theta are added to gx0 and gtheta
+TDS_HD inline void tds_traj_vjp_scatter(const TdsTrajVjpArgs &a, int env, int t, const double *adj, long long as,
+                                        double *lam, long long ls) {
+  const int nin = a.m->input_dim, nsd = a.nsd, nact = a.nact;
+  double *gx = a.gx0 + (size_t)env * nin;
+  for (int i = 0; i < nsd; ++i) {
+    const double g = tds_traj_vjp_load(adj + i * as);
+    if (t > 0) lam[i * ls] = g;
+    else gx[i] = g;
+  }
+  if (t > 0 && a.u) {
+    double *gut = a.gu + ((size_t)env * (a.steps - 1) + (t - 1)) * nact;
+    for (int i = 0; i < nact; ++i) gut[i] = tds_traj_vjp_load(adj + (nsd + i) * as);
+  } else {
+    for (int i = nsd; i < nsd + nact; ++i) gx[i] += tds_traj_vjp_load(adj + i * as);
+  }
+  for (int i = nsd + nact; i < nin; ++i) gx[i] += tds_traj_vjp_load(adj + i * as);
+  double *gt = a.gtheta + (size_t)env * a.p;
+  for (int j = 0; j < a.p; ++j) gt[j] += tds_traj_vjp_load(adj + (nin + j) * as);
+}
+
+// NaN into every gradient of environment env
+TDS_HD inline void tds_traj_vjp_nan(const TdsTrajVjpArgs &a, int env) {
+  const double nan = __builtin_nan("");
+  const int nin = a.m->input_dim;
+  for (int i = 0; i < nin; ++i) a.gx0[(size_t)env * nin + i] = nan;
+  if (a.u)
+    for (long long i = 0; i < (long long)(a.steps - 1) * a.nact; ++i)
+      a.gu[(size_t)env * (a.steps - 1) * a.nact + i] = nan;
+  for (int j = 0; j < a.p; ++j) a.gtheta[(size_t)env * a.p + j] = nan;
+}
+
+// ---------------------------------------------------------------- phase 1
+// steps t0 .. t1 of every environment into the state store (ta.s, every = 1); bad[env] once the last step is done
+template <class B>
+__global__ void __launch_bounds__(64) tds_traj_vjp_primal_kernel(TdsTrajArgs ta, TdsTrajLane<B, 0> *lanes,
+                                                                 long long n_lanes, int t0, int t1, int *bad) {
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n_lanes) return;
+  for (long long it = lane; it < ta.items; it += n_lanes) {
+    const int b = tds_traj_advance<B, 0>(ta, lanes[lane], it, t0, t1);
+    if (t1 == ta.steps) bad[it] = b;
+  }
+}
+
+// s [n][n_rec][nsd] out of the store [n][steps][nsd]: one lane per (environment, record)
+__global__ void __launch_bounds__(256) tds_traj_vjp_select_kernel(const double *store, double *s, long long n_items,
+                                                                  int steps, int every, int n_rec, int nsd) {
+  const long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (it >= n_items) return;
+  const long long env = it / n_rec, r = it % n_rec;
+  const double *src = store + (env * steps + (r + 1) * every - 1) * nsd;
+  double *dst = s + it * nsd;
+  for (int i = 0; i < nsd; ++i) dst[i] = src[i];
+}
+
+// ---------------------------------------------------------------- phase 2
+// recording: wavefront blockIdx.x = (step t0 + blockIdx.x / nblk, environments e0 + 64 (blockIdx.x % nblk) ..); the
+// lane's tape, lens[lane] = its length (-1: not recorded, or overflowed) and yidx [wavefront][nsd][lane] = the variables
+// of y's first nsd entries
+template <class B>
+__global__ void __launch_bounds__(64) tds_traj_vjp_record_kernel(TdsTrajVjpArgs a, int e0, int nblk, int t0,
+                                                                 const int *bad, int *over, TdsVjpParamLane<B> *lanes,
+                                                                 int *lens, int *yidx, TdsRevIdx *ix, TdsRevPart *pd) {
+  constexpr int cap = TdsVjpParamLane<B>::cap;
+  const int l = threadIdx.x;
+  const long long wave = blockIdx.x, lane = wave * 64 + l;
+  const int t = t0 + (int)(wave / nblk);
+  const long long env = e0 + (wave % nblk) * 64 + l;
+  if (l == 0)
+    tds_rev_tape() = TdsRevTape{ix + wave * cap * 64, pd + wave * cap * 64, nullptr, 64, cap, a.m->input_dim + a.p};
+  __syncthreads();
+  if (env >= a.n) return;
+  if (bad[env]) {
+    lens[lane] = -1;
+    return;
+  }
+  TdsVjpParamLane<B> &L = lanes[lane];
+  tds_traj_vjp_record<B>(a, L, (int)env, t);  // the primal was positive definite at every step
+  const int len = tds_rev_cursor(l);
+  if (len > cap) *a.overflow = 1, over[env] = 1;
+  lens[lane] = len > cap ? -1 : len;
+  for (int i = 0; i < a.nsd; ++i) yidx[(wave * a.nsd + i) * 64 + l] = L.y[i].i;
+}
+
+// the chained sweep of steps t1 - 1 .. t0 for environments e0 + 64 blockIdx.x ..: tds_vjp_sweep_kernel's sweep per
+// step, lambda [nsd][n] between them
+template <class B>
+__global__ void __launch_bounds__(64) tds_traj_vjp_sweep_kernel(TdsTrajVjpArgs a, int e0, int nblk, int t0, int t1,
+                                                                const int *bad, const int *lens, const int *yidx,
+                                                                TdsRevIdx *ix, TdsRevPart *pd, double *adj,
+                                                                double *lam) {
+  constexpr int cap = TdsVjpParamLane<B>::cap;
+  const int l = threadIdx.x, nin = a.m->input_dim + a.p;
+  const long long blk = blockIdx.x, env = e0 + blk * 64 + l;
+  __shared__ double ring[kVjpRing * 64];  // the near parts of the adjoints, [slot][lane]
+  __shared__ int top_s;                   // the wavefront's longest tape of the step
+  const bool live = env < a.n && !bad[env < a.n ? env : 0];
+  double *adj_w = adj + blk * (long long)(nin + cap) * 64;
+  double *adj_l = adj_w + l, *ring_l = ring + l, *lam_l = lam + env;
+  for (int t = t1 - 1; t >= t0; --t) {
+    const long long wave = (long long)(t - t0) * nblk + blk;
+    const int len_t = live ? lens[wave * 64 + l] : -1;
+    const int len = len_t > 0 ? len_t : 0;  // a lane without a tape sweeps nothing
+    __syncthreads();
+    if (l == 0) top_s = 0;
+    __syncthreads();
+    if (len > 0) atomicMax(&top_s, len);
+    __syncthreads();
+    const int top = top_s;
+    const TdsRevTape tp = {ix + wave * cap * 64, pd + wave * cap * 64, adj_w, 64, cap, nin};
+    for (int s = 0; s < kVjpRing; ++s) ring_l[s * 64] = 0.0;
+    for (int i = 0; i < nin; ++i) adj_l[(long long)i * 64] = 0.0;
+    if (len_t >= 0) tds_traj_vjp_seed(a, (int)env, t, yidx + wave * a.nsd * 64 + l, 64, lam_l, a.n, adj_l, 64);
+    tds_vjp_sweep(tp, ring_l, l, len, top);
+    if (len_t >= 0) tds_traj_vjp_scatter(a, (int)env, t, adj_l, 64, lam_l, a.n);
+  }
+}
+
+// the last pass: NaN gradients where the primal was NaN or a tape overflowed
+__global__ void __launch_bounds__(256) tds_traj_vjp_nan_kernel(TdsTrajVjpArgs a, const int *bad, const int *over) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env < a.n && (bad[env] || over[env])) tds_traj_vjp_nan(a, env);
+}
+
+// lanes of a recording launch, environments per chunk and steps per window
+struct TdsTrajVjpPlan {
+  long long chunk;
+  int nblk, W;
+};
+
+inline TdsTrajVjpPlan tds_traj_vjp_plan(const tds_hip_sim *s, int n, int steps) {
+  long long budget = s->opt.get(TDS_OPT_TRAJ_VJP_LANES, kTrajVjpLanesDefault);
+  budget = budget < 64 ? 64 : budget > kTrajVjpLanesMax ? kTrajVjpLanesMax : budget / 64 * 64;
+  const long long n64 = ((long long)n + 63) / 64 * 64;
+  TdsTrajVjpPlan pl;
+  pl.chunk = n64 < budget ? n64 : budget;
+  pl.nblk = (int)(pl.chunk / 64);
+  long long W = budget / pl.chunk;
+  const long long opt = s->opt.get(TDS_OPT_TRAJ_STEPS, kTrajStepsDefault);
+  if (W > opt) W = opt;
+  if (W > steps) W = steps;
+  pl.W = W < 1 ? 1 : (int)W;
+  return pl;
+}
+
+// the work buffer: overflow flag | selection | state store | bad | over | lambda | then, one after the other in time,
+// phase 1's lanes and carry and phase 2's lengths, y variables, lanes, tape indices, tape partials and adjoints
+template <class B>
+struct TdsTrajVjpLayout {
+  size_t store, bad, over, lam, ph;                         // common
+  size_t p1_carry, p1_end;                                  // phase 1 (lanes at ph)
+  size_t lens, yidx, lanes, ix, pd, adj, total;             // phase 2 (lens at ph)
+  long long p1_lanes;
+  TdsTrajVjpLayout(const TdsTrajVjpPlan &pl, int n, int steps, int nsd, int nin, int p) {
+    using Lane = TdsVjpParamLane<B>;
+    constexpr size_t cap = Lane::cap;
+    const size_t rec = (size_t)pl.W * pl.chunk;  // lanes of a recording launch
+    store = 256 + tds_vjp_align((size_t)p * sizeof(tds_param_t));
+    bad = store + tds_vjp_align((size_t)n * steps * nsd * sizeof(double));
+    over = bad + tds_vjp_align((size_t)n * sizeof(int));
+    lam = over + tds_vjp_align((size_t)n * sizeof(int));
+    ph = lam + tds_vjp_align((size_t)n * nsd * sizeof(double));
+    p1_lanes = n < kJvpLanes ? n : kJvpLanes;
+    p1_carry = ph + tds_vjp_align((size_t)p1_lanes * sizeof(TdsTrajLane<B, 0>));
+    p1_end = p1_carry + tds_vjp_align((size_t)tds_traj_ncarry<0>(nsd) * n * sizeof(double));
+    lens = ph;
+    yidx = lens + tds_vjp_align(rec * sizeof(int));
+    lanes = yidx + tds_vjp_align(rec * nsd * sizeof(int));
+    ix = lanes + tds_vjp_align(rec * sizeof(Lane));
+    pd = ix + tds_vjp_align(rec * cap * sizeof(TdsRevIdx));
+    adj = pd + tds_vjp_align(rec * cap * sizeof(TdsRevPart));
+    total = adj + tds_vjp_align((size_t)pl.chunk * (nin + p + cap) * sizeof(double));
+    if (total < p1_end) total = p1_end;
+  }
+};
+
+template <class B>
+int tds_traj_vjp_run(tds_hip_sim *s, TdsTrajVjpArgs a, const tds_param_t *params_host, double *s_out) {
+  using Lane = TdsVjpParamLane<B>;
+  const int n = a.n, steps = a.steps, nsd = a.nsd, nin = s->model.input_dim;
+  const TdsTrajVjpPlan pl = tds_traj_vjp_plan(s, n, steps);
+  const TdsTrajVjpLayout<B> lay(pl, n, steps, nsd, nin, a.p);
+  int rc = tds_work_buffer(s, lay.total);
+  if (rc) return rc;
+  char *ws = (char *)s->d_diff_tmp;
+  tds_param_t *d_sel = (tds_param_t *)(ws + 256);
+  if (a.p > 0) {  // a blocking copy: earlier calls on the stream may still read the work buffer
+    TDS_HIP_TRY(hipStreamSynchronize(s->stream));
+    TDS_HIP_TRY(hipMemcpy(d_sel, params_host, (size_t)a.p * sizeof(tds_param_t), hipMemcpyHostToDevice));
+  }
+  a.params = d_sel;
+  a.overflow = (int *)ws;
+  double *store = (double *)(ws + lay.store), *lam = (double *)(ws + lay.lam);
+  int *bad = (int *)(ws + lay.bad), *over = (int *)(ws + lay.over);
+  a.store = store;
+  hipStream_t st = s->stream;
+  TDS_HIP_TRY(hipMemsetAsync(a.overflow, 0, sizeof(int), st));
+  // over and lambda (they lie side by side) start at zero; so do the accumulated gradients
+  TDS_HIP_TRY(hipMemsetAsync(over, 0, lay.ph - lay.over, st));
+  TDS_HIP_TRY(hipMemsetAsync(a.gx0, 0, (size_t)n * nin * sizeof(double), st));
+  if (a.p > 0) TDS_HIP_TRY(hipMemsetAsync(a.gtheta, 0, (size_t)n * a.p * sizeof(double), st));
+
+  // phase 1: the primal, at most traj_steps steps per launch (tds_traj.hip's chunking)
+  {
+    TdsTrajArgs ta = tds_traj_args(&s->model, a.m, n, steps, 1, a.x0, a.u, a.p, a.theta, 0, nullptr, store, nullptr);
+    ta.a.params = d_sel;
+    ta.items = n;
+    ta.carry = (double *)(ws + lay.p1_carry);
+    const long long opt = s->opt.get(TDS_OPT_TRAJ_STEPS, kTrajStepsDefault);
+    const int per = opt < 1 ? 1 : opt > steps ? steps : (int)opt;
+    const unsigned blocks = (unsigned)((lay.p1_lanes + 63) / 64);
+    for (int t0 = 0; t0 < steps; t0 += per) {
+      const int t1 = t0 + per < steps ? t0 + per : steps;
+      hipLaunchKernelGGL((tds_traj_vjp_primal_kernel<B>), dim3(blocks), dim3(64), 0, st, ta,
+                         (TdsTrajLane<B, 0> *)(ws + lay.ph), lay.p1_lanes, t0, t1, bad);
+      TDS_HIP_TRY(hipGetLastError());
+    }
+    if (s_out) {
+      const long long items = (long long)n * a.n_rec;
+      hipLaunchKernelGGL(tds_traj_vjp_select_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, store,
+                         s_out, items, steps, a.every, a.n_rec, nsd);
+      TDS_HIP_TRY(hipGetLastError());
+    }
+  }
+
+  // phase 2: the far parts start at zero; every sweep leaves those of its tape's variables at zero again (inputs:
+  // zeroed before each sweep), so one fill serves all windows and chunks
+  TDS_HIP_TRY(hipMemsetAsync(ws + lay.adj, 0, lay.total - lay.adj, st));
+  Lane *lanes = (Lane *)(ws + lay.lanes);
+  int *lens = (int *)(ws + lay.lens), *yidx = (int *)(ws + lay.yidx);
+  TdsRevIdx *ix = (TdsRevIdx *)(ws + lay.ix);
+  TdsRevPart *pd = (TdsRevPart *)(ws + lay.pd);
+  const int n_win = (steps + pl.W - 1) / pl.W;
+  for (long long e0 = 0; e0 < n; e0 += pl.chunk) {
+    const long long left = ((long long)n - e0 + 63) / 64;
+    const int nblk = left < pl.nblk ? (int)left : pl.nblk;
+    for (int w = n_win - 1; w >= 0; --w) {
+      const int t0 = w * pl.W, t1 = t0 + pl.W < steps ? t0 + pl.W : steps;
+      hipLaunchKernelGGL((tds_traj_vjp_record_kernel<B>), dim3((unsigned)((t1 - t0) * nblk)), dim3(64), 0, st, a,
+                         (int)e0, nblk, t0, bad, over, lanes, lens, yidx, ix, pd);
+      TDS_HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL((tds_traj_vjp_sweep_kernel<B>), dim3((unsigned)nblk), dim3(64), 0, st, a, (int)e0, nblk, t0,
+                         t1, bad, lens, yidx, ix, pd, (double *)(ws + lay.adj), lam);
+      TDS_HIP_TRY(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(tds_traj_vjp_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, bad, over);
+  TDS_HIP_TRY(hipGetLastError());
+  int overflow = 0;  // the call reports an overflow: it waits for its launches
+  TDS_HIP_TRY(hipMemcpyAsync(&overflow, a.overflow, sizeof(int), hipMemcpyDeviceToHost, st));
+  TDS_HIP_TRY(hipStreamSynchronize(st));
+  if (overflow)
+    return fail(TDS_ERR_UNSUPPORTED,
+                "trajectory VJP: an environment's tape exceeds the capacity of its model class%s");
+  return TDS_OK;
+}
+
+// the host instantiation: per environment the primal into a store, then one tape at a time, t descending
+template <class B>
+int tds_traj_vjp_host_run(TdsTrajVjpArgs a, double *s_out, int tape_cap, int *tape_len) {
+  using Lane = TdsVjpParamLane<B>;
+  const tds_model_t *m = a.m;
+  const int n = a.n, steps = a.steps, nsd = a.nsd, nin = m->input_dim, nall = nin + a.p;
+  const int cap = tape_cap > 0 ? tape_cap : Lane::cap;
+  std::vector<double> store((size_t)n * steps * nsd), lam(nsd), adj((size_t)nall + cap);
+  std::vector<TdsTrajLane<B, 0>> Ly(1);
+  std::vector<Lane> L(1);
+  std::vector<TdsRevIdx> ix(cap);
+  std::vector<TdsRevPart> pd(cap);
+  std::vector<int> yi(nsd);
+  a.store = store.data();
+  TdsTrajArgs ta = tds_traj_args(m, m, n, steps, 1, a.x0, a.u, a.p, a.theta, 0, nullptr, store.data(), nullptr);
+  ta.a.params = a.params;
+  ta.items = n;
+  const TdsRevTape tp = {ix.data(), pd.data(), adj.data(), 1, cap, nall};
+  tds_rev_tape() = tp;
+  int bad = 0, over = 0;
+  for (int e = 0; e < n; ++e) {
+    const int bad_e = tds_traj_advance<B, 0>(ta, Ly[0], e, 0, steps);
+    if (s_out)
+      for (int r = 0; r < a.n_rec; ++r)
+        std::copy_n(&store[((size_t)e * steps + (size_t)(r + 1) * a.every - 1) * nsd], nsd,
+                    s_out + ((size_t)e * a.n_rec + r) * nsd);
+    std::fill_n(a.gx0 + (size_t)e * nin, nin, 0.0);
+    std::fill_n(a.gtheta + (size_t)e * a.p, a.p, 0.0);
+    std::fill(lam.begin(), lam.end(), 0.0);
+    int over_e = 0;
+    for (int t = steps - 1; t >= 0 && !bad_e; --t) {
+      tds_traj_vjp_record<B>(a, L[0], e, t);
+      const int len = tds_rev_cursor(0);
+      if (tape_len) tape_len[(size_t)e * steps + t] = len > cap ? -1 : len;
+      over_e |= len > cap;
+      if (over_e) continue;  // the remaining steps are recorded for their lengths only
+      for (int i = 0; i < nsd; ++i) yi[i] = L[0].y[i].i;
+      std::fill(adj.begin(), adj.begin() + nall + len, 0.0);
+      tds_traj_vjp_seed(a, e, t, yi.data(), 1, lam.data(), 1, adj.data(), 1);
+      tds_rev_sweep_host(tp, len);
+      tds_traj_vjp_scatter(a, e, t, adj.data(), 1, lam.data(), 1);
+    }
+    if (bad_e && tape_len) std::fill_n(tape_len + (size_t)e * steps, steps, 0);
+    if (bad_e || over_e) tds_traj_vjp_nan(a, e);
+    bad |= bad_e, over |= over_e;
+  }
+  tds_rev_tape() = TdsRevTape{};
+  if (over) return fail(TDS_ERR_UNSUPPORTED, "trajectory VJP: an environment's tape exceeds the capacity%s");
+  if (bad) return fail(TDS_ERR_INVALID_ARG, "step Jacobians: joint-space inertia not positive definite%s");
+  return TDS_OK;
+}
+
+// the checks of tds_traj_check_args and the outputs the call needs
+int tds_traj_vjp_check_args(const char *fn, const tds_model_t *m, int n, int steps, int every, int p, const void *x0,
+                            const void *u, const void *params, const void *gs, const void *gx0, const void *gu,
+                            const void *gtheta) {
+  int rc = tds_traj_check_args(fn, n, steps, every, 1, p, x0, params, gs, gx0, gx0);
+  if (rc) return rc;
+  const int nact = m->input_dim - m->dof_q - m->dof_qd - (m->step_mode == TDS_STEP_LOCOMOTION ? 3 : 0);
+  if ((p > 0 && !gtheta) || (u && nact > 0 && steps > 1 && !gu))
+    return fail(TDS_ERR_INVALID_ARG, fn, ": NULL or empty argument");
+  return TDS_OK;
+}
+
+TdsTrajVjpArgs tds_traj_vjp_args(const tds_model_t *m, const tds_model_t *m_arg, int n, int steps, int every,
+                                 const double *x0, const double *u, int p, const tds_param_t *params,
+                                 const double *theta, const double *gs, double *gx0, double *gu, double *gtheta) {
+  TdsTrajVjpArgs a;
+  a.m = m_arg, a.n = n, a.p = p, a.steps = steps, a.every = every, a.n_rec = steps / every;
+  a.nsd = m->dof_q + m->dof_qd;
+  a.nact = m->input_dim - a.nsd - (m->step_mode == TDS_STEP_LOCOMOTION ? 3 : 0);
+  // actions that no step reads (steps = 1) or that have no slots are no input of the call
+  a.x0 = x0, a.u = steps > 1 && a.nact > 0 ? u : nullptr, a.theta = theta, a.gs = gs, a.params = params;
+  a.store = nullptr, a.gx0 = gx0, a.gu = gu, a.gtheta = gtheta, a.overflow = nullptr;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tds_hip_trajectory_vjp(tds_hip_sim_t *s, int n, int steps, int every, const void *x0_dev, const void *u_dev,
+                           int p, const tds_param_t *params_host, const void *theta_dev, const void *gs_dev,
+                           void *s_dev, void *gx0_dev, void *gu_dev, void *gtheta_dev) {
+  if (!s) return fail(TDS_ERR_INVALID_ARG, "tds_hip_trajectory_vjp: NULL or empty argument%s");
+  int rc = tds_traj_vjp_check_args("tds_hip_trajectory_vjp%s", &s->model, n, steps, every, p, x0_dev, u_dev,
+                                   params_host, gs_dev, gx0_dev, gu_dev, gtheta_dev);
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  int cls;
+  if ((rc = tds_diff_prepare(s, &cls))) return rc;
+  if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
+  const TdsTrajVjpArgs a = tds_traj_vjp_args(&s->model, (const tds_model_t *)s->d_diff_model, n, steps, every,
+                                             (const double *)x0_dev, (const double *)u_dev, p, nullptr,
+                                             (const double *)theta_dev, (const double *)gs_dev, (double *)gx0_dev,
+                                             (double *)gu_dev, (double *)gtheta_dev);
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_traj_vjp_run<typename decltype(b)::type>(s, a, params_host, (double *)s_dev);
+  });
+}
+
+int tds_hip_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int every, const double *x0,
+                                const double *u, int p, const tds_param_t *params, const double *theta,
+                                const double *gs, double *s, double *gx0, double *gu, double *gtheta, int tape_cap,
+                                int *tape_len) {
+  if (!model) return fail(TDS_ERR_INVALID_ARG, "tds_hip_trajectory_vjp_host: NULL or empty argument%s");
+  int rc = tds_traj_vjp_check_args("tds_hip_trajectory_vjp_host%s", model, n, steps, every, p, x0, u, params, gs, gx0,
+                                   gu, gtheta);
+  if (rc) return rc;
+  int cls;
+  if ((rc = tds_param_host_prepare(model, p, params, &cls))) return rc;
+  const TdsTrajVjpArgs a = tds_traj_vjp_args(model, model, n, steps, every, x0, u, p, params, theta, gs, gx0, gu, gtheta);
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_traj_vjp_host_run<typename decltype(b)::type>(a, s, tape_cap, tape_len);
+  });
+}
+
+}  // extern "C"

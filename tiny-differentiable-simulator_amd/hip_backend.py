@@ -135,6 +135,10 @@ def lib():
             [C.c_void_p, C.c_int] + [C.c_void_p] * 3
         L.tds_hip_trajectory_jvp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
             [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.tds_hip_trajectory_vjp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
+            [C.c_void_p] * 6
+        L.tds_hip_trajectory_vjp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
+            [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
         RP = C.POINTER(_model.RbModel)
         L.tds_rb_params_get.argtypes = [RP, C.c_int, PP, C.c_void_p]
         L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
@@ -364,6 +368,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
     "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
+    "tds_hip_trajectory_vjp", "tds_hip_trajectory_vjp_host",
     "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
@@ -812,6 +817,43 @@ def trajectory_jvp_host(m: _model.Model, x0, v=None, steps: int = 1, every: int 
     if js is not None and squeeze:
         js = js[:, 0]
     return s, js
+
+
+def trajectory_vjp_host(m: _model.Model, x0, gs, steps: int, every: int = 1, u=None, params=(), theta=None,
+                        tape_cap: int = 0, tape_len: bool = False):
+    """Reverse-mode trajectory derivative on the CPU (tds_hip_trajectory_vjp_host; the checker of
+    HipSim.trajectory_vjp, needs no GPU).
+
+    x0, u, params and theta as for trajectory_jvp_host; gs [N, n_rec, nq + nd], the cotangent on the recorded states.
+    Returns (s, gx0, gu, gtheta): s [N, n_rec, nq + nd], gx0 [N, input_dim], gu [N, steps - 1, n_act] (zeros where u is
+    None) and gtheta [N, p]; with tape_len also the entries each step recorded [N, steps] (-1: overflowed).  tape_cap
+    as for vjp_host."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x0.shape[0], len(params)
+    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    up = None
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (n, max(int(steps) - 1, 0), n_act):
+            raise ValueError(f"u: expected [{n}, {int(steps) - 1}, {n_act}], got {tuple(u.shape)}")
+        up = u.ctypes.data
+    gs = np.ascontiguousarray(gs, dtype=np.float64)
+    if n_rec > 0 and gs.shape != (n, n_rec, nsd):
+        raise ValueError(f"gs: expected [{n}, {n_rec}, {nsd}], got {tuple(gs.shape)}")
+    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
+    gx0 = np.zeros((n, m.input_dim), dtype=np.float64)
+    gu = np.zeros((n, max(int(steps) - 1, 0), max(n_act, 0)), dtype=np.float64)
+    gth = np.zeros((n, p), dtype=np.float64)
+    lens = np.zeros((n, max(int(steps), 1)), dtype=np.int32) if tape_len else None
+    _check(lib().tds_hip_trajectory_vjp_host(C.byref(m), n, int(steps), int(every), x0.ctypes.data, up, p, sel,
+                                             None if th is None else th.ctypes.data, gs.ctypes.data, s.ctypes.data,
+                                             gx0.ctypes.data, gu.ctypes.data, gth.ctypes.data, int(tape_cap),
+                                             lens.ctypes.data if tape_len else None))
+    return (s, gx0, gu, gth, lens) if tape_len else (s, gx0, gu, gth)
 
 
 def trajectory_directions(input_dim: int, wrt, p: int = 0, device=None):
@@ -1307,6 +1349,42 @@ class HipSim:
                                             C.c_void_p(v3.data_ptr()), C.c_void_p(s.data_ptr()),
                                             C.c_void_p(js.data_ptr())))
         return s, (js[:, 0] if squeeze else js)
+
+    def trajectory_vjp(self, x0, gs, steps: int, every: int = 1, u=None, params=(), theta=None):
+        """(s, gx0, gu, gtheta): the states s of trajectory_jvp's trajectory and the gradients of <gs, s> for the
+        cotangent gs [N, n_rec, nq + nd] on them: gx0 [N, input_dim] in x0, gu [N, steps - 1, n_act] in the actions u of
+        steps 1 .. (zeros where u is None: x0's action slots then feed every step, and gx0 holds their gradient) and
+        gtheta [N, p] in theta.  Reverse mode: one primal pass, then the steps' tapes recorded several at a time
+        (option traj_vjp_lanes) and swept back in turn; the call waits for its kernels.  f64 handles only."""
+        import torch
+
+        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
+        x0 = x0.contiguous()
+        n, p = x0.shape[0], len(params)
+        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
+        sel = param_spec(params)
+        th = None if theta is None else self._theta(theta, n, p)
+        up = None
+        if u is not None:
+            assert u.is_cuda and u.dtype == torch.float64
+            assert tuple(u.shape) == (n, max(int(steps) - 1, 0), n_act), (tuple(u.shape), n, int(steps) - 1, n_act)
+            u = u.contiguous()
+            up = C.c_void_p(u.data_ptr())
+        gs = gs.contiguous()
+        assert gs.is_cuda and gs.dtype == torch.float64
+        assert n_rec < 1 or tuple(gs.shape) == (n, n_rec, nsd), (tuple(gs.shape), n, n_rec, nsd)
+        dev = x0.device
+        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=dev)
+        gx0 = torch.empty((n, self.input_dim), dtype=torch.float64, device=dev)
+        gu = torch.zeros((n, max(int(steps) - 1, 0), max(n_act, 0)), dtype=torch.float64, device=dev)
+        gth = torch.empty((n, p), dtype=torch.float64, device=dev)
+        # (pointers of empty tensors may be NULL: every output gets a buffer of at least one element)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else s.data_ptr())  # noqa: E731
+        _check(lib().tds_hip_trajectory_vjp(self.h, n, int(steps), int(every), C.c_void_p(x0.data_ptr()), up, p, sel,
+                                            None if th is None else C.c_void_p(th.data_ptr()),
+                                            C.c_void_p(gs.data_ptr()), C.c_void_p(s.data_ptr()),
+                                            C.c_void_p(gx0.data_ptr()), ptr(gu), ptr(gth)))
+        return s, gx0, gu, gth
 
     # -- dynamics queries: kinematics, mass matrix, bias, forward and inverse dynamics, point Jacobians -----------
     def _dyn_rows(self, a, n, width, what):
