@@ -101,6 +101,24 @@ __device__ int tds_oct_prof_iter = 500;
 #define OCT_MARK(name) do { } while (0)
 #endif
 
+// The step boundary of the two-wavefront step-loop builds, three parts, each behind a switch of its own (an experiment build
+// turns one off with -DTDS_OCT_...=0; builds that do not take a part keep their statement order — see oct_body):
+//   TDS_OCT_SD_LATE    a friction row's first use of its normal row's impulse behind the row's 8-lane sum
+//   TDS_OCT_CARRY      the main wavefront's state across barrier (0) in registers
+//   TDS_OCT_TOP_EARLY  the constants of the PD block and jcalc requested in front of barrier (0)
+#ifndef TDS_OCT_SD_LATE
+#define TDS_OCT_SD_LATE 1
+#endif
+#ifndef TDS_OCT_CARRY
+#define TDS_OCT_CARRY 1
+#endif
+#ifndef TDS_OCT_TOP_EARLY
+#define TDS_OCT_TOP_EARLY 1
+#endif
+#ifndef TDS_OCT_SPLIT_LOOP  // (1: a loop per wavefront even where nothing is carried — what the split is worth on its own)
+#define TDS_OCT_SPLIT_LOOP 0
+#endif
+
 namespace {
 
 #define OCT_SYNC()                                             \
@@ -245,6 +263,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // (16-32 B), the straight-line form of build 3 with two more registers, and the one-wavefront build plays both roles in one
   // stream: nothing waits for its main part (profiles/oct_kernel_resources_lds.txt).  Same arithmetic either way, term by term.
   constexpr bool BATCH_SCHUR = LOOP && BUILD == 3;
+  // The step boundary (step-loop forms of the two-wavefront builds only: where a switch is off every statement stands where it stood —
+  // reordered statements move the register allocation of builds that do not take them, tools/experiments/lds_batching_not_kept.txt):
+  // SD_LATE: main_sweep; CARRY, TOP_EARLY: main_fin -> main_kin of the next step
+  constexpr bool SD_LATE = LOOP && (BUILD == 2 || BUILD == 3) && TDS_OCT_SD_LATE != 0;
+  // (CARRY and TOP_EARLY in the build for one wavefront per SIMD only — the benchmark's: the 256-register build pays for the
+  //  carried state with 20 B of scratch and for the 33 constants with 64 - 84 B: profiles/oct_step_boundary_resources.txt)
+  constexpr bool CARRY = LOOP && BUILD == 3 && TDS_OCT_CARRY != 0;
+  constexpr bool TOP_EARLY = LOOP && BUILD == 3 && TDS_OCT_TOP_EARLY != 0;
+  constexpr bool SPLIT_LOOP = CARRY || TOP_EARLY || (LOOP && BUILD == 3 && TDS_OCT_SPLIT_LOOP != 0);
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -299,12 +326,70 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // (where my lane's action sits in the record: one register across the steps, against a table read in front of the PD block's
   //  read of the action — two LDS round trips in a row at the top of the main wavefront's step)
   const int act_slot = (int)(CT + (threadIdx.x & 7) * TB::LSTR)[TB::ACT];
-  for (int it = 0; it < nsteps; ++it) {  // ================================ step loop ================================
-  // (nothing but `it`, next_act and act_slot lives across an iteration: lane and kernel-argument segment are laundered)
+  // CARRY: what the main wavefront's integration (main_fin) hands to its next kinematics (main_kin) in registers — its dof's q
+  // and qd, the root's six coordinates and six velocities, the very values it stores into the LDS record — so that the top of a
+  // step does not read back across barrier (0) what the wavefront wrote itself a phase earlier.  The record is read for the
+  // first step of a launch (here: behind the prologue's barrier) and where the reset pool replaced the state of one of the
+  // wavefront's environments (main_pool); lanes of an environment past n_envs carry what they stored, as they read it before.
+  struct Carried { T q, qd, rq[6], rqd[6]; };
+  // TOP_EARLY: the constants of the PD block, jcalc, the root's frame and velocities — nothing writes them inside a launch: the
+  // lane table and the scalar table (written by the prologue, in front of its barrier), kp / kd / max_force of the x record
+  // (the reset pool rewrites q | qd only, the helper the action slots only) — requested by the main wavefront in main_fin and
+  // held across barrier (0), whose own wait for the LDS takes them in: behind it nothing covers their round trips.  (xt: the
+  // translation of X_T; its rotation, read where X_T is not the identity only, stays where it is.)
+  struct TopConsts { T S[6], rotf, nax[3], nn[6], xt[3], ipose, stiff, damp, act_lim, xt_ident, base_t[3], grav[3], kp, kd, max_force; };
+  auto carry_load = [&](const T *xr_, int lane_, Carried &c) {
+    c.q = xr_[6 + lane_];
+    c.qd = xr_[nq + 6 + lane_];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      c.rq[r] = xr_[r];
+      c.rqd[r] = xr_[nq + r];
+    }
+  };
+  auto top_request = [&](const T *xr_, const T *CL_, TopConsts &t) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t.S[k] = CL_[TB::S + k];
+    t.rotf = CL_[TB::ROTF];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.nax[k] = CL_[TB::NAX + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t.nn[k] = CL_[TB::NN + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.xt[k] = CL_[TB::XT + 9 + k];
+    t.ipose = CL_[TB::IPOSE];
+    t.stiff = CL_[TB::STIFF];
+    t.damp = CL_[TB::DAMP];
+    t.act_lim = CT[TB::SC + TB::ACTION_LIMIT];
+    t.xt_ident = CT[TB::SC + TB::XT_IDENT];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      t.base_t[k] = CT[TB::SC + TB::BASE_T + k];
+      t.grav[k] = CT[TB::SC + TB::GRAV + k];
+    }
+    t.kp = xr_[nq + nd + adim];
+    t.kd = xr_[nq + nd + adim + 1];
+    t.max_force = xr_[nq + nd + adim + 2];
+  };
+  Carried car = {};
+  TopConsts tc = {};
+  if constexpr (CARRY || TOP_EARLY) {
+    const int lane_ = threadIdx.x & 7;
+    const T *const xr_ = sm + ((threadIdx.x & 63) >> 3) * O.stride;
+    if constexpr (CARRY) carry_load(xr_, lane_, car);
+    if constexpr (TOP_EARLY) top_request(xr_, CT + lane_ * TB::LSTR, tc);
+  }
+  // ================================ a step: the body of the step loop ================================
+  // ROLE 2: one loop for the whole workgroup, the wavefronts part ways inside the step (`wv`).  ROLE 0 / 1 (SPLIT_LOOP): the
+  // main wavefront's / the helper's step, each in a loop of its own — see the loops behind the body.
+  auto step_body = [&](auto rolec, const int it) {
+  constexpr int ROLE = decltype(rolec)::value;
+  // (nothing but `it`, next_act and act_slot lives across an iteration — and, on the main wavefront of the builds that take
+  //  them, `car` and `tc` from main_fin to main_kin: lane and kernel-argument segment are laundered)
   const __attribute__((address_space(4))) char *ka_seg = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
   int tid = threadIdx.x;
   if constexpr (LOOP) asm volatile("" : "+s"(ka_seg), "+v"(tid));
-  const int wv = W2 ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;
+  const int wv = ROLE < 2 ? ROLE : (W2 ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0);
   const bool is_main = !W2 || wv == 0, is_help = !W2 || wv == 1;  // wave-uniform (the profile build's stamps)
   // Two wavefronts per SIMD (BUILD 2): where a main wavefront shares its SIMD with a helper, the main one — the step's
   // instruction stream — issues first (Ant x 8192, same box: 7.93 / 8.09e8 -> 8.42 / 8.37e8 env-steps/s; no effect at one
@@ -359,13 +444,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 
   // the root body's frame and the root's revolute axes from the six sines / cosines (kinematics.hpp:64-97; tds_kernels.hip
   // phase C: same formulas): R5, P, A4, A5 and the linear parts P x A of the three revolute axes (A3 = e_x)
-  auto root_frame = [&](T sx, T cx, T sy, T cy, T sz, T cz) {
+  // (rq, bt: the root's position and the base offset — the record and the table, or the main wavefront's registers: CARRY, TOP_EARLY)
+  auto root_frame = [&](const T *rq, const T *bt, T sx, T cx, T sy, T cy, T sz, T cz) {
     R5[0] = cy * cz;                 R5[1] = -cy * sz;                R5[2] = sy;
     R5[3] = sx * sy * cz + cx * sz;  R5[4] = cx * cz - sx * sy * sz;  R5[5] = -sx * cy;
     R5[6] = sx * sz - cx * sy * cz;  R5[7] = cx * sy * sz + sx * cz;  R5[8] = cx * cy;
-    P[0] = xr[0] + CT[TB::SC + TB::BASE_T];
-    P[1] = xr[1] + CT[TB::SC + TB::BASE_T + 1];
-    P[2] = xr[2] + CT[TB::SC + TB::BASE_T + 2];
+    P[0] = rq[0] + bt[0];
+    P[1] = rq[1] + bt[1];
+    P[2] = rq[2] + bt[2];
     A4[0] = T(0); A4[1] = cx; A4[2] = sx;
     A5[0] = sy; A5[1] = -sx * cy; A5[2] = cx * cy;
     pA3[0] = T(0); pA3[1] = P[2]; pA3[2] = -P[1];  // P x e_x
@@ -389,26 +475,35 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   auto main_kin = [&]() {
     // ================================ main: PD, jcalc, kinematics ================================
     OCT_MARK("main_top");
-    q = xr[dq];
-    qd = xr[nq + dq];
+    // (a constant of the top of the step: the register requested in front of barrier (0), TOP_EARLY, or the read at its place
+    //  of use — the condition is a compile-time constant: one arm only is compiled)
+#define OCT_TOP(early, read) (TOP_EARLY ? (early) : (read))
+    if constexpr (CARRY) {
+      q = car.q;
+      qd = car.qd;
+    } else {
+      q = xr[dq];
+      qd = xr[nq + dq];
+    }
     // ---- PD controller (locomotion_contact_simulation.h:168-258); joint stiffness / damping
     tau = T(0);
     {
       const int act_i = act_slot;
       if (act_i >= 0) {
         const int var = nq + nd + adim;
-        const T kp = xr[var], kd = xr[var + 1], max_force = xr[var + 2];
-        const T act_lim = CT[TB::SC + TB::ACTION_LIMIT];
+        const T kp = OCT_TOP(tc.kp, xr[var]), kd = OCT_TOP(tc.kd, xr[var + 1]), max_force = OCT_TOP(tc.max_force, xr[var + 2]);
+        const T act_lim = OCT_TOP(tc.act_lim, CT[TB::SC + TB::ACTION_LIMIT]);
+        // (the action stays behind barrier (0): the helper writes it during the step)
         T a = xr[nq + nd + act_i];
         a = a < act_lim ? a : act_lim;
         a = a > -act_lim ? a : -act_lim;
-        const T q_des = CL[TB::IPOSE] + a;
+        const T q_des = OCT_TOP(tc.ipose, CL[TB::IPOSE]) + a;
         T f = kp * (q_des - q) + kd * (T(0) - qd);
         f = f > -max_force ? f : -max_force;
         f = f < max_force ? f : max_force;
         tau = f;
       }
-      tau -= CL[TB::STIFF] * q + CL[TB::DAMP] * qd;
+      tau -= OCT_TOP(tc.stiff, CL[TB::STIFF]) * q + OCT_TOP(tc.damp, CL[TB::DAMP]) * qd;
       // (tau is next read by the forward dynamics, two barriers on: left to itself the back end moves this line down there and
       //  keeps stiffness and damping alive for it — in the 256-register build through scratch, a memory round trip the main
       //  wavefront waited for behind barrier (2))
@@ -417,32 +512,32 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_MARK("main_jcalc");
     // ---- B. jcalc (link.hpp:229-287)
 #pragma unroll
-    for (int k = 0; k < 6; ++k) Sl[k] = CL[TB::S + k];
+    for (int k = 0; k < 6; ++k) Sl[k] = OCT_TOP(tc.S[k], CL[TB::S + k]);
     T Rp[9], tp[3];
     {
       // the joint transform: R_J = cos I + sin [n]x + (1 - cos) n n^T about the joint's unit axis (table: n, n n^T; a prismatic
       // joint's angle is multiplied by 0), t_J = S_linear q (zero for a revolute joint) — every joint type of link.hpp:229-287
       // without a branch; X_parent = X_T X_J, and where every X_T rotation is the identity (the Ant) no product at all
       T sn, cs;
-      tds_sincos(q * CL[TB::ROTF], &sn, &cs);
+      tds_sincos(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), &sn, &cs);
       const T c1 = T(1) - cs;
-      const T nx = CL[TB::NAX], ny = CL[TB::NAX + 1], nz = CL[TB::NAX + 2];
+      const T nx = OCT_TOP(tc.nax[0], CL[TB::NAX]), ny = OCT_TOP(tc.nax[1], CL[TB::NAX + 1]), nz = OCT_TOP(tc.nax[2], CL[TB::NAX + 2]);
       T RJ[9];
-      RJ[0] = cs + c1 * CL[TB::NN + 0];
-      RJ[1] = c1 * CL[TB::NN + 1] - sn * nz;
-      RJ[2] = c1 * CL[TB::NN + 2] + sn * ny;
-      RJ[3] = c1 * CL[TB::NN + 1] + sn * nz;
-      RJ[4] = cs + c1 * CL[TB::NN + 3];
-      RJ[5] = c1 * CL[TB::NN + 4] - sn * nx;
-      RJ[6] = c1 * CL[TB::NN + 2] - sn * ny;
-      RJ[7] = c1 * CL[TB::NN + 4] + sn * nx;
-      RJ[8] = cs + c1 * CL[TB::NN + 5];
+      RJ[0] = cs + c1 * OCT_TOP(tc.nn[0], CL[TB::NN + 0]);
+      RJ[1] = c1 * OCT_TOP(tc.nn[1], CL[TB::NN + 1]) - sn * nz;
+      RJ[2] = c1 * OCT_TOP(tc.nn[2], CL[TB::NN + 2]) + sn * ny;
+      RJ[3] = c1 * OCT_TOP(tc.nn[1], CL[TB::NN + 1]) + sn * nz;
+      RJ[4] = cs + c1 * OCT_TOP(tc.nn[3], CL[TB::NN + 3]);
+      RJ[5] = c1 * OCT_TOP(tc.nn[4], CL[TB::NN + 4]) - sn * nx;
+      RJ[6] = c1 * OCT_TOP(tc.nn[2], CL[TB::NN + 2]) - sn * ny;
+      RJ[7] = c1 * OCT_TOP(tc.nn[4], CL[TB::NN + 4]) + sn * nx;
+      RJ[8] = cs + c1 * OCT_TOP(tc.nn[5], CL[TB::NN + 5]);
       const T tJ[3] = {Sl[3] * q, Sl[4] * q, Sl[5] * q};
-      if (CT[TB::SC + TB::XT_IDENT] != T(0)) {  // wave-uniform
+      if (OCT_TOP(tc.xt_ident, CT[TB::SC + TB::XT_IDENT]) != T(0)) {  // wave-uniform
 #pragma unroll
         for (int k = 0; k < 9; ++k) Rp[k] = RJ[k];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) tp[k] = CL[TB::XT + 9 + k] + tJ[k];
+        for (int k = 0; k < 3; ++k) tp[k] = OCT_TOP(tc.xt[k], CL[TB::XT + 9 + k]) + tJ[k];
       } else {
         T RT[9], r[3];
 #pragma unroll
@@ -450,7 +545,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         mat3_mul(RT, RJ, Rp);
         mat3_mulv(RT, tJ, r);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) tp[k] = CL[TB::XT + 9 + k] + r[k];
+        for (int k = 0; k < 3; ++k) tp[k] = OCT_TOP(tc.xt[k], CL[TB::XT + 9 + k]) + r[k];
       }
     }
     OCT_MARK("main_rootsincos");
@@ -458,7 +553,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     //         environment, broadcast (and, two-wavefront build, handed to the helper behind the links' world transforms)
     {
       T rs, rc;
-      tds_sincos(xr[3 + (lane < 3 ? lane : 0)], &rs, &rc);
+      T ang;  // (my root angle: lanes 0, 1, 2 the three angles, the others the first)
+      if constexpr (CARRY) {
+        // (by value first: a conditional between array elements is a conditional between addresses, and `car` a record in scratch)
+        const T a3 = car.rq[3], a4 = car.rq[4], a5 = car.rq[5];
+        ang = lane == 1 ? a4 : (lane == 2 ? a5 : a3);
+      } else {
+        ang = xr[3 + (lane < 3 ? lane : 0)];
+      }
+      tds_sincos(ang, &rs, &rc);
       const T sx = oct_bcast<0>(rs), cx = oct_bcast<0>(rc);
       const T sy = oct_bcast<1>(rs), cy = oct_bcast<1>(rc);
       const T sz = oct_bcast<2>(rs), cz = oct_bcast<2>(rc);
@@ -469,11 +572,12 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           sc[2 * lane + 1] = rc;
         }
       }
-      root_frame(sx, cx, sy, cy, sz, cz);
+      root_frame(CARRY ? car.rq : xr, TOP_EARLY ? tc.base_t : CT + TB::SC + TB::BASE_T, sx, cx, sy, cy, sz, cz);
     }
     OCT_MARK("main_rootvel");
     {
-      const T d0 = xr[nq + 0], d1 = xr[nq + 1], d2 = xr[nq + 2], d3 = xr[nq + 3], d4 = xr[nq + 4], d5 = xr[nq + 5];
+      const T *const rqd = CARRY ? car.rqd : xr + nq;
+      const T d0 = rqd[0], d1 = rqd[1], d2 = rqd[2], d3 = rqd[3], d4 = rqd[4], d5 = rqd[5];
       const T U[3] = {d0, d1, d2};
       const T J3[3] = {d3, T(0), T(0)}, J4[3] = {A4[0] * d4, A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
       const T W4[3] = {J3[0] + J4[0], J3[1] + J4[1], J3[2] + J4[2]};
@@ -504,9 +608,10 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         v5[k] = W5[k];
         v5[3 + k] = V5[k];
         a5[k] = a45[k] + a55[k];
-        a5[3 + k] = (l3[k] + l4[k] + l5[k]) - CT[TB::SC + TB::GRAV + k];
+        a5[3 + k] = (l3[k] + l4[k] + l5[k]) - OCT_TOP(tc.grav[k], CT[TB::SC + TB::GRAV + k]);
       }
     }
+#undef OCT_TOP
     OCT_MARK("main_legs");
     // ---- the legs: the ankle composes its joint transform with the hip's (one step of a segmented scan along the pair),
     //      the root's pose in front; prefix sums of the joint velocities and of the velocity-product accelerations
@@ -635,7 +740,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 #pragma unroll
       for (int k = 0; k < 3; ++k) p[k] = kin[9 + k];
       const T *const sc = E + O.win + 8 * OctLds::ZW + 96;
-      root_frame(sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]);
+      root_frame(xr, CT + TB::SC + TB::BASE_T, sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]);
     }
     // ---- I. narrowphase (contact_point.hpp:96-161): my link's capsule = two spheres; the root body's sphere on every lane.
     //         Penetrating points in the reference's order (root, then per link +L/2 end, -L/2 end) into the contact list
@@ -1291,6 +1396,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         // (a normal row's b_r carries (1 + e) J (dt qdd): the e-fold of z~_r . (dt y~) = -z~_r . u~_init on top of what u~ holds)
         if constexpr (NORMAL) jw = oct_sum(zl * (u + rest * u_init) + o.zm * (urm + rest * urm_init));
         else jw = oct_sum(zl * u + o.zm * urm);
+        // (SD_LATE: the normal row's impulse is first used HERE — tied to the sum, behind its last addition.  Left to itself the
+        //  back end canonicalises it for the maximum below directly behind its request at the top of the friction arm: a wait
+        //  for the whole LDS round trip — and for the next row's five operands — in front of the sum, which does not need it)
+        T sd = T(0);
+        if constexpr (!NORMAL) {
+          sd = o.sd;
+          if constexpr (SD_LATE) asm volatile("" : "+v"(jw), "+v"(sd));
+        }
         T xn;
         if constexpr (FIRST) xn = (o.b - jw) * o.a;
         else xn = (o.b - (jw - o.g * o.xo)) * o.a;
@@ -1298,7 +1411,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           xn = max_t<T>(xn, T(0));
           xn = min_t<T>(xn, sw_cap);
         } else {
-          const T hi = mu * max_t<T>(o.sd, T(0));  // where_lt(s, 0, 0, s)
+          const T hi = mu * max_t<T>(sd, T(0));  // where_lt(s, 0, 0, s)
           xn = max_t<T>(xn, -hi);
           xn = min_t<T>(xn, hi);
         }
@@ -1396,6 +1509,10 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       qn0 = qn_root[0];
       qn2 = qn_root[2];
       qo0 = q_old0;
+      // (TOP_EARLY: the next step's constants, behind the integration's own reads — nothing waits for them in front of barrier
+      //  (0), whose wait for the LDS completes them; the prologue's barrier ordered the tables' and the record's writes, and
+      //  nothing writes these slots inside a launch)
+      if constexpr (TOP_EARLY) top_request(xr, CL, tc);
       OCT_SYNC();
       if (lane == 0) {
 #pragma unroll
@@ -1404,8 +1521,18 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           xr[nq + r] = qdr_new[r];
         }
       }
-      xr[dq] = q + qd_new * dt;
+      const T q_new = q + qd_new * dt;
+      xr[dq] = q_new;
       xr[nq + dq] = qd_new;
+      if constexpr (CARRY) {  // (the stores above stay: the helper's records, the rows and the next launch read the record)
+        car.q = q_new;
+        car.qd = qd_new;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          car.rq[r] = qn_root[r];
+          car.rqd[r] = qdr_new[r];
+        }
+      }
       if (lane == 0) {
         xr[in_dim] = q_old0;  // x_{t-1} (the Ant's reward reads it)
         xr[in_dim + 3] = T(0);  // "the y state of this step is out already" (set below for an environment the reset pool re-initialises)
@@ -1471,7 +1598,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     // ---- auto_reset_when_done through the reset pool (ctl.pool; ars_vectorized_environment.h:262-277): a done environment
     //      takes its next pre-settled state — y, reward and done describe the terminal step, the observation and the state
     //      the fresh environment: its y state goes out HERE, before the record is overwritten
-    if (ctl.pool != nullptr && valid && (done_in_reg ? done_reg : xr[in_dim + 1] != T(0))) {
+    const bool replaced = ctl.pool != nullptr && valid && (done_in_reg ? done_reg : xr[in_dim + 1] != T(0));
+    if (replaced) {
       TR *yo, *yo2;
       int yend, yend2;
       y_where(yo, yo2, yend, yend2);
@@ -1491,6 +1619,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       if (lane == 0) {
         ctl.reset_count[env] = c + 1u;
         xr[in_dim + 3] = T(1);
+      }
+    }
+    if constexpr (CARRY) {
+      // (the carried state of a replaced environment is the terminal step's: where any environment of the wavefront was replaced —
+      //  wave-uniform, rare — every lane takes its state from the record again; the others read back what they stored)
+      if (ctl.pool != nullptr && __any(replaced)) {
+        OCT_SYNC();
+        carry_load(xr, lane, car);
       }
     }
     OCT_MARK("main_pool_end");
@@ -1758,7 +1894,21 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     y_slot = y_slot + 1 >= ctl_arg.y_slots ? 0 : y_slot + 1;
     o_slot = o_slot + 1 >= ctl_arg.obs_slots ? 0 : o_slot + 1;
   }
-  }  // ================================ end of the step loop ================================
+  };  // ================================ end of a step ================================
+  // ================================ step loop ================================
+  // SPLIT_LOOP: each wavefront of the workgroup in a loop of its own.  What the main wavefront carries from one step into the
+  // next (`car`, `tc`) is a loop-carried value of ITS loop alone: in the one loop both wavefronts pass through the loop's
+  // header, the helper's path had to define the values as well, and the register allocation joined the two paths' registers
+  // with up to 140 moves per step at the bottom of the loop (profiles/oct_step_boundary_resources.txt).
+  if constexpr (SPLIT_LOOP) {
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0) {
+      for (int it = 0; it < nsteps; ++it) step_body(std::integral_constant<int, 0>{}, it);
+    } else {
+      for (int it = 0; it < nsteps; ++it) step_body(std::integral_constant<int, 1>{}, it);
+    }
+  } else {
+    for (int it = 0; it < nsteps; ++it) step_body(std::integral_constant<int, 2>{}, it);
+  }
 #ifdef TDS_OCT_PROF
   if (threadIdx.x == 0 && blockIdx.x < 2048) {
     unsigned long long c_;

@@ -11,7 +11,8 @@ LDS latency it has nothing to cover with (~70 cycles per dependent read).  Two c
             their slots, in a second table.
 
 usage: tools/oct_isa_phases.py [kernel substring, default IddLb1ELi3 = f64 step-loop two-wavefront build]
-                               [--phases profiles/oct_lds_before.txt] [--src other/tds_oct.hip]"""
+                               [--phases profiles/oct_lds_before.txt] [--src other/tds_oct.hip]
+                               [--define TDS_OCT_CARRY=0 ...] [--asm marks.s: an assembly compiled before, not compiled here]"""
 import argparse
 import collections
 import os
@@ -45,13 +46,18 @@ def main():
     ap.add_argument("kernel", nargs="?", default="IddLb1ELi3")
     ap.add_argument("--phases", default=None)
     ap.add_argument("--src", default=os.path.join(CS, "tds_oct.hip"))
+    ap.add_argument("--define", action="append", default=[], metavar="NAME=VALUE")
+    ap.add_argument("--asm", default=None)
     args = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "oct_marks.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CS,
-                               "-Wno-unused-function", "-mllvm", "-disable-machine-licm", "-ffp-contract=on", "-DTDS_OCT_MARKS", "--cuda-device-only", "-S", "-o", out,
-                               args.src], stderr=subprocess.DEVNULL)
-        txt = open(out).read()
+    if args.asm:
+        txt = open(args.asm).read()
+    else:
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "oct_marks.s")
+            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CS,
+                                   "-Wno-unused-function", "-mllvm", "-disable-machine-licm", "-ffp-contract=on", "-DTDS_OCT_MARKS"] + ["-D" + d for d in args.define] +
+                                  ["--cuda-device-only", "-S", "-o", out, args.src], stderr=subprocess.DEVNULL)
+            txt = open(out).read()
     m = re.search(r"^(_Z\w*tds_oct_kernel" + args.kernel + r"\w*):.*?\n(.*?)^\.Lfunc_end\d+:", txt, re.S | re.M)
     body = m.group(2).split("\n")
     cur, counts = "(prologue)", collections.OrderedDict()
