@@ -688,6 +688,50 @@ int tds_hip_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int 
                                 const double *gs, double *s, double *gx0, double *gu, double *gtheta,
                                 int tape_cap, int *tape_len /* [n][steps], optional */);
 
+/* Closed-loop policy gradients: the trajectory of tds_hip_trajectory_jvp (records, gains, theta, every, n_rec, scope,
+   refusals and the f64-only rule as there) with EVERY step t = 0 .. steps - 1 taking its action from a policy network
+   evaluated on the state that enters the step, u_t = pi_W(obs_t), and the gradients of a loss on the recorded states
+   and on the actions through the dynamics AND the policy.
+     obs_t   [q | qd] entering step t (x0's for t = 0, the state after step t - 1 otherwise) with obs[0] = obs[1] = 0,
+             as the rollouts' policy kernels have it.  flags bit 0: step 0 sees the two entries raw (as tds_hip_rollout);
+             flags bit 1: every step does (fixed-base models, whose q[0], q[1] are joints).  Other bits: INVALID_ARG.
+     policy  [n][P] f64, per-environment parameters of the network num_layers, layer_sizes, activations, use_bias:
+             checks, limits and parameter order of tds_hip_set_policy_network, P as tds_hip_policy_num_parameters counts
+             it; num_layers = 0 is the default linear policy (action_dim x obs_dim weights, then biases).  The network
+             is an argument: the handle's own (tds_hip_set_policy_network) is neither read nor changed.
+   x0's action slots are not read.  A model with action_dim < 1 or whose record's action slots are not its actions
+   (n_act != action_dim) gives TDS_ERR_INVALID_ARG.
+   Cotangents: gs [n][n_rec][dof_q + dof_qd] on the recorded states and ga [n][steps][n_act] on the actions taken, each
+   optional; both NULL computes the primal only (s required; no tapes are recorded, no gradient is written).
+   Outputs: s [n][n_rec][dof_q + dof_qd] (optional where a cotangent is given), u [n][steps][n_act] the actions taken
+   (optional), gpolicy [n][P], gx0 [n][input_dim] (its action slots are returned as zero), gtheta [n][p] (where p > 0).
+   lambda_T = 0 and, t descending: the step's VJP as tds_hip_trajectory_vjp has it gives lambda_t's physical part and
+   ubar_t; ubar_t += ga_t; gpolicy += (d pi / d W)^T ubar_t; lambda_t += mask^T (d pi / d obs)^T ubar_t, the layers'
+   activations recomputed at obs_t.  The derivative is that of the algorithm as executed: ReLU and ELU take the
+   primal's branch, masked observation entries pass nothing back.  NaN and overflow rules per environment as
+   tds_hip_trajectory_vjp, gpolicy included.
+   Device pointers (params_host, the network's arrays: host).  The primal runs one step per launch with the policy's
+   forward kernel (one wavefront per environment) in front of each; backward, per chunk and window as
+   tds_hip_trajectory_vjp, one launch records the window's tapes, then each step is swept by a launch of its own with
+   the policy's backward kernel behind it.  Options traj_steps and traj_vjp_lanes apply as there and do not change the
+   results.  Work buffer: tds_hip_trajectory_vjp's plus the x0 copy, the action store and its adjoints
+   (n (input_dim + 2 (steps - 1) n_act) doubles); the primal-only call needs the state store, the primal lanes and the
+   x0 copy and action store alone. */
+int tds_hip_policy_trajectory_vjp(tds_hip_sim_t *sim, int n, int steps, int every, int flags, const void *x0_dev,
+                                  const void *policy_dev, int num_layers, const int *layer_sizes,
+                                  const int *activations, const int *use_bias, int p, const tds_param_t *params_host,
+                                  const void *theta_dev, const void *gs_dev, const void *ga_dev, void *s_dev,
+                                  void *u_dev, void *gpolicy_dev, void *gx0_dev, void *gtheta_dev);
+/* The same on the CPU (host arrays, needs no GPU; one tape at a time): the checker.  The network's arithmetic is the
+   device's statement with the device's summation tree (csrc/tds_policy.h).  tape_cap, tape_len and the return codes as
+   tds_hip_trajectory_vjp_host (tape_len is written only where a cotangent is given). */
+int tds_hip_policy_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int every, int flags,
+                                       const double *x0, const double *policy, int num_layers, const int *layer_sizes,
+                                       const int *activations, const int *use_bias, int p, const tds_param_t *params,
+                                       const double *theta, const double *gs, const double *ga, double *s, double *u,
+                                       double *gpolicy, double *gx0, double *gtheta, int tape_cap,
+                                       int *tape_len /* [n][steps], optional */);
+
 /* Batched dynamics queries (the reference's forward_kinematics, mass_matrix, forward_dynamics, point_jacobian of
    python/pytinydiffsim.inl:629-668 and inverse_dynamics of src/dynamics/inverse_dynamics.hpp, for n states at once).
    State q [n][dof_q], qd [n][dof_qd] (NULL: zero), f64 device pointers.  Scope and refusals are those of

@@ -366,3 +366,73 @@ def trajectory_fn(sim, steps: int, wrt=(), params=(), every: int = 1, mode: str 
         return fn.apply(z, theta, x0, u, sim, int(steps), int(every), ix, cache[key], spec)
 
     return f
+
+
+_PolicyTrajectoryFunction = None
+
+
+def _policy_trajectory_function():
+    global _PolicyTrajectoryFunction
+    if _PolicyTrajectoryFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class PolicyTrajectoryFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x0, policy, theta, sim, steps, every, net, params, obs_raw):
+                x = x0.detach()
+                pol = policy.detach()
+                th = None if theta is None else theta.detach()
+                ctx.shared_policy = pol.dim() == 1
+                ctx.shared_theta = th is not None and th.dim() == 1
+                ctx.has_theta = th is not None
+                ctx.sim, ctx.steps, ctx.every, ctx.net, ctx.params, ctx.obs_raw = sim, steps, every, net, params, obs_raw
+                ctx.save_for_backward(*(t for t in (x, pol, th) if t is not None))
+                return sim.policy_trajectory(x, pol, steps, every, *net, params=params, theta=th, obs_raw=obs_raw)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_s, grad_u):
+                saved = list(ctx.saved_tensors)
+                x, pol = saved[0], saved[1]
+                th = saved[2] if ctx.has_theta else None
+                gs = None if grad_s is None else grad_s.to(x.dtype).contiguous()
+                ga = None if grad_u is None else grad_u.to(x.dtype).contiguous()
+                if gs is None and ga is None:
+                    return (None,) * 9
+                _, _, gpol, gx0, gth = ctx.sim.policy_trajectory_vjp(
+                    x, pol, gs, ctx.steps, ctx.every, ga, *ctx.net, params=ctx.params, theta=th, obs_raw=ctx.obs_raw)
+                if ctx.shared_policy:  # one policy for every environment: its gradient sums over them
+                    gpol = gpol.sum(0)
+                if ctx.shared_theta:
+                    gth = gth.sum(0)
+                return (gx0, gpol, (gth if ctx.has_theta else None)) + (None,) * 6
+
+        _PolicyTrajectoryFunction = PolicyTrajectoryFunction
+    return _PolicyTrajectoryFunction
+
+
+def policy_trajectory_fn(sim, steps: int, layer_sizes=None, activations=None, use_bias=None, params=(), every: int = 1,
+                         obs_raw: bool = False):
+    """(x0, policy, theta=None) -> (s, u): the closed-loop trajectory u_t = pi(obs_t) of HipSim.policy_trajectory (a
+    HipSim, f64): the states s [N, n_rec, nq + nd] after steps every, 2 every, .., steps and the actions taken u
+    [N, steps, n_act], differentiable in policy, theta and x0 through the dynamics and the policy network in one
+    HipSim.policy_trajectory_vjp per backward pass.  Losses and rewards are the caller's torch code on s and u.
+
+    policy [P] shared by every environment (its gradient is summed over them) or [N, P]; the network as for
+    hip_backend.policy_network_spec (layer_sizes None: the linear policy); params and theta as for trajectory_fn.  x0's
+    action slots are not read and get a zero gradient; its gain slots get theirs."""
+    from . import hip_backend
+
+    p = len(params)
+    sel = hip_backend.param_spec(params)
+    spec = [sel[j] for j in range(p)]
+    net = (layer_sizes, activations, use_bias)
+
+    def f(x0, policy, theta=None):
+        if theta is not None and p == 0:
+            raise ValueError("policy_trajectory_fn: theta given but no params selected")
+        return _policy_trajectory_function().apply(x0, policy, theta, sim, int(steps), int(every), net, spec,
+                                                   bool(obs_raw))
+
+    return f

@@ -1,7 +1,9 @@
 // tds_traj_vjp.hip — reverse-mode derivatives of articulated-body trajectories on gfx950: the trajectory of
 // tds_traj.hip (forward_zero chained over `steps` steps, states recorded every `every` steps), one cotangent gs on the
 // recorded states, and its gradients in x0, in the actions u of steps 1 .. and in theta.  C ABI
-// tds_hip_trajectory_vjp / tds_hip_trajectory_vjp_host (include/tds_hip.h).
+// tds_hip_trajectory_vjp / tds_hip_trajectory_vjp_host (include/tds_hip.h).  The closed-loop form, every step's action
+// taken from a policy network and the gradient in its parameters (tds_hip_policy_trajectory_vjp / _host), is
+// orchestrated at the end of this file over the same kernels and the policy kernels of tds_policy_grad.hip.
 //
 // Phase 1, the primal: the double item of tds_traj.hip (tds_traj_advance<B, 0>, every = 1) writes the state after every
 // step into a state store [n][steps][nsd] in the work buffer; s is copied out of it.
@@ -24,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include "tds_policy.h"
 #include "tds_traj.h"
 #include "tds_vjp_param.h"
 
@@ -428,6 +431,278 @@ TdsTrajVjpArgs tds_traj_vjp_args(const tds_model_t *m, const tds_model_t *m_arg,
   return a;
 }
 
+
+// ================================================================ closed loop: u_t = pi_W(obs(s_t))
+// tds_hip_policy_trajectory_vjp: the trajectory above with every step's action taken from the policy network
+// (tds_policy.h) on the state that enters the step.  The policy's forward kernel runs in front of every primal step
+// and writes the action where the open-loop kernels read it (t = 0: the action slots of a copy of x0; t > 0: row t - 1
+// of an action store), so the primal, recording and sweep kernels above see an ordinary trajectory.  Backward, the
+// recording launches stay (W steps side by side: a record depends on the primal alone); the sweeps go one step per
+// launch, with the policy's backward kernel behind each: it reads ubar_t where the sweep scattered it (gu's row t - 1,
+// or gx0's action slots at t = 0, which it then zeroes), adds ga_t, accumulates gpolicy and adds the observation
+// adjoint to lambda (t = 0: to gx0's state part).
+
+struct TdsPolicyTrajArgs {
+  TdsPolicyNet nn;
+  const double *x0, *policy, *ga;  // the caller's x0, [n][P], [n][steps][nact] or NULL
+  double *u_out, *gpolicy;         // [n][steps][nact] or NULL, [n][P]
+  int flags;
+  bool grad;                       // a cotangent was given
+};
+
+inline int tds_policy_traj_raw(const TdsPolicyTrajArgs &pa, int t) {
+  return ((pa.flags & 2) || ((pa.flags & 1) && t == 0)) ? 1 : 0;
+}
+
+// what the closed loop adds to the work buffer, behind the sibling's: the x0 copy, the action store, its adjoints and,
+// where only ga is given, a zero gs
+struct TdsPolicyTrajExtra {
+  size_t xc, us, gu, gz, total;
+  TdsPolicyTrajExtra(size_t base, int n, int steps, int n_rec, int nsd, int nin, int nact, bool grad, bool zero_gs) {
+    const size_t rows = (size_t)n * (steps > 1 ? steps - 1 : 1) * nact * sizeof(double);
+    xc = tds_vjp_align(base);
+    us = xc + tds_vjp_align((size_t)n * nin * sizeof(double));
+    gu = us + tds_vjp_align(rows);
+    gz = gu + (grad ? tds_vjp_align(rows) : 0);
+    total = gz + (zero_gs ? tds_vjp_align((size_t)n * n_rec * nsd * sizeof(double)) : 0);
+  }
+};
+
+template <class B>
+int tds_policy_traj_run(tds_hip_sim *s, TdsTrajVjpArgs a, const TdsPolicyTrajArgs &pa, const tds_param_t *params_host,
+                        double *s_out) {
+  using Lane = TdsVjpParamLane<B>;
+  const int n = a.n, steps = a.steps, nsd = a.nsd, nact = a.nact, nin = s->model.input_dim;
+  const int P = pa.nn.nw + pa.nn.nb;
+  const TdsTrajVjpPlan pl = tds_traj_vjp_plan(s, n, steps);
+  const TdsTrajVjpLayout<B> lay(pl, n, steps, nsd, nin, a.p);
+  const bool zero_gs = pa.grad && !a.gs;
+  const TdsPolicyTrajExtra ex(pa.grad ? lay.total : lay.p1_end, n, steps, a.n_rec, nsd, nin, nact, pa.grad, zero_gs);
+  int rc = tds_work_buffer(s, ex.total);
+  if (rc) return rc;
+  char *ws = (char *)s->d_diff_tmp;
+  tds_param_t *d_sel = (tds_param_t *)(ws + 256);
+  if (a.p > 0) {  // a blocking copy: earlier calls on the stream may still read the work buffer
+    TDS_HIP_TRY(hipStreamSynchronize(s->stream));
+    TDS_HIP_TRY(hipMemcpy(d_sel, params_host, (size_t)a.p * sizeof(tds_param_t), hipMemcpyHostToDevice));
+  }
+  a.params = d_sel;
+  a.overflow = (int *)ws;
+  double *store = (double *)(ws + lay.store), *lam = (double *)(ws + lay.lam);
+  double *xc = (double *)(ws + ex.xc), *us = (double *)(ws + ex.us), *gu = (double *)(ws + ex.gu);
+  int *bad = (int *)(ws + lay.bad), *over = (int *)(ws + lay.over);
+  const long long urow = (long long)(steps > 1 ? steps - 1 : 1) * nact;  // an environment's doubles of us and gu
+  a.store = store, a.x0 = xc, a.u = steps > 1 ? us : nullptr, a.gu = gu;
+  hipStream_t st = s->stream;
+  TDS_HIP_TRY(hipMemsetAsync(a.overflow, 0, sizeof(int), st));
+  TDS_HIP_TRY(hipMemsetAsync(over, 0, lay.ph - lay.over, st));
+  TDS_HIP_TRY(hipMemcpyAsync(xc, pa.x0, (size_t)n * nin * sizeof(double), hipMemcpyDeviceToDevice, st));
+
+  // the primal: one step per launch, the policy in front of each
+  {
+    TdsTrajArgs ta = tds_traj_args(&s->model, a.m, n, steps, 1, xc, us, a.p, a.theta, 0, nullptr, store, nullptr);
+    ta.a.params = d_sel;
+    ta.items = n;
+    ta.carry = (double *)(ws + lay.p1_carry);
+    const unsigned blocks = (unsigned)((lay.p1_lanes + 63) / 64);
+    for (int t = 0; t < steps; ++t) {
+      TdsPolicyFwdArgs f;
+      f.policy = pa.policy, f.n = n, f.raw = tds_policy_traj_raw(pa, t);
+      f.obs = t > 0 ? store + (size_t)(t - 1) * nsd : xc, f.obs_stride = t > 0 ? (long long)steps * nsd : nin;
+      f.dst = t > 0 ? us + (size_t)(t - 1) * nact : xc + nsd, f.dst_stride = t > 0 ? urow : nin;
+      f.out = pa.u_out ? pa.u_out + (size_t)t * nact : nullptr, f.out_stride = (long long)steps * nact;
+      TDS_HIP_TRY((hipError_t)tds_policy_fwd_launch(st, pa.nn, f));
+      hipLaunchKernelGGL((tds_traj_vjp_primal_kernel<B>), dim3(blocks), dim3(64), 0, st, ta,
+                         (TdsTrajLane<B, 0> *)(ws + lay.ph), lay.p1_lanes, t, t + 1, bad);
+      TDS_HIP_TRY(hipGetLastError());
+    }
+    if (s_out) {
+      const long long items = (long long)n * a.n_rec;
+      hipLaunchKernelGGL(tds_traj_vjp_select_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, store,
+                         s_out, items, steps, a.every, a.n_rec, nsd);
+      TDS_HIP_TRY(hipGetLastError());
+    }
+  }
+  if (!pa.grad) return TDS_OK;
+
+  TDS_HIP_TRY(hipMemsetAsync(a.gx0, 0, (size_t)n * nin * sizeof(double), st));
+  if (a.p > 0) TDS_HIP_TRY(hipMemsetAsync(a.gtheta, 0, (size_t)n * a.p * sizeof(double), st));
+  TDS_HIP_TRY(hipMemsetAsync(pa.gpolicy, 0, (size_t)n * P * sizeof(double), st));
+  TDS_HIP_TRY(hipMemsetAsync(gu, 0, ex.gz - ex.gu, st));
+  if (zero_gs) {
+    TDS_HIP_TRY(hipMemsetAsync(ws + ex.gz, 0, ex.total - ex.gz, st));
+    a.gs = (const double *)(ws + ex.gz);
+  }
+  TDS_HIP_TRY(hipMemsetAsync(ws + lay.adj, 0, lay.total - lay.adj, st));
+  constexpr long long cap = Lane::cap;
+  Lane *lanes = (Lane *)(ws + lay.lanes);
+  int *lens = (int *)(ws + lay.lens), *yidx = (int *)(ws + lay.yidx);
+  TdsRevIdx *ix = (TdsRevIdx *)(ws + lay.ix);
+  TdsRevPart *pd = (TdsRevPart *)(ws + lay.pd);
+  const int n_win = (steps + pl.W - 1) / pl.W;
+  for (long long e0 = 0; e0 < n; e0 += pl.chunk) {
+    const long long left = ((long long)n - e0 + 63) / 64;
+    const int nblk = left < pl.nblk ? (int)left : pl.nblk;
+    const long long envs = (long long)n - e0 < (long long)nblk * 64 ? (long long)n - e0 : (long long)nblk * 64;
+    for (int w = n_win - 1; w >= 0; --w) {
+      const int t0 = w * pl.W, t1 = t0 + pl.W < steps ? t0 + pl.W : steps;
+      hipLaunchKernelGGL((tds_traj_vjp_record_kernel<B>), dim3((unsigned)((t1 - t0) * nblk)), dim3(64), 0, st, a,
+                         (int)e0, nblk, t0, bad, over, lanes, lens, yidx, ix, pd);
+      TDS_HIP_TRY(hipGetLastError());
+      for (int t = t1 - 1; t >= t0; --t) {
+        // the sweep of step t alone: its tapes begin (t - t0) nblk wavefronts into the window's
+        const long long w0 = (long long)(t - t0) * nblk;
+        hipLaunchKernelGGL((tds_traj_vjp_sweep_kernel<B>), dim3((unsigned)nblk), dim3(64), 0, st, a, (int)e0, nblk, t,
+                           t + 1, bad, lens + w0 * 64, yidx + w0 * nsd * 64, ix + w0 * cap * 64, pd + w0 * cap * 64,
+                           (double *)(ws + lay.adj), lam);
+        TDS_HIP_TRY(hipGetLastError());
+        TdsPolicyBwdArgs b;
+        b.policy = pa.policy, b.gpolicy = pa.gpolicy, b.bad = bad, b.e0 = (int)e0, b.count = (int)envs;
+        b.raw = tds_policy_traj_raw(pa, t), b.zero_ubar = t == 0;
+        b.obs = t > 0 ? store + (size_t)(t - 1) * nsd : xc, b.obs_stride = t > 0 ? (long long)steps * nsd : nin;
+        b.ubar = t > 0 ? gu + (size_t)(t - 1) * nact : a.gx0 + nsd, b.ubar_stride = t > 0 ? urow : nin;
+        b.ga = pa.ga ? pa.ga + (size_t)t * nact : nullptr, b.ga_stride = (long long)steps * nact;
+        b.lam = t > 0 ? lam : a.gx0, b.lam_entry = t > 0 ? n : 1, b.lam_env = t > 0 ? 1 : nin;
+        TDS_HIP_TRY((hipError_t)tds_policy_bwd_launch(st, pa.nn, b));
+      }
+    }
+  }
+  hipLaunchKernelGGL(tds_traj_vjp_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, bad, over);
+  TDS_HIP_TRY(hipGetLastError());
+  TDS_HIP_TRY((hipError_t)tds_policy_nan_launch(st, pa.gpolicy, P, bad, over, n));
+  int overflow = 0;  // the call reports an overflow: it waits for its launches
+  TDS_HIP_TRY(hipMemcpyAsync(&overflow, a.overflow, sizeof(int), hipMemcpyDeviceToHost, st));
+  TDS_HIP_TRY(hipStreamSynchronize(st));
+  if (overflow)
+    return fail(TDS_ERR_UNSUPPORTED,
+                "trajectory VJP: an environment's tape exceeds the capacity of its model class%s");
+  return TDS_OK;
+}
+
+// the host instantiation: per environment the closed-loop primal step by step, then one tape at a time, t descending,
+// the network's backward pass behind each sweep
+template <class B>
+int tds_policy_traj_host_run(TdsTrajVjpArgs a, const TdsPolicyTrajArgs &pa, double *s_out, int tape_cap,
+                             int *tape_len) {
+  using Lane = TdsVjpParamLane<B>;
+  const tds_model_t *m = a.m;
+  const int n = a.n, steps = a.steps, nsd = a.nsd, nact = a.nact, nin = m->input_dim, nall = nin + a.p;
+  const int P = pa.nn.nw + pa.nn.nb;
+  const int cap = tape_cap > 0 ? tape_cap : Lane::cap;
+  const size_t urow = (size_t)(steps > 1 ? steps - 1 : 1) * nact;
+  std::vector<double> store((size_t)n * steps * nsd), lam(nsd), adj(pa.grad ? (size_t)nall + cap : 0);
+  std::vector<double> xc(pa.x0, pa.x0 + (size_t)n * nin), us(n * urow), gu(n * urow, 0.0);
+  std::vector<double> carry((size_t)tds_traj_ncarry<0>(nsd) * n), gz;
+  std::vector<double> act(kPolicyActs), dact(kPolicyActs), del(2 * TDS_NN_MAX_UNITS);
+  std::vector<TdsTrajLane<B, 0>> Ly(1);
+  std::vector<Lane> L(pa.grad ? 1 : 0);
+  std::vector<TdsRevIdx> ix(pa.grad ? cap : 0);
+  std::vector<TdsRevPart> pd(pa.grad ? cap : 0);
+  std::vector<int> yi(nsd);
+  if (pa.grad && !a.gs) {
+    gz.assign((size_t)n * a.n_rec * nsd, 0.0);
+    a.gs = gz.data();
+  }
+  a.store = store.data(), a.x0 = xc.data(), a.u = steps > 1 ? us.data() : nullptr, a.gu = gu.data();
+  TdsTrajArgs ta = tds_traj_args(m, m, n, steps, 1, xc.data(), us.data(), a.p, a.theta, 0, nullptr, store.data(),
+                                 nullptr);
+  ta.a.params = a.params;
+  ta.items = n;
+  ta.carry = carry.data();
+  const TdsRevTape tp = {ix.data(), pd.data(), adj.data(), 1, cap, nall};
+  if (pa.grad) tds_rev_tape() = tp;
+  auto obs_of = [&](int e, int t) {
+    return t > 0 ? store.data() + ((size_t)e * steps + (t - 1)) * nsd : xc.data() + (size_t)e * nin;
+  };
+  int bad = 0, over = 0;
+  for (int e = 0; e < n; ++e) {
+    const double *W = pa.policy + (size_t)e * P;
+    int bad_e = 0;
+    for (int t = 0; t < steps; ++t) {
+      tds_policy_forward(pa.nn, W, obs_of(e, t), tds_policy_traj_raw(pa, t), act.data(), nullptr);
+      const double *out = act.data() + (pa.nn.n - 1) * TDS_NN_MAX_UNITS;
+      double *dst = t > 0 ? us.data() + e * urow + (size_t)(t - 1) * nact : xc.data() + (size_t)e * nin + nsd;
+      std::copy_n(out, nact, dst);
+      if (pa.u_out) std::copy_n(out, nact, pa.u_out + ((size_t)e * steps + t) * nact);
+      bad_e = tds_traj_advance<B, 0>(ta, Ly[0], e, t, t + 1);
+    }
+    if (s_out)
+      for (int r = 0; r < a.n_rec; ++r)
+        std::copy_n(&store[((size_t)e * steps + (size_t)(r + 1) * a.every - 1) * nsd], nsd,
+                    s_out + ((size_t)e * a.n_rec + r) * nsd);
+    bad |= bad_e;
+    if (!pa.grad) continue;
+    double *gx = a.gx0 + (size_t)e * nin, *gP = pa.gpolicy + (size_t)e * P;
+    std::fill_n(gx, nin, 0.0);
+    std::fill_n(a.gtheta + (size_t)e * a.p, a.p, 0.0);
+    std::fill_n(gP, P, 0.0);
+    std::fill(lam.begin(), lam.end(), 0.0);
+    int over_e = 0;
+    for (int t = steps - 1; t >= 0 && !bad_e; --t) {
+      tds_traj_vjp_record<B>(a, L[0], e, t);
+      const int len = tds_rev_cursor(0);
+      if (tape_len) tape_len[(size_t)e * steps + t] = len > cap ? -1 : len;
+      over_e |= len > cap;
+      if (over_e) continue;  // the remaining steps are recorded for their lengths only
+      for (int i = 0; i < nsd; ++i) yi[i] = L[0].y[i].i;
+      std::fill(adj.begin(), adj.begin() + nall + len, 0.0);
+      tds_traj_vjp_seed(a, e, t, yi.data(), 1, lam.data(), 1, adj.data(), 1);
+      tds_rev_sweep_host(tp, len);
+      tds_traj_vjp_scatter(a, e, t, adj.data(), 1, lam.data(), 1);
+      // the network at obs_t: ubar_t (+ ga_t) down the layers
+      const int raw = tds_policy_traj_raw(pa, t);
+      tds_policy_forward(pa.nn, W, obs_of(e, t), raw, act.data(), dact.data());
+      double *ub = t > 0 ? gu.data() + e * urow + (size_t)(t - 1) * nact : gx + nsd;
+      for (int i = 0; i < nact; ++i) {
+        del[i] = ub[i] + (pa.ga ? pa.ga[((size_t)e * steps + t) * nact + i] : 0.0);
+        if (t == 0) ub[i] = 0.0;
+      }
+      const double *gobs = tds_policy_backward(pa.nn, W, act.data(), dact.data(), del.data(),
+                                               del.data() + TDS_NN_MAX_UNITS, gP);
+      double *dstl = t > 0 ? lam.data() : gx;
+      for (int o = 0; o < nsd; ++o)
+        if (o >= 2 || raw) dstl[o] += gobs[o];
+    }
+    if (bad_e && tape_len) std::fill_n(tape_len + (size_t)e * steps, steps, 0);
+    if (bad_e || over_e) {
+      tds_traj_vjp_nan(a, e);
+      std::fill_n(gP, P, __builtin_nan(""));
+    }
+    over |= over_e;
+  }
+  if (pa.grad) tds_rev_tape() = TdsRevTape{};
+  if (over) return fail(TDS_ERR_UNSUPPORTED, "trajectory VJP: an environment's tape exceeds the capacity%s");
+  if (bad) return fail(TDS_ERR_INVALID_ARG, "step Jacobians: joint-space inertia not positive definite%s");
+  return TDS_OK;
+}
+
+// the argument checks of both entry points, up to the model's own
+int tds_policy_traj_check_args(const char *fn, int n, int steps, int every, int p, const void *x0, const void *policy,
+                               const void *params, const void *gs, const void *ga, const void *s, const void *gpolicy,
+                               const void *gx0, const void *gtheta) {
+  const bool grad = gs || ga;
+  int rc = tds_traj_check_args(fn, n, steps, every, grad ? 1 : 0, p, x0, params, grad ? gx0 : nullptr, s,
+                               grad ? gpolicy : nullptr);
+  if (rc) return rc;
+  if (!policy || (grad && p > 0 && !gtheta)) return fail(TDS_ERR_INVALID_ARG, fn, ": NULL or empty argument");
+  return TDS_OK;
+}
+
+// the model's actions and the network, once the model itself has passed
+int tds_policy_traj_net(const char *fn, const tds_model_t *m, int num_layers, const int *layer_sizes,
+                        const int *activations, const int *use_bias, int flags, TdsPolicyNet *nn) {
+  const int nsd = m->dof_q + m->dof_qd;
+  const int nact = m->input_dim - nsd - (m->step_mode == TDS_STEP_LOCOMOTION ? 3 : 0);
+  if (m->action_dim < 1 || nact != m->action_dim)
+    return fail(TDS_ERR_INVALID_ARG, fn, ": the model has no actions, or its record's action slots are not its actions");
+  if (flags & ~3) return fail(TDS_ERR_INVALID_ARG, fn, ": unknown flags");
+  if (const char *why = tds_policy_net_make(nsd, m->action_dim, num_layers, layer_sizes, activations, use_bias, nn)) {
+    snprintf(tds_internal::g_err, sizeof(tds_internal::g_err), "%s", why);
+    return TDS_ERR_INVALID_ARG;
+  }
+  return TDS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +740,54 @@ int tds_hip_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int 
   const TdsTrajVjpArgs a = tds_traj_vjp_args(model, model, n, steps, every, x0, u, p, params, theta, gs, gx0, gu, gtheta);
   return tds_with_bound(cls, [&](auto b) {
     return tds_traj_vjp_host_run<typename decltype(b)::type>(a, s, tape_cap, tape_len);
+  });
+}
+
+int tds_hip_policy_trajectory_vjp(tds_hip_sim_t *s, int n, int steps, int every, int flags, const void *x0_dev,
+                                  const void *policy_dev, int num_layers, const int *layer_sizes,
+                                  const int *activations, const int *use_bias, int p, const tds_param_t *params_host,
+                                  const void *theta_dev, const void *gs_dev, const void *ga_dev, void *s_dev,
+                                  void *u_dev, void *gpolicy_dev, void *gx0_dev, void *gtheta_dev) {
+  const char *fn = "tds_hip_policy_trajectory_vjp%s";
+  if (!s) return fail(TDS_ERR_INVALID_ARG, fn, ": NULL or empty argument");
+  int rc = tds_policy_traj_check_args(fn, n, steps, every, p, x0_dev, policy_dev, params_host, gs_dev, ga_dev, s_dev,
+                                      gpolicy_dev, gx0_dev, gtheta_dev);
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  int cls;
+  if ((rc = tds_diff_prepare(s, &cls))) return rc;
+  if ((rc = tds_param_check_sel(&s->model, p, params_host))) return rc;
+  TdsPolicyTrajArgs pa;
+  if ((rc = tds_policy_traj_net(fn, &s->model, num_layers, layer_sizes, activations, use_bias, flags, &pa.nn))) return rc;
+  pa.x0 = (const double *)x0_dev, pa.policy = (const double *)policy_dev, pa.ga = (const double *)ga_dev;
+  pa.u_out = (double *)u_dev, pa.gpolicy = (double *)gpolicy_dev, pa.flags = flags, pa.grad = gs_dev || ga_dev;
+  const TdsTrajVjpArgs a = tds_traj_vjp_args(&s->model, (const tds_model_t *)s->d_diff_model, n, steps, every,
+                                             (const double *)x0_dev, nullptr, p, nullptr, (const double *)theta_dev,
+                                             (const double *)gs_dev, (double *)gx0_dev, nullptr, (double *)gtheta_dev);
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_policy_traj_run<typename decltype(b)::type>(s, a, pa, params_host, (double *)s_dev);
+  });
+}
+
+int tds_hip_policy_trajectory_vjp_host(const tds_model_t *model, int n, int steps, int every, int flags,
+                                       const double *x0, const double *policy, int num_layers, const int *layer_sizes,
+                                       const int *activations, const int *use_bias, int p, const tds_param_t *params,
+                                       const double *theta, const double *gs, const double *ga, double *s, double *u,
+                                       double *gpolicy, double *gx0, double *gtheta, int tape_cap, int *tape_len) {
+  const char *fn = "tds_hip_policy_trajectory_vjp_host%s";
+  if (!model) return fail(TDS_ERR_INVALID_ARG, fn, ": NULL or empty argument");
+  int rc = tds_policy_traj_check_args(fn, n, steps, every, p, x0, policy, params, gs, ga, s, gpolicy, gx0, gtheta);
+  if (rc) return rc;
+  int cls;
+  if ((rc = tds_param_host_prepare(model, p, params, &cls))) return rc;
+  TdsPolicyTrajArgs pa;
+  if ((rc = tds_policy_traj_net(fn, model, num_layers, layer_sizes, activations, use_bias, flags, &pa.nn))) return rc;
+  pa.x0 = x0, pa.policy = policy, pa.ga = ga, pa.u_out = u, pa.gpolicy = gpolicy, pa.flags = flags;
+  pa.grad = gs || ga;
+  const TdsTrajVjpArgs a = tds_traj_vjp_args(model, model, n, steps, every, x0, nullptr, p, params, theta, gs, gx0,
+                                             nullptr, gtheta);
+  return tds_with_bound(cls, [&](auto b) {
+    return tds_policy_traj_host_run<typename decltype(b)::type>(a, pa, s, tape_cap, tape_len);
   });
 }
 

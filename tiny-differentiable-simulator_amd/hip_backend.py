@@ -139,6 +139,10 @@ def lib():
             [C.c_void_p] * 6
         L.tds_hip_trajectory_vjp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
             [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.tds_hip_policy_trajectory_vjp.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + \
+            [C.c_void_p] * 3 + [C.c_int, PP] + [C.c_void_p] * 8
+        L.tds_hip_policy_trajectory_vjp_host.argtypes = [P] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + \
+            [C.c_void_p] * 3 + [C.c_int, PP] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         RP = C.POINTER(_model.RbModel)
         L.tds_rb_params_get.argtypes = [RP, C.c_int, PP, C.c_void_p]
         L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
@@ -369,6 +373,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
     "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
     "tds_hip_trajectory_vjp", "tds_hip_trajectory_vjp_host",
+    "tds_hip_policy_trajectory_vjp", "tds_hip_policy_trajectory_vjp_host",
     "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
@@ -854,6 +859,86 @@ def trajectory_vjp_host(m: _model.Model, x0, gs, steps: int, every: int = 1, u=N
                                              gx0.ctypes.data, gu.ctypes.data, gth.ctypes.data, int(tape_cap),
                                              lens.ctypes.data if tape_len else None))
     return (s, gx0, gu, gth, lens) if tape_len else (s, gx0, gu, gth)
+
+
+def policy_network_spec(m: _model.Model, layer_sizes=None, activations=None, use_bias=None):
+    """(num_layers, layer_sizes, activations, use_bias, P): a policy network as the C ABI takes it (int32 arrays, kept
+    alive by the caller) and its parameter count; layer_sizes None: the default linear policy (num_layers 0).
+    activations: one TDS_NN_ACT_* per layer after the input (default: identity); use_bias: one flag per layer, the input
+    layer's included (default: every layer but the input)."""
+    import numpy as np
+
+    od, ad = m.dof_q + m.dof_qd, m.action_dim
+    if layer_sizes is None:
+        return 0, None, None, None, ad * od + ad
+    ls = np.ascontiguousarray(layer_sizes, dtype=np.int32)
+    nl = int(ls.shape[0])
+    act = np.full(max(nl - 1, 1), -1, dtype=np.int32) if activations is None else \
+        np.ascontiguousarray(activations, dtype=np.int32)
+    ub = np.array([0] + [1] * (nl - 1), dtype=np.int32) if use_bias is None else \
+        np.ascontiguousarray(use_bias, dtype=np.int32)
+    if act.shape[0] < nl - 1 or ub.shape[0] != nl:
+        raise ValueError(f"policy network: {nl} layers need {nl - 1} activations and {nl} bias flags")
+    nw = int(sum(int(ls[i - 1]) * int(ls[i]) for i in range(1, nl)))
+    nb = int(sum(int(ls[i]) for i in range(nl) if ub[i]))
+    return nl, ls, act, ub, nw + nb
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def policy_trajectory_vjp_host(m: _model.Model, x0, policy, gs, steps: int, every: int = 1, ga=None, layer_sizes=None,
+                               activations=None, use_bias=None, params=(), theta=None, first_obs_raw: bool = False,
+                               obs_raw: bool = False, tape_cap: int = 0, tape_len: bool = False):
+    """Closed-loop policy gradients on the CPU (tds_hip_policy_trajectory_vjp_host; the checker of
+    HipSim.policy_trajectory_vjp, needs no GPU).
+
+    x0 [N, input_dim] (its action slots are not read), policy [P] (every environment) or [N, P], gs None or
+    [N, n_rec, nq + nd], ga None or [N, steps, n_act]; the network as for policy_network_spec; params and theta as for
+    trajectory_vjp_host.  Returns (s, u, gpolicy, gx0, gtheta), with tape_len also the entries each step recorded
+    [N, steps]; gs and ga both None: (s, u), the primal alone."""
+    import numpy as np
+
+    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x0.shape[0], len(params)
+    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
+    nl, ls, act, ub, P = policy_network_spec(m, layer_sizes, activations, use_bias)
+    pol = np.asarray(policy, dtype=np.float64)
+    if pol.ndim == 1:
+        pol = np.broadcast_to(pol, (n, pol.shape[0]))
+    if pol.shape != (n, P):
+        raise ValueError(f"policy: expected [{P}] or [{n}, {P}], got {tuple(np.shape(policy))}")
+    pol = np.ascontiguousarray(pol)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    T = max(int(steps), 0)
+    if gs is not None:
+        gs = np.ascontiguousarray(gs, dtype=np.float64)
+        if n_rec > 0 and gs.shape != (n, n_rec, nsd):
+            raise ValueError(f"gs: expected [{n}, {n_rec}, {nsd}], got {tuple(gs.shape)}")
+    if ga is not None:
+        ga = np.ascontiguousarray(ga, dtype=np.float64)
+        if T > 0 and ga.shape != (n, T, n_act):
+            raise ValueError(f"ga: expected [{n}, {T}, {n_act}], got {tuple(ga.shape)}")
+    grad = gs is not None or ga is not None
+    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
+    u = np.zeros((n, max(T, 1), max(n_act, 1)), dtype=np.float64)
+    gpol = np.zeros((n, P), dtype=np.float64)
+    gx0 = np.zeros((n, m.input_dim), dtype=np.float64)
+    gth = np.zeros((n, max(p, 1)), dtype=np.float64)
+    lens = np.zeros((n, max(T, 1)), dtype=np.int32) if tape_len else None
+    flags = (1 if first_obs_raw else 0) | (2 if obs_raw else 0)
+    _check(lib().tds_hip_policy_trajectory_vjp_host(
+        C.byref(m), n, int(steps), int(every), flags, x0.ctypes.data, pol.ctypes.data, nl, _np_ptr(ls), _np_ptr(act),
+        _np_ptr(ub), p, sel, _np_ptr(th), _np_ptr(gs), _np_ptr(ga), s.ctypes.data, u.ctypes.data,
+        gpol.ctypes.data if grad else None, gx0.ctypes.data if grad else None, gth.ctypes.data if grad else None,
+        int(tape_cap), _np_ptr(lens)))
+    u = u[:, :T, :max(n_act, 0)]
+    if not grad:
+        return s, u
+    out = (s, u, gpol, gx0, gth[:, :p])
+    return out + (lens,) if tape_len else out
 
 
 def trajectory_directions(input_dim: int, wrt, p: int = 0, device=None):
@@ -1385,6 +1470,63 @@ class HipSim:
                                             C.c_void_p(gs.data_ptr()), C.c_void_p(s.data_ptr()),
                                             C.c_void_p(gx0.data_ptr()), ptr(gu), ptr(gth)))
         return s, gx0, gu, gth
+
+    # -- closed loop: the policy network between the steps, gradients through dynamics and policy -----------------
+    def policy_trajectory_vjp(self, x0, policy, gs, steps: int, every: int = 1, ga=None, layer_sizes=None,
+                              activations=None, use_bias=None, params=(), theta=None, first_obs_raw: bool = False,
+                              obs_raw: bool = False):
+        """(s, u, gpolicy, gx0, gtheta) of the closed-loop trajectory u_t = pi(obs_t) (tds_hip_policy_trajectory_vjp):
+        the recorded states s [N, n_rec, nq + nd], the actions taken u [N, steps, n_act], and the gradients of
+        <gs, s> + <ga, u> in the policy's parameters [N, P], in x0 [N, input_dim] (action slots zero) and in theta
+        [N, p].  policy [P] (every environment) or [N, P]; the network as for hip_backend.policy_network_spec
+        (layer_sizes None: the linear policy); gs [N, n_rec, nq + nd] or None, ga [N, steps, n_act] or None (both None:
+        the primal alone, the gradients come back as None).  obs_raw: the policy sees obs[0], obs[1] as they are at
+        every step (fixed-base models), first_obs_raw: at step 0 only.  The call waits for its kernels where a
+        cotangent is given.  f64 handles only."""
+        import torch
+
+        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
+        x0 = x0.contiguous()
+        n, p = x0.shape[0], len(params)
+        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
+        nl, ls, act, ub, P = policy_network_spec(self.model, layer_sizes, activations, use_bias)
+        assert policy.is_cuda and policy.dtype == torch.float64
+        if policy.dim() == 1:
+            policy = policy.unsqueeze(0).expand(n, -1)
+        assert tuple(policy.shape) == (n, P), (tuple(policy.shape), n, P)
+        policy = policy.contiguous()
+        sel = param_spec(params)
+        th = None if theta is None else self._theta(theta, n, p)
+        T = max(int(steps), 0)
+        dev = x0.device
+        if gs is not None:
+            gs = gs.contiguous()
+            assert gs.is_cuda and gs.dtype == torch.float64
+            assert n_rec < 1 or tuple(gs.shape) == (n, n_rec, nsd), (tuple(gs.shape), n, n_rec, nsd)
+        if ga is not None:
+            ga = ga.contiguous()
+            assert ga.is_cuda and ga.dtype == torch.float64
+            assert T < 1 or tuple(ga.shape) == (n, T, n_act), (tuple(ga.shape), n, T, n_act)
+        grad = gs is not None or ga is not None
+        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=dev)
+        u = torch.empty((n, max(T, 1), max(n_act, 1)), dtype=torch.float64, device=dev)
+        gpol = torch.empty((n, P), dtype=torch.float64, device=dev) if grad else None
+        gx0 = torch.empty((n, self.input_dim), dtype=torch.float64, device=dev) if grad else None
+        gth = torch.empty((n, max(p, 1)), dtype=torch.float64, device=dev) if grad else None
+        # (pointers of empty tensors may be NULL: a model without actions is refused by the library, not here)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if t.numel() else s.data_ptr())  # noqa: E731
+        flags = (1 if first_obs_raw else 0) | (2 if obs_raw else 0)
+        _check(lib().tds_hip_policy_trajectory_vjp(
+            self.h, n, int(steps), int(every), flags, ptr(x0), ptr(policy), nl, _np_ptr(ls), _np_ptr(act), _np_ptr(ub),
+            p, sel, ptr(th), ptr(gs), ptr(ga), ptr(s), ptr(u), ptr(gpol), ptr(gx0), ptr(gth)))
+        u = u[:, :T, :max(n_act, 0)]
+        return s, u, gpol, gx0, (gth[:, :p] if grad else None)
+
+    def policy_trajectory(self, x0, policy, steps: int, every: int = 1, layer_sizes=None, activations=None,
+                          use_bias=None, params=(), theta=None, first_obs_raw: bool = False, obs_raw: bool = False):
+        """(s, u): the closed-loop trajectory of policy_trajectory_vjp alone (async)"""
+        return self.policy_trajectory_vjp(x0, policy, None, steps, every, None, layer_sizes, activations, use_bias,
+                                          params, theta, first_obs_raw, obs_raw)[:2]
 
     # -- dynamics queries: kinematics, mass matrix, bias, forward and inverse dynamics, point Jacobians -----------
     def _dyn_rows(self, a, n, width, what):
