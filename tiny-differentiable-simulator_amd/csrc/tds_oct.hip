@@ -118,6 +118,17 @@ __device__ int tds_oct_prof_iter = 500;
 #ifndef TDS_OCT_SPLIT_LOOP  // (1: a loop per wavefront even where nothing is carried — what the split is worth on its own)
 #define TDS_OCT_SPLIT_LOOP 0
 #endif
+// Who computes what between barriers (1b) and (2) of the step-loop build for one wavefront per SIMD, two parts, a switch each
+// (the same convention: -DTDS_OCT_...=0 compiles a part out, and every statement then stands where it stood):
+//   TDS_OCT_POSES_LATE     the visual poses behind the helper's last row window, in its idle tail in front of barrier (0)
+//   TDS_OCT_HELP_SCHUR     the 21 sums of the Schur complement on the helper, handed over at a barrier of its own, (1c)
+// (The head of the forward dynamics in front of (1c) as well was measured and lost: tools/experiments/oct_helper_schur_not_kept.txt.)
+#ifndef TDS_OCT_POSES_LATE
+#define TDS_OCT_POSES_LATE 1
+#endif
+#ifndef TDS_OCT_HELP_SCHUR
+#define TDS_OCT_HELP_SCHUR 1
+#endif
 
 namespace {
 
@@ -272,6 +283,19 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   constexpr bool CARRY = LOOP && BUILD == 3 && TDS_OCT_CARRY != 0;
   constexpr bool TOP_EARLY = LOOP && BUILD == 3 && TDS_OCT_TOP_EARLY != 0;
   constexpr bool SPLIT_LOOP = CARRY || TOP_EARLY || (LOOP && BUILD == 3 && TDS_OCT_SPLIT_LOOP != 0);
+  // Between barriers (1b) and (2) (the same build only: the others keep their statement order).  Without them the helper idles
+  // ~2 k cycles in front of barrier (0) and is yet the late one at barrier (2), behind the visual poses:
+  // POSES_LATE: help_poses' computation and stores move behind the helper's last row window (help_poses_tail) — the link and root
+  //   transforms stay in the helper's registers across the windows, whose rows overwrite the hand-over slots; the first window's
+  //   rows then pass from rows_leg to rows_root in registers (no rows_park / rows_fetch);
+  // HELP_SCHUR: the 21 Schur sums by the helper directly behind (1b) (help_schur), barrier (1c), and the main wavefront's root
+  //   block straight through in front of it.
+  // LDS between (1b) and (2) in this build: W (O.xs) is read by the helper only, in front of (1c) — the sweep's first impulse is
+  // written behind the first window barrier; O.fac is written by the helper in front of (1c), read by every main lane behind it,
+  // then overwritten by main lane 0 with the factors (behind an OCT_SYNC: every lane's reads are done) and read by the helper
+  // behind (2); the helper's next write to it is behind (1b) of the next step.
+  constexpr bool POSES_LATE = LOOP && BUILD == 3 && TDS_OCT_POSES_LATE != 0;
+  constexpr bool HELP_SCHUR = LOOP && BUILD == 3 && TDS_OCT_HELP_SCHUR != 0;
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -401,7 +425,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   (void)is_main;
   (void)is_help;
 #ifdef TDS_OCT_PROF
-  unsigned long long prof_t[56] = {};  // 0 .. 13 phases, 24 .. 35 the main wavefront's barriers, 40 .. 51 the helper's
+  unsigned long long prof_t[56] = {};  // 0 .. 14 phases, 24 .. 37 the main wavefront's barriers, 40 .. 53 the helper's
   const bool prof_on = blockIdx.x == TDS_OCT_PROF_WG && it == tds_oct_prof_iter;
   if (it == 0 && tid == 0 && blockIdx.x < 2048) {
     unsigned long long c_;
@@ -804,7 +828,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     OCT_STAMP(8, na);
   };
-  auto help_poses = [&]() {
+  // (two halves: POSES_LATE takes them apart — the head stays between barriers (1b) and (2), the tail goes behind the helper's
+  //  last row window; everywhere else help_poses runs them back to back)
+  auto help_poses_head = [&]() {
     OCT_MARK("help_signal_poses");
     if constexpr (LOOP) {
       // (loads and stores return through one in-order counter on gfx9: this wait sees the helper's record stores of the step
@@ -817,6 +843,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         else tds_signal_slot(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
       }
     }
+  };
+  auto help_poses_tail = [&]() {
+    // (POSES_LATE: R, p, R5, P are the helper's registers since help_np — the hand-over slots they came from are row slots of
+    //  the later windows by now; the pose slots of the y record are nobody else's: main_pool and help_rec store the state part)
+    if constexpr (POSES_LATE) OCT_MARK("help_poses_late");
     // ---- M1. visual poses of y, from the PRE-step X_world (locomotion_contact_simulation.h:281-299): visual 1 + lane is
     //          my link's (DevModel::oct checks the order); visual 0 — the root body's — goes out on lane 7
     TR *yo, *yo2;
@@ -854,6 +885,10 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     OCT_MARK("help_np_end");
     OCT_STAMP(9, na);
+  };
+  auto help_poses = [&]() {
+    help_poses_head();
+    help_poses_tail();
   };
 
   auto main_dyn = [&]() {
@@ -1003,6 +1038,40 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     OCT_STAMP(3, Lc[5]);
   };
+  // HELP_SCHUR: the Schur sums by the helper, directly behind barrier (1b): L_c (O.lcw) and W (O.xs) are in LDS there, and the
+  // sums pass through LDS (O.fac) on their way to the 6 x 6 LDL^T anyway.  main_dyn2's table, passes and FMA chains, term by
+  // term; the helper has nothing to put across a pass's round trip, so the 48 operands of the three passes are requested in one
+  // batch (pass by pass the listing showed 13 exposed round trips; the helper has the registers: see the resource table).
+  auto help_schur = [&]() {
+    OCT_MARK("help_schur");
+    const T *const lcw = E + O.lcw;
+    const T *const wl = E + O.xs;
+    T *const Ssum = E + O.fac;
+    const int code = (int)CL[TB::SCHUR];
+    T la[3][8], wa[3][8];
+    int ee[3];
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+      const int rc = (code >> (6 * pass)) & 63;
+      const int r = rc >> 3, rp = rc & 7;
+      ee[pass] = (r * (r + 1)) / 2 + rp;
+#pragma unroll
+      for (int l = 0; l < 8; ++l) {
+        la[pass][l] = lcw[l * OctLds::LCW + r];
+        wa[pass][l] = wl[l * 6 + rp];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (every request in front of the first sum)
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+      T acc = T(0);
+#pragma unroll
+      for (int l = 0; l < 8; ++l) acc += la[pass][l] * wa[pass][l];
+      Ssum[ee[pass]] = acc;
+    }
+    OCT_MARK("help_schur_end");
+    OCT_STAMP(14, na);
+  };
   auto main_dyn2 = [&]() {
     OCT_MARK("main_schur");
     const T ax3[6] = {T(1), T(0), T(0), pA3[0], pA3[1], pA3[2]}, ax4[6] = {A4[0], A4[1], A4[2], pA4[0], pA4[1], pA4[2]},
@@ -1029,7 +1098,19 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       Sm[15] = F5[3]; Sm[16] = F5[4]; Sm[17] = F5[5]; Sm[18] = dot6(ax5, F3); Sm[19] = dot6(ax5, F4); Sm[20] = dot6(ax5, F5);
     };
     // the sums sum_lanes L_c[r] W[r'] of the Schur complement, entry e = r (r + 1) / 2 + r' on lane e mod 8 (three passes)
-    {
+    if constexpr (HELP_SCHUR) {
+      // The helper sums (help_schur) while this wavefront does what needs no sum: the root block straight through; barrier (1c):
+      // the 21 sums are in O.fac.  Both wavefronts take it once per step, unconditionally.
+      // (fences: left to itself the back end moves the root block — arithmetic on registers — up in front of barrier (1b), where
+      //  the helper, early there, would wait for it instead of summing beside it; and nothing is to slide behind (1c))
+      __builtin_amdgcn_sched_barrier(0);
+      root_block_a1();
+      root_block_a2();
+      root_block_b();
+      __builtin_amdgcn_sched_barrier(0);
+      OCT_MARK("main_wait_schur");
+      OCT_BAR_T(36);  // (1c)
+    } else {
       const T *const lcw = E + O.lcw;
       const T *const wl = E + O.xs;  // (W = L_c D in the impulses' slots: every read of it stands here, behind barrier (1b) and in
                                      //  front of barrier (2), in either order of the reads; the sweep's impulses come behind (2))
@@ -1218,7 +1299,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // The row's entries of z~ pass from stage to stage in registers (RowRegs), and a slot of the row in LDS is written once, with
   // its final value.  The first window's rows wait for the root block's factors across the visual poses: parked in their own
   // slots of the row (rows_park) and read back in FRONT of barrier (2) (rows_fetch) — behind it the helper reads nothing
-  // but the factors.
+  // but the factors.  (POSES_LATE builds: the poses stand behind the last window, and the first window's rows stay in registers.)
   struct RowRegs {
     T z0, z1, zr[6];
     int hl;
@@ -1764,7 +1845,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
 
   // ================================ the step ================================
-  // barriers of a two-wavefront workgroup: (1) the kinematics are in LDS; (1b) the leg blocks' factors and couplings; (2) the
+  // barriers of a two-wavefront workgroup: (1) the kinematics are in LDS; (1b) the leg blocks' factors and couplings; (1c,
+  // HELP_SCHUR builds only) the helper's 21 Schur sums; (2) the
   // root block's factors (main wavefront), the contact list and counts (helper); one per row window (window wi is in LDS: the
   // helper stays a window ahead of the sweep); (0) the
   // step's state, reward and done are in the LDS record — the helper stores the step's records while the main wavefront
@@ -1810,12 +1892,22 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       RowRegs rw = {};
       if (NA > 0) rows_geom(0, 0, rw);
       OCT_BAR_T(42);  // (1b)
-      if (NA > 0) {
-        rows_leg(0, rw);
-        rows_park(rw);
+      if constexpr (HELP_SCHUR) {
+        help_schur();
+        OCT_BAR_T(52);  // (1c): once per step, whatever NA, pgs_iters, valid and last are — as the main wavefront's in main_dyn2
       }
-      help_poses();
-      if (NA > 0) rows_fetch(rw);
+      if constexpr (POSES_LATE) {
+        // (nothing stands between the first window's leg stage and its root stage but the barrier: the rows stay in registers)
+        if (NA > 0) rows_leg(0, rw);
+        help_poses_head();
+      } else {
+        if (NA > 0) {
+          rows_leg(0, rw);
+          rows_park(rw);
+        }
+        help_poses();
+        if (NA > 0) rows_fetch(rw);
+      }
       OCT_BAR_T(44);  // (2)
       // (the same windows as the main wavefront's two loops, the first one — the stretch the main wavefront waits for: nothing
       //  but the factors' reads, the root stage and the barrier — taken out in front: there is one exactly when NA > 0 and
@@ -1836,6 +1928,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           }
         }
       }
+      // (behind the last row window, or right behind (2) where a step has none: the helper's idle tail)
+      if constexpr (POSES_LATE) help_poses_tail();
       OCT_BAR_T(50);  // (0)
       help_rec();
     }
@@ -1881,11 +1975,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     for (int k = 0; k < 14; ++k)
       if (((k < 8 || k >= 12) && is_main) || (k >= 8 && k < 12 && is_help)) tds_oct_prof_buf[k] = prof_t[k];
     if (is_help) tds_oct_prof_buf[15] = (unsigned long long)NA;
+    if (is_help) tds_oct_prof_buf[14] = prof_t[14];  // (the helper's Schur sums are stored: help_schur)
+    // (barrier (1c): the main wavefront's stamps 36 / 37, the helper's 52 / 53)
 #pragma unroll
-    for (int k = 24; k < 36; ++k)
+    for (int k = 24; k < 38; ++k)
       if (is_main) tds_oct_prof_buf[k] = prof_t[k];
 #pragma unroll
-    for (int k = 40; k < 52; ++k)
+    for (int k = 40; k < 54; ++k)
       if (is_help) tds_oct_prof_buf[k] = prof_t[k];
   }
 #endif

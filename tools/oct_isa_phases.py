@@ -28,7 +28,7 @@ EXPOSED_SLOTS = 12
 PHASES = [("PD, jcalc, root sincos, kinematics", ["main_top", "main_jcalc", "main_rootsincos", "main_rootvel", "main_legs", "main_publish_kin"]),
           ("D rigid inertias", ["main_rigid"]),
           ("E totals, G, H leg LDL^T", ["main_totals", "main_FC", "main_legldl"]),
-          ("Schur sums, root block, 6 x 6 LDL^T", ["main_schur", "main_Rblock", "main_ldl6"])]
+          ("Schur sums, root block, 6 x 6 LDL^T", ["main_schur", "main_wait_schur", "main_Rblock", "main_ldl6"])]
 
 
 def phase_cycles(path):

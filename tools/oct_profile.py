@@ -69,16 +69,18 @@ def main():
         barriers(t)
 
 
-BARRIERS = ["(1) kinematics in LDS", "(1b) leg factors, couplings", "(2) root factors, contact list", "first row window", "(0) state, reward, done"]
+# (name, the main wavefront's stamp in front of the barrier, the helper's; + 1: behind it)
+BARRIERS = [("(1) kinematics in LDS", 24, 40), ("(1b) leg factors, couplings", 26, 42), ("(1c) Schur sums (helper)", 36, 52),
+            ("(2) root factors, contact list", 28, 44), ("first row window", 30, 46), ("(0) state, reward, done", 34, 50)]
 
 
 def barriers(t):
     """Per barrier of the two-wavefront build: arrival of both wavefronts (cycles from the main wavefront's top of step), who was
     first and how long it waited for the other (stamps 24 + 2 b / 40 + 2 b in front of the barrier, + 1 behind it; the window
-    barriers behind the first one add up in stamps 32 / 48)."""
+    barriers behind the first one add up in stamps 32 / 48; barrier (1c) of the builds whose helper sums the Schur complement:
+    36 / 52)."""
     print("  barriers: main wavefront arrives | helper arrives | first to arrive, its wait for the other | released (main, helper)")
-    for b, name in enumerate(BARRIERS):
-        km, kh = 24 + 2 * b + (2 if b == 4 else 0), 40 + 2 * b + (2 if b == 4 else 0)
+    for name, km, kh in BARRIERS:
         if t[km] == 0 or t[kh] == 0:
             print(f"    {name}: not passed in this iteration")
             continue
@@ -86,6 +88,11 @@ def barriers(t):
         who = "main" if am <= ah else "helper"
         print(f"    {name:34s} {am:6d} | {ah:6d} | {who:6s} waits {abs(ah - am):5d} | {t[km + 1] - t[0]:6d} {t[kh + 1] - t[0]:6d}")
     print(f"    later row windows, time inside their barriers in all: main wavefront {t[32]}, helper {t[48]}")
+    if t[36] and t[52]:
+        print(f"    main wavefront, (1b) released -> arrival at (2): {t[28] - t[27]}; helper's Schur sums stored at {t[14] - t[0]}; "
+              f"visual poses out {t[34] - t[9]} cycles in front of the main wavefront's arrival at (0)")
+    else:
+        print(f"    main wavefront, (1b) released -> arrival at (2): {t[28] - t[27]}")
     print("    (a stamp costs the wavefront that takes it ~40-60 cycles: a clock read and its wait)")
 
 
