@@ -606,6 +606,43 @@ typedef struct tds_param {
 } tds_param_t;
 /* theta [p] = the blob's values of the selection (host arrays); checks the selection. */
 int tds_hip_params_get(const tds_model_t *model, int p, const tds_param_t *params, double *theta);
+/* The inverse: *out_model = the blob with the selected scalars set to theta [p] (host arrays; out_model may be model
+   itself).  Same checks and refusals as tds_hip_params_get; an off-diagonal inertia comp sets both mirror entries.
+   This is the definition of "the model of variant v" below. */
+int tds_hip_params_apply(const tds_model_t *model, int p, const tds_param_t *params, const double *theta,
+                         tds_model_t *out_model);
+
+/* Per-environment model variants: STEPPING a batch whose environments differ in the scalars a selection names (domain
+   randomisation, sampling-based system identification).  Variant v is tds_hip_params_apply(the handle's blob, params,
+   theta_host [v]) built into a device model of its own, so every derived quantity follows; environment e steps under
+   variant env_variant_host [e] (int32 [num_envs]; NULL where n_variants == num_envs: the identity).  While variants are
+   installed EVERY stepping path of the handle — forward_zero, step, step_many, the record rings, the rollout, forced
+   resets through tds_hip_reset (re-initialised and settled under the environment's own variant) — runs the general step
+   kernel's variant builds, one wavefront per workgroup (tds_hip_single_step_kernel and tds_hip_kernel_info report
+   that); the 8-lane, 16-lane and serial-chain kernels decline.  n_variants == 0 clears: the handle is back on its own
+   kernel and computes bit for bit what it computed before.  The derivative and query entry points (tds_hip_jvp*,
+   tds_hip_vjp*, tds_hip_trajectory_*, tds_hip_policy_trajectory_*, tds_hip_dynamics, tds_hip_contacts, ...) take theta
+   explicitly or read the handle's own blob: they IGNORE installed variants.
+   Every variant must have the base model's STRUCTURE: outside the fields a selection can change (X_T, mass, centre of
+   mass, inertia, joint springs, gravity, friction, restitution, and the frames of contact points and visuals) its
+   device model equals the base's — a mass on a massless root link, for instance, changes how the root chain is
+   treated; such a variant is TDS_ERR_INVALID_ARG, the message names the variant and the field.  A map entry outside
+   [0, n_variants), n_variants > num_envs, n_variants != num_envs with a NULL map, or a bad selection:
+   TDS_ERR_INVALID_ARG.  Models with spherical joints and worlds of several bodies: TDS_ERR_UNSUPPORTED with the
+   parameter derivatives' message.  A handle with auto-reset on: TDS_ERR_UNSUPPORTED, as is tds_hip_set_auto_reset(1)
+   while variants are installed (the reset pool's entries are settled under one model), the handle of a multi-GPU
+   shard, phase stamps and option alt_build.  Memory: n_variants * sizeof(device model), 40.5 KB each in double
+   arithmetic, 23.8 KB in float.  The call waits for the handle's stream, then replaces the arrays and drops every
+   captured step_many graph and prepared launch. */
+int tds_hip_set_model_variants(tds_hip_sim_t *sim, int n_variants, int p, const tds_param_t *params_host,
+                               const double *theta_host /* [n_variants][p] */, const int32_t *env_variant_host);
+/* variants installed on the handle (0: none) */
+int tds_hip_model_variants(const tds_hip_sim_t *sim);
+/* The checks of tds_hip_set_model_variants on the CPU, for a handle of num_envs environments of `dtype` (needs no GPU);
+   *bytes (optional) receives the size of the device array of the variants' models. */
+int tds_hip_model_variants_host(const tds_model_t *model, int dtype, int num_envs, int n_variants, int p,
+                                const tds_param_t *params, const double *theta, const int32_t *env_variant,
+                                int64_t *bytes);
 /* Forward mode in [x | theta]: jv[n][k][output_dim] = J v for v [n][k][input_dim + p]; k = 0 computes y only (v, jv
    may then be NULL).  x_dev [n][input_dim], theta_dev [n][p], y_dev (optional) [n][output_dim]: device pointers;
    params_host: host array.  Enqueued on the handle's stream (the selection is copied into the work buffer with a

@@ -18,6 +18,7 @@
 #include "tds_api_internal.h"
 #include "tds_launch_plan.h"
 #include "tds_oct_windows.h"
+#include "tds_variants_api.h"
 
 namespace tds_internal {
 thread_local char g_err[512] = "";
@@ -117,7 +118,8 @@ template <typename T, typename TR>
 static int launch_planned_t(const tds_hip_sim *s, const DevModel<T> &h, const TdsLaunchPlan &p, const TdsLds &L, const void *x,
                             void *y, const void *actions, void *fb, void *obs, void *ovf, int n, hipStream_t stream,
                             const TdsStepCtl &ctl, long long *prof) {
-  const DevModel<T> *d = (const DevModel<T> *)s->d_model;
+  // (variants installed: the array of the variants' models; ctl.variant names each environment's entry)
+  const DevModel<T> *d = (const DevModel<T> *)(ctl.variant ? s->d_variants : s->d_model);
   const TR *xi = (const TR *)x, *a = (const TR *)actions;
   TR *yo = (TR *)y, *f = (TR *)fb, *ob = (TR *)obs;
   if (p.kernel == TDS_KERNEL_QUAD16)
@@ -178,7 +180,16 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
   const TdsLaunchPlan plan = tds_launch_plan(*s, req);
   if (plan.refused)
     return fail(TDS_ERR_UNSUPPORTED, "option loop_occ = 1: no one-wavefront-per-SIMD step-loop build below 24 padded dof");
-  const TdsLds &lds = tds_plan_layout(*s, plan);
+  // per-environment model variants: the variant builds read no workgroup constant table (it would be the first lane
+  // group's): a layout without its rows, and the dynamic LDS size follows
+  TdsLds lds = tds_plan_layout(*s, plan);
+  if (s->n_variants > 0) {
+    if (req.progress || req.peers || req.pool_pass || req.pool_states)
+      return fail(TDS_ERR_UNSUPPORTED, "model variants: not with the multi-GPU exchange or the reset pool");
+    if (s->opt.get(TDS_OPT_ALT_BUILD, 0) != 0) return fail(TDS_ERR_UNSUPPORTED, "model variants: not with option alt_build");
+    lds.cw = 0;
+    ctl.variant = s->d_env_variant + ((opts && opts->env_first > 0) ? opts->env_first : 0);
+  }
   void *ovf = (opts && opts->ovf) ? opts->ovf : ((opts && opts->pool_pass) ? nullptr : s->d_ovf);
   if (opts && opts->env_first > 0) {  // a sub-range of the environments: every per-environment array moves along
     const size_t e0 = (size_t)opts->env_first, el = s->elem;
@@ -564,6 +575,8 @@ int tds_hip_destroy(tds_hip_sim_t *s) {
   }
   if (s->graph_fork) (void)hipEventDestroy(s->graph_fork);
   if (s->d_model) (void)hipFree(s->d_model);
+  if (s->d_variants) (void)hipFree(s->d_variants);
+  if (s->d_env_variant) (void)hipFree(s->d_env_variant);
   if (s->d_x) (void)hipFree(s->d_x);
   if (s->d_y) (void)hipFree(s->d_y);
   if (s->d_ovf) (void)hipFree(s->d_ovf);
@@ -1554,12 +1567,92 @@ int tds_hip_set_auto_reset(tds_hip_sim_t *s, int enable, unsigned long long seed
   if (!s) return fail(TDS_ERR_INVALID_ARG, "sim is NULL");
   if (enable && s->model.reward_mode == TDS_REWARD_NONE)
     return fail(TDS_ERR_INVALID_ARG, "auto-reset needs a model with a termination rule (reward_mode)");
+  if (enable && s->n_variants > 0)
+    return fail(TDS_ERR_UNSUPPORTED, "auto-reset with model variants installed: the reset pool's entries are settled under one model");
   s->auto_reset = enable != 0;
   s->seed = seed;
   s->pool_ready = false;  // (entries depend on the seed)
   s->pool_discard = true;
   return TDS_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------
+// Per-environment model variants: V models of the handle's structure, one per environment through a map.  Each is the
+// handle's blob with a parameter selection set to theta_v, run through tds_build_dev_model (tds_variants.h) — the whole
+// array goes up once, the launches then take the general kernel's variant builds (tds_launch_plan.h).
+// ------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+void variants_free(tds_hip_sim *s) {
+  if (s->d_variants) (void)hipFree(s->d_variants);
+  if (s->d_env_variant) (void)hipFree(s->d_env_variant);
+  s->d_variants = nullptr;
+  s->d_env_variant = nullptr;
+  s->n_variants = 0;
+}
+template <typename T>
+int variants_upload(tds_hip_sim *s, int n_variants, int p, const tds_param_t *params, const double *theta, void **d_out) {
+  std::vector<DevModel<T>> host;
+  char why[256];
+  const int rc = tds_build_variants<T>(&s->model, n_variants, p, params, theta, &host, why, sizeof(why));
+  if (rc) return fail(rc, "%s", why);
+  const size_t bytes = host.size() * sizeof(DevModel<T>);
+  HIP_TRY(hipMalloc(d_out, bytes));
+  if (hipMemcpy(*d_out, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(*d_out);
+    *d_out = nullptr;
+    return fail(TDS_ERR_HIP, "model variants: upload failed%s");
+  }
+  return TDS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int tds_hip_set_model_variants(tds_hip_sim_t *s, int n_variants, int p, const tds_param_t *params_host,
+                               const double *theta_host, const int32_t *env_variant_host) {
+  if (!s) return fail(TDS_ERR_INVALID_ARG, "sim is NULL");
+  DeviceGuard guard(s->device);
+  if (n_variants == 0) {  // clear: back to the handle's own model and kernel
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    drop_graphs(s);
+    variants_free(s);
+    return TDS_OK;
+  }
+  if (p < 0 || (p > 0 && !theta_host)) return fail(TDS_ERR_INVALID_ARG, "tds_hip_set_model_variants: NULL argument%s");
+  int rc = tds_variants_prepare(&s->model, s->num_envs, n_variants, p, params_host, env_variant_host);
+  if (rc) return rc;
+  if (s->auto_reset)
+    return fail(TDS_ERR_UNSUPPORTED, "model variants on a handle with auto-reset on: the reset pool's entries are settled under one model");
+  if (s->shard_ring_shaped) return fail(TDS_ERR_UNSUPPORTED, "model variants: not on the handle of a multi-GPU shard");
+  void *d_new = nullptr;
+  rc = s->compute_f64() ? variants_upload<double>(s, n_variants, p, params_host, theta_host, &d_new)
+                        : variants_upload<float>(s, n_variants, p, params_host, theta_host, &d_new);
+  if (rc) return rc;
+  std::vector<int> map((size_t)s->num_envs);
+  for (int e = 0; e < s->num_envs; ++e) map[(size_t)e] = env_variant_host ? env_variant_host[e] : e;
+  int *d_map = nullptr;
+  if (hipMalloc((void **)&d_map, map.size() * sizeof(int)) != hipSuccess ||
+      hipMemcpy(d_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d_new);
+    if (d_map) (void)hipFree(d_map);
+    return fail(TDS_ERR_HIP, "model variants: upload of the environment map failed%s");
+  }
+  // launches in flight read the old arrays; the cached step_many graphs and prepared launches hold the old kernel and
+  // its arguments
+  if (hipStreamSynchronize(s->stream) != hipSuccess) {
+    (void)hipFree(d_new);
+    (void)hipFree(d_map);
+    return fail(TDS_ERR_HIP, "model variants: hipStreamSynchronize failed%s");
+  }
+  drop_graphs(s);
+  variants_free(s);
+  s->d_variants = d_new;
+  s->d_env_variant = d_map;
+  s->n_variants = n_variants;
+  return TDS_OK;
+}
+
+int tds_hip_model_variants(const tds_hip_sim_t *s) { return s ? s->n_variants : 0; }
 
 int tds_hip_reset(tds_hip_sim_t *s, const unsigned char *mask_dev, void *obs_dev) {
   if (!s) return fail(TDS_ERR_INVALID_ARG, "sim is NULL");
@@ -2072,6 +2165,7 @@ int tds_hip_last_kernel_ms(tds_hip_sim_t *s, float *ms) {
 int tds_hip_profile_phases(tds_hip_sim_t *s, long long *cycles_host, int n) {
   if (!s || !cycles_host) return fail(TDS_ERR_INVALID_ARG, "NULL argument");
   if (n < TDS_NUM_PHASE_STAMPS) return fail(TDS_ERR_INVALID_ARG, "need room for 14 stamps");
+  if (s->n_variants > 0) return fail(TDS_ERR_UNSUPPORTED, "phase stamps: no stamped build with model variants installed");
   DeviceGuard guard(s->device);
   // room for 2 x 14 stamps and a grid the two-wavefront form serves: profile THAT form (14..: the helper wavefront)
   TdsLaunchReq r;

@@ -30,6 +30,12 @@ struct tds_hip_sim {
   size_t elem = 8;  // bytes per scalar of the RECORDS in HBM (x, y, actions, obs, policy)
   hipStream_t stream = nullptr;
   void *d_model = nullptr;  // DevModel<T>, T = compute scalar
+  // per-environment model variants (tds_hip_set_model_variants): n_variants > 0: every stepping launch takes the general
+  // kernel's variant builds (tds_launch_plan.h), which read d_variants [n_variants] DevModel<T> through d_env_variant
+  // [num_envs]; d_model stays the handle's own model (what the launches go back to when the variants are cleared)
+  int n_variants = 0;
+  void *d_variants = nullptr;
+  int *d_env_variant = nullptr;
   DevModel<double> h64;
   DevModel<float> h32;
   TdsLds lds;

@@ -108,6 +108,10 @@ struct TdsStepCtl {
   int n_peers;                      // ranks other than this one (0: one rank — the counters and the own flags only)
   int peer_flag_off;                // flag index of this rank in the launch's slot 0: slot0 * world + rank
   int peer_flag_stride;             // flags per slot (= world)
+  // PER-ENVIRONMENT MODEL VARIANTS (tds_hip_set_model_variants; variant builds of the general kernel only): != NULL:
+  // [n_envs] index of the environment's model in the array the model argument points to (entry 0 is also where every
+  // build reads the model's STRUCTURE: dimensions, indices, flags).  Indexed with the launch's local environment number.
+  const int *variant;
 };
 // arrival counting of the peer-store exchange: workgroup b counts itself in on first-level counter b mod TDS_PEER_SUB of
 // the slot, the workgroup that completes a first-level counter on the slot's second-level counter.  One counter for the

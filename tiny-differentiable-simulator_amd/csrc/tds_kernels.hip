@@ -725,7 +725,15 @@ __device__ __forceinline__ void tds_reset_state(T *xr, const DevModel<T> *mdl, c
 // with three workgroup barriers at the bars.  The LDS groups that alias each other in the one-wave layout are
 // disjoint here (their lifetimes now overlap), which costs LDS and is why this form is launched only while the whole
 // grid fits the GPU at once (tds_launch_step_impl).
-template <typename T, typename TR, int G, int NDP, bool PROF, int LP, int KIND, bool W2 = false>
+// VAR: per-environment model VARIANTS (tds_hip_set_model_variants): mdl_arg points to an ARRAY of models of one structure
+// and ctl.variant [n_envs] names each environment's entry.  The lane group of an environment reads the model's VALUES —
+// what a parameter selection can change: X_T, mass, centre of mass, inertia, joint springs, gravity, friction,
+// restitution, and the contact points' and visuals' frames (re-based where fixed links are folded) — through its own
+// entry; the STRUCTURE — dimensions, indices, flags, and every constant no selection reaches — still comes from entry 0
+// through scalar loads, so that every branch on it stays wave-uniform (the host checks that the entries agree in all of
+// it).  One wavefront per workgroup, straight-line and step loop; the workgroup's constant table (TdsLds::cw) is the
+// first lane group's and is not used.
+template <typename T, typename TR, int G, int NDP, bool PROF, int LP, int KIND, bool W2 = false, bool VAR = false>
 __global__ __launch_bounds__(W2 ? 128 : 64)
 __attribute__((amdgpu_waves_per_eu((LP == 2 || W2 || (LP == 0 && NDP < 24)) ? 2 : 1)))
 void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
@@ -738,6 +746,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   const TdsStepCtl &ctl = ctl_arg;
   static_assert(!W2 || ((LP == 0 || LP == 1) && KIND == 0 && NDP < 24),
                 "two-wavefront workgroups: plain kernels, straight-line or step-loop");
+  static_assert(!VAR || (!W2 && !PROF && (KIND == 0 || KIND == 1)), "variant builds: one wavefront, fixed or floating base");
   // LDS slots behind the x record (xr[in_dim + ...]): 0 x_{t-1}, 1 done; two-wavefront layout: 2, 3 contact counts, 4 "y~ is
   // published", 5 columns of L published; then (step-loop builds with record rings) the step's reward and "its records are out"
   constexpr int RW_SLOT = W2 ? 6 : 2, OUT_SLOT = W2 ? 7 : 3;
@@ -795,6 +804,13 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   bool frozen = false;
   int tds_iter = 0;
   (void)tds_iter;
+  // variant builds: the environment's entry of the model array (lane groups past n_envs: entry 0, a valid model).  The
+  // ONE value besides the loop state that crosses the back edge: an iteration re-derives its pointer from a laundered copy
+  int var0 = 0;
+  if constexpr (VAR) {
+    const int env = blockIdx.x * EPW + grp0;
+    if (env < n_envs) var0 = ctl.variant[env];
+  }
   if constexpr (LOOP) {
     // prologue of the step-loop build: x record -> LDS, forced reset of the selected environments
     const DevModel<T> *mdl = mdl_arg;
@@ -810,7 +826,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     // workgroup per CU).  Measured (experiment slots, same process: profiles/r04_ab_slots3_lds_consts.txt): Ant x 4096 ring
     // launches 13.66 -> 13.46 (small constants) -> 13.08 us per step (+ X_T); mass / centre of mass / inertia / motion axis
     // on top change nothing (they are consumed phases later: their latency was hidden already).
-    if constexpr (KIND == 0) {
+    if constexpr (KIND == 0 && !VAR) {
       if (L.cw != 0) {  // wave-uniform (kernel argument)
         constexpr int CWL = TDS_CW_LANE(sizeof(T));
         T *const CW = sm + EPW * L.stride;
@@ -857,7 +873,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     TDS_WAVE_SYNC();
     bool finished0 = false;  // forced reset with zero settle steps: nothing to simulate
     if (ctl.reset_mode == TDS_RESET_FORCED && valid && (ctl.mask == nullptr || ctl.mask[env] != 0)) {
-      tds_reset_state<T, G>(xr, mdl, ctl, env, lane, nq, nd);
+      tds_reset_state<T, G>(xr, mdl + var0, ctl, env, lane, nq, nd);
       if (nset > 0) {
         mode = TDS_MODE_SETTLE;
         sleft = nset;
@@ -896,6 +912,15 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   if constexpr (LOOP && NDP < 32) asm volatile("" : "+v"(lane_l), "+v"(grp_l), "+s"(mdl_g));
   if constexpr (LOOP && NDP >= 32) asm volatile("" : "+s"(mdl_g));
   const DevModel<T> *const mdl = (const DevModel<T> *)mdl_g;
+  // mdv: where the model's VALUES are read (see VAR) — the environment's own entry, its index laundered like the
+  // pointer: the loads through it are re-issued per iteration instead of being hoisted and kept live across the loop
+  const DevModel<T> *mdv_p = mdl;
+  if constexpr (VAR) {
+    int var_l = var0;
+    if constexpr (LOOP) asm volatile("" : "+v"(var_l));
+    mdv_p = (const DevModel<T> *)(mdl_g + var_l);
+  }
+  const DevModel<T> *const mdv = mdv_p;
   const int lane = lane_l, grp = grp_l;
   // ---- the kernel arguments of this iteration (step-loop builds: read through a laundered segment pointer, see TdsKaRef)
   constexpr bool KA = LOOP;
@@ -942,7 +967,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
   const bool isl = li < nl;
   const int lsafe = isl ? li : 0;
   // (step-loop launches: from the workgroup's constant table in LDS where the host granted one, see the prologue)
-  const bool cwt = LOOP && KIND == 0 && L.cw != 0;  // wave-uniform
+  const bool cwt = LOOP && KIND == 0 && !VAR && L.cw != 0;  // wave-uniform
   constexpr int CWL = TDS_CW_LANE(sizeof(T));
   const T *const CW = sm + EPW * L.stride;
   // (read through an LDS-address-space pointer: as generic pointers the compiler merged "table or model" into ONE flat load
@@ -1025,8 +1050,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     par_slot = (isl && parent >= 0) ? mdl->lc_slot[parent] : -1;
     act_i = isl ? mdl->act_index[lsafe] : -1;
     init_pose_l = mdl->init_pose[lsafe];
-    stiff_l = mdl->stiffness[lsafe];
-    damp_l = mdl->damping[lsafe];
+    stiff_l = mdv->stiffness[lsafe];
+    damp_l = mdv->damping[lsafe];
   }
   // Top of a step of a two-wavefront step loop, BOTH wavefronts: barrier (0).  The main wavefront arrives from its
   // integration (the LDS record holds the state, reward and done flag of the step before), the helper — long waiting — from
@@ -1056,11 +1081,11 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     if (cwt && L.cw >= CWL + TDS_CW_XT) {  // (X_T from the workgroup's table; the rest is consumed phases later)
 #pragma unroll
       for (int k = 0; k < 6; ++k) Sl[k] = md->S[k][lsafe];
-      mass_l = md->mass[lsafe];
+      mass_l = mdv->mass[lsafe];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) com_l[k] = md->com[k][lsafe];
+      for (int k = 0; k < 3; ++k) com_l[k] = mdv->com[k][lsafe];
 #pragma unroll
-      for (int k = 0; k < 9; ++k) Il[k] = md->inertia[k][lsafe];
+      for (int k = 0; k < 9; ++k) Il[k] = mdv->inertia[k][lsafe];
 #pragma unroll
       for (int k = 0; k < 9; ++k) RT[k] = CWl[(CWL + k) * G + lane];
 #pragma unroll
@@ -1069,15 +1094,15 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) Sl[k] = md->S[k][lsafe];
-    mass_l = md->mass[lsafe];
+    mass_l = mdv->mass[lsafe];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) com_l[k] = md->com[k][lsafe];
+    for (int k = 0; k < 3; ++k) com_l[k] = mdv->com[k][lsafe];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Il[k] = md->inertia[k][lsafe];
+    for (int k = 0; k < 9; ++k) Il[k] = mdv->inertia[k][lsafe];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) RT[k] = md->X_T[k][lsafe];
+    for (int k = 0; k < 9; ++k) RT[k] = mdv->X_T[k][lsafe];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) tT[k] = md->X_T[9 + k][lsafe];
+    for (int k = 0; k < 3; ++k) tT[k] = mdv->X_T[9 + k][lsafe];
   };
   if constexpr (!LOOP) {
     if (main_wave) load_link_consts(mdl);
@@ -1098,12 +1123,12 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     pf_cp_link = md->cp_link[kc];
     pf_cp_anc = md->anc_dofs[pf_cp_link >= 0 ? pf_cp_link : 0];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pf_cp_loc[c] = md->cp_local[c][kc];
+    for (int c = 0; c < 3; ++c) pf_cp_loc[c] = mdv->cp_local[c][kc];
     pf_cp_rad = md->cp_radius[kc];
     const int kv = lane < pf_nv ? lane : 0;
     pf_vis_link = md->vis_link[kv];
 #pragma unroll
-    for (int c = 0; c < 12; ++c) pf_vis_X[c] = md->vis_X[c][kv];
+    for (int c = 0; c < 12; ++c) pf_vis_X[c] = mdv->vis_X[c][kv];
     pf_dof_link = md->dof_link[lane < md->dof_qd ? lane : 0];
     pf_anc = md->anc_dofs[pf_dof_link];
 #pragma unroll
@@ -1116,8 +1141,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     pf_plane_c = md->plane_c;
     pf_cfm = md->cfm;
     pf_erp_dt = md->erp_over_dt;
-    pf_rest = md->restitution;
-    pf_mu = md->friction;
+    pf_rest = mdv->restitution;
+    pf_mu = mdv->friction;
     pf_iters = md->pgs_iterations;
   };
   if constexpr (!LOOP) load_phase_consts(mdl);
@@ -1138,7 +1163,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     }
     TDS_WAVE_SYNC();
   }
-  auto reset_state = [&]() { tds_reset_state<T, G>(xr, mdl, ctl, env, lane, nq, nd); };
+  auto reset_state = [&]() { tds_reset_state<T, G>(xr, mdv, ctl, env, lane, nq, nd); };
   const bool live = mode != TDS_MODE_IDLE;
   const bool last_run = mode == TDS_MODE_RUN && left == 1;
   const bool settling = LOOP && mode == TDS_MODE_SETTLE;
@@ -1427,9 +1452,9 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
           T loc[3] = {pf_cp_loc[0], pf_cp_loc[1], pf_cp_loc[2]};
           T rad = pf_cp_rad;
           if (!first) {
-            loc[0] = mdl->cp_local[0][k];
-            loc[1] = mdl->cp_local[1][k];
-            loc[2] = mdl->cp_local[2][k];
+            loc[0] = mdv->cp_local[0][k];
+            loc[1] = mdv->cp_local[1][k];
+            loc[2] = mdv->cp_local[2][k];
             rad = mdl->cp_radius[k];
           }
           T ctr[3];
@@ -1511,10 +1536,15 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
 #pragma unroll
           for (int c = 0; c < 3; ++c) pv[c] = pf_vis_X[9 + c];
           if (!first) {
+            // (variant builds: the visual's frame from the environment's own model; named through `mdl` in every other
+            //  build, so that this lambda captures what it captured before the variant builds existed — as a second
+            //  capture the same pointer cost the float two-wavefront builds of 8 padded dof eight registers)
+            const DevModel<T> *mvis = mdl;
+            if constexpr (VAR) mvis = mdv;
 #pragma unroll
-            for (int c = 0; c < 9; ++c) Rv[c] = mdl->vis_X[c][k];
+            for (int c = 0; c < 9; ++c) Rv[c] = mvis->vis_X[c][k];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) pv[c] = mdl->vis_X[9 + c][k];
+            for (int c = 0; c < 3; ++c) pv[c] = mvis->vis_X[9 + c][k];
           }
           T Ro[9], po[3], qo[4];
           mat3_mul(Rl, Rv, Ro);
@@ -2137,7 +2167,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
         v[k] = torso ? W5[k] : T(0);
         v[3 + k] = torso ? V5[k] : T(0);
         a0[k] = torso ? a45[k] + a55[k] : T(0);
-        a0[3 + k] = torso ? (l3[k] + l4[k] + l5[k]) - mdl->grav[k] : T(0);
+        a0[3 + k] = torso ? (l3[k] + l4[k] + l5[k]) - mdv->grav[k] : T(0);
       }
     }
     if (leg_len != 0) {
@@ -2343,9 +2373,9 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
       }
     });
     if (inch && !fl) {
-      a0[3] -= mdl->grav[0];
-      a0[4] -= mdl->grav[1];
-      a0[5] -= mdl->grav[2];
+      a0[3] -= mdv->grav[0];
+      a0[4] -= mdv->grav[1];
+      a0[5] -= mdv->grav[2];
     }
     if (inch && lds_children) {  // children other than lane + 1 read my record
 #pragma unroll
@@ -2412,9 +2442,9 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
 #pragma unroll
         for (int k = 0; k < 6; ++k) vq[k] = aq[k] = T(0);
         // base acceleration = -gravity in the body's own base frame (forward_dynamics.hpp:237-243)
-        aq[3] = two ? -mdl->gravb[bod][0] : -mdl->grav[0];
-        aq[4] = two ? -mdl->gravb[bod][1] : -mdl->grav[1];
-        aq[5] = two ? -mdl->gravb[bod][2] : -mdl->grav[2];
+        aq[3] = two ? -mdl->gravb[bod][0] : -mdv->grav[0];
+        aq[4] = two ? -mdl->gravb[bod][1] : -mdv->grav[1];
+        aq[5] = two ? -mdl->gravb[bod][2] : -mdv->grav[2];
         if (flm && fbk == 0) {
           // floating base (kinematics.hpp:35-47): base_X_world = (quat_to_matrix(q[0..3]), q[4..6]) of the body's own
           // share of the q record; it is the frame of all six pseudo links (identity joint transforms behind this one)
@@ -3132,7 +3162,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
           xv -= ((d < k && jrow) ? lv : T(0)) * xk;
         }
       });
-      if (fl && d >= njd + 3 && d < nd) xv += mdl->grav[d - njd - 3];  // forward_dynamics.hpp:315-319
+      if (fl && d >= njd + 3 && d < nd) xv += mdv->grav[d - njd - 3];  // forward_dynamics.hpp:315-319
       if (flm && bdof && d >= dbase0 + 3) xv += mdl->gravb[mdl->dof_body[d]][d - dbase0 - 3];
       // integrate_euler_qdd; from here on the velocities live in dof order in the column scratch
       TDS_WAVE_SYNC();
@@ -3653,8 +3683,8 @@ template <typename T, typename TR>
 using TdsStepKernelFn = void (*)(const DevModel<T> *, TdsLds, const TR *, TR *, const TR *, TR *, TR *, T *, long long *,
                                  TdsStepCtl, int);
 
-// THE BUILD TABLE: which tds_step_kernel<T, TR, G, NDP, PROF, LP, KIND, W2> exist for a (T, TR, KIND, G, NDP), written
-// once.  f(kernel, stamped, loop, two_waves) is called for one build after the other until it returns true (a
+// THE BUILD TABLE: which tds_step_kernel<T, TR, G, NDP, PROF, LP, KIND, W2, VAR> exist for a (T, TR, KIND, G, NDP), written
+// once.  f(kernel, stamped, loop, two_waves, variants) is called for one build after the other until it returns true (a
 // two-wavefront build runs 128 threads per workgroup, every other one 64).  Whatever is not listed here is never
 // instantiated; the kernel's static_assert has the last word on what may be.
 //   * straight-line and step-loop build, one wavefront per workgroup: every key.  Step loop: below 24 padded dof the
@@ -3670,25 +3700,32 @@ using TdsStepKernelFn = void (*)(const DevModel<T> *, TdsLds, const TR *, TR *, 
 //     dof they carried 130 - 180 B of scratch per lane, profiles/r06_kernel_resources_f64_k0.txt).
 //   * phase stamps (a diagnostic: profiles/*_phases.txt): plain kernels with double records, straight-line form, one- and
 //     two-wavefront; -DTDS_PROF_LOOP (a profiling build outside the library) adds the stamped two-wavefront step loop.
+//   * per-environment model variants (VAR): fixed- and floating-base kernels, straight-line and step loop, one wavefront
+//     per workgroup; no two-wavefront and no stamped variant build.
 template <typename T, typename TR, int KIND, int G, int NDP, typename F>
 bool tds_builds_of(F &f) {
   constexpr int LP_LOOP = NDP < 24 ? 2 : 1;
   constexpr bool TWO_WAVES = KIND == 0 && NDP <= 14;
   constexpr bool STAMPS = KIND == 0 && sizeof(T) == 8 && sizeof(TR) == 8;
-  if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND>, false, false, false)) return true;
-  if (f(tds_step_kernel<T, TR, G, NDP, false, LP_LOOP, KIND>, false, true, false)) return true;
+  constexpr bool VARIANTS = KIND == 0 || KIND == 1;
+  if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND>, false, false, false, false)) return true;
+  if (f(tds_step_kernel<T, TR, G, NDP, false, LP_LOOP, KIND>, false, true, false, false)) return true;
   if constexpr (TWO_WAVES) {
-    if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND, true>, false, false, true)) return true;
-    if (f(tds_step_kernel<T, TR, G, NDP, false, 1, KIND, true>, false, true, true)) return true;
+    if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND, true>, false, false, true, false)) return true;
+    if (f(tds_step_kernel<T, TR, G, NDP, false, 1, KIND, true>, false, true, true, false)) return true;
   }
   if constexpr (STAMPS) {
-    if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND>, true, false, false)) return true;
+    if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND>, true, false, false, false)) return true;
     if constexpr (TWO_WAVES) {
-      if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND, true>, true, false, true)) return true;
+      if (f(tds_step_kernel<T, TR, G, NDP, true, 0, KIND, true>, true, false, true, false)) return true;
 #ifdef TDS_PROF_LOOP
-      if (f(tds_step_kernel<T, TR, G, NDP, true, 1, KIND, true>, true, true, true)) return true;
+      if (f(tds_step_kernel<T, TR, G, NDP, true, 1, KIND, true>, true, true, true, false)) return true;
 #endif
     }
+  }
+  if constexpr (VARIANTS) {
+    if (f(tds_step_kernel<T, TR, G, NDP, false, 0, KIND, false, true>, false, false, false, true)) return true;
+    if (f(tds_step_kernel<T, TR, G, NDP, false, LP_LOOP, KIND, false, true>, false, true, false, true)) return true;
   }
   return false;
 }
@@ -3721,10 +3758,14 @@ int tds_launch_step_impl(const DevModel<T> *d_model, const DevModel<T> &h_model,
   const bool simple = ctl.nsub == 1 && ctl.reset_mode == TDS_RESET_NONE && ctl.policy == nullptr &&
                       ctl.obs_ring == nullptr && ctl.y_ring == nullptr;  // (record rings: the step-loop builds write them)
   const bool stamped = prof != nullptr;
+  // per-environment model variants (ctl.variant): the variant builds — one wavefront, no stamps; a kind that has none is
+  // an error of the caller (-2), never a launch of a build that would read one model for all
+  const bool variants = ctl.variant != nullptr;
   // (the step-loop compilation follows from the key — see the table; TDS_FORM_LOOP_OCC* have nothing left to choose from)
   auto launch = [&](bool loop, bool w2) {
-    return tds_visit_builds<T, TR, KIND>(lanes_per_env, L.NDP, [&](TdsStepKernelFn<T, TR> kernel, bool kstamped, bool kloop, bool kw2) {
-      if (kstamped != stamped || kloop != loop || kw2 != w2) return false;
+    return tds_visit_builds<T, TR, KIND>(lanes_per_env, L.NDP, [&](TdsStepKernelFn<T, TR> kernel, bool kstamped, bool kloop, bool kw2,
+                                                                     bool kvar) {
+      if (kstamped != stamped || kloop != loop || kw2 != w2 || kvar != variants) return false;
       hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kw2 ? 128 : 64), shmem, stream, d_model, L, x_in, y_out, actions,
                          x_feedback, obs_out, ovf, prof, ctl, n_envs);
       return true;
@@ -3732,9 +3773,9 @@ int tds_launch_step_impl(const DevModel<T> *d_model, const DevModel<T> &h_model,
   };
   // the two-wavefront build where the key has one, else the one-wavefront build; a stamped launch that has no step-loop
   // build takes the stamped straight-line one
-  int r = launch(!simple, two_waves);
-  if (r == 0 && two_waves) r = launch(!simple, false);
-  if (r == 0 && stamped && !simple) r = launch(false, false);
+  int r = launch(!simple, two_waves && !variants);
+  if (r == 0 && two_waves && !variants) r = launch(!simple, false);
+  if (r == 0 && stamped && !simple && !variants) r = launch(false, false);
   if (r < 0) return -1;
   if (r == 0) return -2;  // (phase stamps: plain kernels with double records only)
   return (int)hipGetLastError();
@@ -3744,7 +3785,7 @@ int tds_launch_step_impl(const DevModel<T> *d_model, const DevModel<T> &h_model,
 template <typename T, typename TR, int KIND>
 int tds_kernel_max_dynamic_lds_impl(int lanes_per_env, int ndp, int bytes) {
   hipError_t e = hipSuccess;
-  const int r = tds_visit_builds<T, TR, KIND>(lanes_per_env, ndp, [&](TdsStepKernelFn<T, TR> kernel, bool, bool, bool) {
+  const int r = tds_visit_builds<T, TR, KIND>(lanes_per_env, ndp, [&](TdsStepKernelFn<T, TR> kernel, bool, bool, bool, bool) {
     e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     return e != hipSuccess;
   });

@@ -43,8 +43,13 @@ struct TdsLaunchPlan {
 inline TdsLaunchPlan tds_launch_plan(const tds_hip_sim &s, const TdsLaunchReq &r) {
   const TdsOptions &o = s.opt;
   const bool c64 = s.compute_f64();
+  // Per-environment model variants installed (tds_hip_set_model_variants) are a fact of the handle like option oct = 0:
+  // the own kernels are tuned around ONE constant table per workgroup and decline, the general kernel's variant builds
+  // exist as one-wavefront workgroups only — the one-wave layout, never the two-wavefront form.
+  const bool variants = s.n_variants > 0;
   // (the own kernels of the star-shaped robots and the serial chains exist for double arithmetic only)
-  const int quad = c64 ? s.h64.quad : 0, oct = c64 ? s.h64.oct : 0, chain = c64 ? s.h64.chain : 0;
+  const int quad = (c64 && !variants) ? s.h64.quad : 0, oct = (c64 && !variants) ? s.h64.oct : 0;
+  const int chain = (c64 && !variants) ? s.h64.chain : 0;
   const bool floating = c64 ? s.h64.is_floating : s.h32.is_floating;
   const bool spherical = (c64 ? s.h64.num_spherical : s.h32.num_spherical) != 0;
   const bool two = (c64 ? s.h64.num_bodies : s.h32.num_bodies) >= 2;
@@ -70,7 +75,7 @@ inline TdsLaunchPlan tds_launch_plan(const tds_hip_sim &s, const TdsLaunchReq &r
   const int epw = 64 / s.lanes;
   const long long loop_w2 = o.get(TDS_OPT_LOOP_W2, 1);
   const bool w2_fits = s.w2_max_blocks > 0 && (n_res + epw - 1) / epw <= s.w2_max_blocks && r.reset_mode == TDS_RESET_NONE &&
-                       !r.rollout && !r.pool_pass && r.prof != 1;
+                       !r.rollout && !r.pool_pass && r.prof != 1 && !variants;
   const bool is_loop = r.nsub > 1 || r.rings;
   const bool exchanged = r.progress && o.get(TDS_OPT_EXCHANGE_W2, 1) == 0;
   const bool two_waves = w2_fits && (!is_loop || (loop_w2 != 0 && !exchanged && (loop_w2 != 2 || !r.pool_states) &&
@@ -194,7 +199,7 @@ inline TdsLaunchPlan tds_launch_plan(const tds_hip_sim &s, const TdsLaunchReq &r
   // exactly as at N = 1 and its slots are exchanged once it has completed (a wait beside that build gets onto a compute
   // unit only when the launch retires).  (Compares the workgroups of the kernel that takes the launch with the general
   // kernel's w2_max_blocks.)
-  p.exchange_after = o.get(TDS_OPT_EXCHANGE_W2, 1) != 0 && loop_w2 != 0 && s.w2_max_blocks > 0 &&
+  p.exchange_after = !variants && o.get(TDS_OPT_EXCHANGE_W2, 1) != 0 && loop_w2 != 0 && s.w2_max_blocks > 0 &&
                      p.blocks <= s.w2_max_blocks && s.lds_w2.NDP <= 16;
   return p;
 }

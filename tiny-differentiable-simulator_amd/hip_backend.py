@@ -125,6 +125,11 @@ def lib():
                                             C.c_int, C.c_void_p]
         PP = C.POINTER(Param)
         L.tds_hip_params_get.argtypes = [P, C.c_int, PP, C.c_void_p]
+        L.tds_hip_params_apply.argtypes = [P, C.c_int, PP, C.c_void_p, P]
+        L.tds_hip_set_model_variants.argtypes = [C.c_void_p, C.c_int, C.c_int, PP, C.c_void_p, C.c_void_p]
+        L.tds_hip_model_variants.argtypes = [C.c_void_p]
+        L.tds_hip_model_variants_host.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, PP, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_int64)]
         L.tds_hip_jvp_params.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PP] + [C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3
         L.tds_hip_vjp_params.argtypes = L.tds_hip_jvp_params.argtypes
@@ -370,7 +375,8 @@ EXPORTED_SYMBOLS = [
     "tds_hip_single_step_kernel", "tds_hip_launch_plan_host", "tds_hip_oct_window_plan_host",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
-    "tds_hip_params_get", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
+    "tds_hip_params_get", "tds_hip_params_apply", "tds_hip_set_model_variants", "tds_hip_model_variants",
+    "tds_hip_model_variants_host", "tds_hip_jvp_params", "tds_hip_vjp_params", "tds_hip_jvp_params_host",
     "tds_hip_vjp_params_host", "tds_hip_trajectory_jvp", "tds_hip_trajectory_jvp_host",
     "tds_hip_trajectory_vjp", "tds_hip_trajectory_vjp_host",
     "tds_hip_policy_trajectory_vjp", "tds_hip_policy_trajectory_vjp_host",
@@ -702,6 +708,56 @@ def params_get(m: _model.Model, params):
     theta = np.zeros(max(p, 1), dtype=np.float64)
     _check(lib().tds_hip_params_get(C.byref(m), p, sel, theta.ctypes.data))
     return theta[:p]
+
+
+def params_apply(m: _model.Model, params, theta) -> _model.Model:
+    """a copy of the model blob with the selected scalars set to theta [p] (tds_hip_params_apply: the inverse of
+    params_get, same checks; an off-diagonal inertia comp sets both mirror entries).  The model of a variant."""
+    import numpy as np
+
+    sel = param_spec(params)
+    p = len(params)
+    t = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1))
+    if t.shape[0] != p:
+        raise ValueError(f"theta: expected [{p}], got {tuple(np.shape(theta))}")
+    out = m.copy()
+    _check(lib().tds_hip_params_apply(C.byref(m), p, sel, t.ctypes.data if p else None, C.byref(out)))
+    return out
+
+
+def _variant_args(params, theta, env_variant, num_envs):
+    """(selection, p, theta [V, p] float64, V, map int32 [num_envs] or None) of a set of model variants; theta may be a
+    numpy array or a tensor on any device"""
+    import numpy as np
+
+    sel = param_spec(params)
+    p = len(params)
+    if hasattr(theta, "detach"):
+        theta = theta.detach().cpu().numpy()
+    t = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
+    if t.ndim != 2 or t.shape[1] != p:
+        raise ValueError(f"theta: expected [V, {p}], got {tuple(t.shape)}")
+    ev = None
+    if env_variant is not None:
+        if hasattr(env_variant, "detach"):
+            env_variant = env_variant.detach().cpu().numpy()
+        ev = np.ascontiguousarray(np.asarray(env_variant).astype(np.int32).reshape(-1))
+        if ev.shape[0] != num_envs:
+            raise ValueError(f"env_variant: expected [{num_envs}], got {tuple(np.shape(env_variant))}")
+    return sel, p, t, t.shape[0], ev
+
+
+def model_variants_host(m: _model.Model, params, theta, env_variant=None, num_envs: int | None = None, dtype: str = "f64"):
+    """the checks of HipSim.set_model_variants on the CPU (tds_hip_model_variants_host; needs no GPU) for a handle of
+    num_envs environments (default: one per variant); returns the bytes of the device array of the variants' models"""
+    import numpy as np
+
+    n = int(np.shape(theta)[0] if num_envs is None else num_envs)
+    sel, p, t, nv, ev = _variant_args(params, theta, env_variant, n)
+    nbytes = C.c_int64(0)
+    _check(lib().tds_hip_model_variants_host(C.byref(m), dtype_code(dtype), n, nv, p, sel, t.ctypes.data if t.size else None,
+                                             None if ev is None else ev.ctypes.data, C.byref(nbytes)))
+    return int(nbytes.value)
 
 
 def _theta_rows(theta, n, p):
@@ -1654,6 +1710,25 @@ class HipSim:
             assert tuple(obs.shape) == (self.num_envs, self.obs_dim + 2)
             op = C.c_void_p(obs.data_ptr())
         _check(lib().tds_hip_step_obs(self.h, ap, int(substeps), op))
+
+    def set_model_variants(self, params, theta, env_variant=None):
+        """per-environment model variants (tds_hip_set_model_variants): variant v is params_apply(model, params,
+        theta[v]), theta [V, p] a numpy array or a tensor on any device, params anything param_spec takes; environment e
+        steps under variant env_variant[e] (None with V == num_envs: its own).  Every stepping path then runs the
+        general kernel's variant builds; the derivative and query methods ignore the variants."""
+        sel, p, t, nv, ev = _variant_args(params, theta, env_variant, self.num_envs)
+        if nv == 0:
+            raise ValueError("theta: no variants (clear_model_variants() removes them)")
+        _check(lib().tds_hip_set_model_variants(self.h, nv, p, sel, t.ctypes.data if t.size else None,
+                                                None if ev is None else ev.ctypes.data))
+
+    def clear_model_variants(self):
+        """back to the handle's own model and kernel"""
+        _check(lib().tds_hip_set_model_variants(self.h, 0, 0, None, None, None))
+
+    @property
+    def num_model_variants(self) -> int:
+        return int(lib().tds_hip_model_variants(self.h))
 
     def set_auto_reset(self, enable: bool, seed: int = 0):
         """Reset (+ settle) environments whose step ends with done inside the step launch."""
