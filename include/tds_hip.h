@@ -1177,6 +1177,39 @@ int tds_rb_jvp_host(const tds_rb_model_t *model, int n, int steps, const double 
 /* theta [p] = the model's values of the selection (host arrays); checks the selection. */
 int tds_rb_params_get(const tds_rb_model_t *model, int p, const tds_param_t *params, double *theta);
 
+/* Reverse-mode derivatives of rollouts: the rollout of tds_rb_jvp, the state after every `every`-th step recorded in
+   s [n][n_rec][num_bodies][TDS_RB_STATE] (n_rec = steps / every; every must divide steps, every = steps gives s_T alone),
+   one cotangent gs [n][n_rec][num_bodies * TDS_RB_STATE] on the recorded states, and its gradients gs0
+   [n][num_bodies * TDS_RB_STATE] in s0 and gtheta [n][p] in theta: sum over the records of (d s_r / d [s0 | theta])^T gs_r.
+   s may be NULL; gs0 or gtheta may be NULL where not wanted; gtheta is not touched when p = 0.  The convention, the
+   selections, theta (NULL: the model's values), the checks and the scope are tds_rb_jvp's: the derivative of the
+   algorithm as executed, quaternion entries raw, f64 handles only (an f32 handle gives TDS_ERR_UNSUPPORTED), any
+   n >= 1, the resident state untouched, enqueued on the handle's stream (the call waits for its launches: it reports
+   overflows).
+   A primal pass keeps the state after every step; the steps' tapes are then recorded a window of W steps at a time,
+   one lane per (step, world), and swept back once; only the state cotangent crosses window boundaries.
+   tape_cap: the entries one step's tape of one world may hold; 0: a bound derived from the model (collision spheres of
+   the pairs the dispatcher accepts x solver_iterations x the entries of one narrowphase + solve, plus gravity and
+   integrate), capped by what work_bytes leaves for one step of 64 worlds.  A world one of whose steps overflows gets NaN
+   in gs0 and gtheta and the call returns TDS_ERR_UNSUPPORTED ("tape exceeds the capacity"); the other worlds' results
+   stand.  A collision sphere that ends without an impulse leaves no entries, so a scene whose contacts are few next to
+   its pairs (billiards: 350 to 11 765 entries per step against a bound of 336 448) is served far better by an explicit
+   tape_cap: the tapes' strides, hence W, follow the capacity.
+   work_bytes: the upper bound on the handle's work buffer for this call (0: 8 GiB); it decides W and the worlds per
+   pass (whole wavefronts), never the results.  One that cannot hold one step of 64 worlds gives TDS_ERR_INVALID_ARG; the
+   message names the size needed.  tds_rb_vjp_plan tells what a call would choose, without a device:
+   plan[4] = tape capacity | worlds per pass | W | bytes of work buffer. */
+int tds_rb_vjp(tds_rb_sim_t *sim, int n, int steps, int every, const void *s0_dev, int p,
+               const tds_param_t *params_host, const void *theta_dev, const void *gs_dev, void *s_dev, void *gs0_dev,
+               void *gtheta_dev, int tape_cap, size_t work_bytes);
+/* The same templates on the CPU (host arrays, needs no GPU), one world and one tape at a time: the checker of
+   tds_rb_vjp. */
+int tds_rb_vjp_host(const tds_rb_model_t *model, int n, int steps, int every, const double *s0, int p,
+                    const tds_param_t *params, const double *theta, const double *gs, double *s, double *gs0,
+                    double *gtheta, int tape_cap);
+int tds_rb_vjp_plan(const tds_rb_model_t *model, int n, int steps, int p, int tape_cap, size_t work_bytes,
+                    long long *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ _StepFunction = None
 _StepFunctionReverse = None
 _ParamStepFunction = None
 _RbRolloutFunction = None
+_RbRolloutReverseFunction = None
 _TrajectoryFunction = None
 _TrajectoryReverseFunction = None
 
@@ -201,7 +202,54 @@ def _rb_rollout_function():
     return _RbRolloutFunction
 
 
-def rb_rollout_fn(sim, steps: int, wrt, params=()):
+def _rb_rollout_reverse_function():
+    global _RbRolloutReverseFunction
+    if _RbRolloutReverseFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class RbRolloutReverseFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, u, theta, s0, sim, steps, every, idx, params):
+                n, nb = s0.shape[0], sim.model.num_bodies
+                s = s0.detach().reshape(n, -1).clone()
+                s[:, idx] = u.detach().to(s.dtype)
+                s = s.reshape(n, nb, -1)
+                th = None if theta is None else theta.detach()
+                ctx.shared = th is not None and th.dim() == 1
+                ctx.has_theta = th is not None
+                ctx.sim, ctx.steps, ctx.every, ctx.idx, ctx.params = sim, steps, every, idx, params
+                ctx.save_for_backward(*(t for t in (s, th) if t is not None))
+                if every is None:
+                    return sim.jvp(s, None, steps, params, th)[0]
+                # the records: the primal kernel chained, `every` steps per launch (the same steps, bit for bit)
+                out, cur = [], s
+                for _ in range(steps // every):
+                    cur = sim.jvp(cur, None, every, params, th)[0]
+                    out.append(cur)
+                return torch.stack(out, 1)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_s):
+                saved = list(ctx.saved_tensors)
+                s = saved.pop(0)
+                th = saved.pop(0) if ctx.has_theta else None
+                _, gs0, gth = ctx.sim.vjp(s, grad_s.to(s.dtype).contiguous(), ctx.steps, ctx.params, th, ctx.every)
+                n = s.shape[0]
+                if ctx.shared:  # one theta for every world: its gradient sums over them
+                    gth = gth.sum(0)
+                gu = gs0.reshape(n, -1)[:, ctx.idx]
+                # the entries wrt were overwritten by u: s0's own gradient is zero there
+                g0 = gs0.reshape(n, -1).clone()
+                g0[:, ctx.idx] = 0.0
+                return gu, (gth if ctx.has_theta else None), g0.reshape(gs0.shape), None, None, None, None, None
+
+        _RbRolloutReverseFunction = RbRolloutReverseFunction
+    return _RbRolloutReverseFunction
+
+
+def rb_rollout_fn(sim, steps: int, wrt, params=(), mode: str = "forward", every=None):
     """(s0, u, theta=None) -> s_T: `steps` World::steps of a RigidBodySim (f64) from s0 [N, num_bodies, 13] with the
     state entries wrt (a list of (body, comp), comp 0..12 of position | quaternion xyzw | linear | angular velocity)
     overwritten by u [N, len(wrt)], differentiable in u and theta.
@@ -209,9 +257,20 @@ def rb_rollout_fn(sim, steps: int, wrt, params=()):
     params: a selection of ("mass", body), ("gravity", comp), ("friction",), ("restitution",) (hip_backend.param_spec);
     theta: None (the model's values), [p] shared by every world (its gradient is summed over them) or [N, p].  Where u
     or theta requires grad, the forward pass computes the len(wrt) + p needed columns of d s_T / d [u | theta] with
-    RigidBodySim.jvp and backward is J^T grad.  s0 itself is not differentiated: s0.requires_grad raises."""
+    RigidBodySim.jvp and backward is J^T grad.  s0 itself is not differentiated: s0.requires_grad raises.
+
+    mode "reverse": the forward pass keeps only its inputs and backward is one RigidBodySim.vjp, whatever the number of
+    inputs: differentiable in u, in theta and in s0 itself (its entries wrt excepted: u overwrites them).  With `every`
+    given (reverse mode only) the result is the states after every, 2 every, .., steps steps, [N, n_rec, num_bodies, 13],
+    so that a loss may read intermediate states of the roll."""
     from . import hip_backend
 
+    if mode not in ("forward", "reverse"):
+        raise ValueError(f"rb_rollout_fn: mode must be 'forward' or 'reverse', not {mode!r}")
+    if every is not None and mode != "reverse":
+        raise ValueError("rb_rollout_fn: every needs mode='reverse' (forward mode returns the final state alone)")
+    if every is not None and (int(every) < 1 or int(steps) % int(every)):
+        raise ValueError(f"rb_rollout_fn: every ({every}) must divide steps ({steps})")
     nb = sim.model.num_bodies
     p = len(params)
     sel = hip_backend.param_spec(params)
@@ -220,16 +279,31 @@ def rb_rollout_fn(sim, steps: int, wrt, params=()):
     fn = _rb_rollout_function()
     cache = {}
 
+    def check(u, theta):
+        if u.dim() != 2 or u.shape[1] != len(idx):
+            raise ValueError(f"rb_rollout_fn: u must be [N, {len(idx)}], got {tuple(u.shape)}")
+        if theta is not None and p == 0:
+            raise ValueError("rb_rollout_fn: theta given but no params selected")
+
+    if mode == "reverse":
+        rev = _rb_rollout_reverse_function()
+
+        def fr(s0, u, theta=None):
+            import torch
+
+            check(u, theta)
+            ix = torch.tensor(idx, dtype=torch.long, device=s0.device)
+            return rev.apply(u, theta, s0, sim, int(steps), None if every is None else int(every), ix, spec)
+
+        return fr
+
     def f(s0, u, theta=None):
         import torch
 
         if s0.requires_grad:
             raise ValueError("rb_rollout_fn: s0 is not differentiated (only the entries wrt, through u): detach s0 "
                              "or list the entries in wrt")
-        if u.dim() != 2 or u.shape[1] != len(idx):
-            raise ValueError(f"rb_rollout_fn: u must be [N, {len(idx)}], got {tuple(u.shape)}")
-        if theta is not None and p == 0:
-            raise ValueError("rb_rollout_fn: theta given but no params selected")
+        check(u, theta)
         key = str(s0.device)
         if key not in cache:
             cache[key] = hip_backend.rb_directions(nb, wrt, p, device=s0.device)

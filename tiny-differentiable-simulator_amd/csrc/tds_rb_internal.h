@@ -1,5 +1,5 @@
-// tds_rb_internal.h — the handle behind tds_rb_sim_t, shared by tds_rb.hip (stepping) and tds_rb_diff.hip (forward-mode
-// rollout derivatives).  Not part of the C ABI.
+// tds_rb_internal.h — the handle behind tds_rb_sim_t, shared by tds_rb.hip (stepping), tds_rb_diff.hip (forward-mode
+// rollout derivatives) and tds_rb_vjp.hip (reverse mode).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +17,8 @@ struct tds_rb_sim {
   RbDev<double> h64;
   RbDev<float> h32;
   std::vector<float> stage;
-  // tds_rb_jvp: tangents of the launch's lanes and the parameter selection, grown as needed, kept for the next call
+  // tds_rb_jvp: tangents of the launch's lanes; tds_rb_vjp: state store, tapes and adjoints.  Grown as needed, kept for
+  // the next call
   void *d_work = nullptr;
   size_t work_bytes = 0;
 };

@@ -1,4 +1,5 @@
-// tds_rb_step.h — one statement of World::step for worlds of free rigid bodies (tds_rb.hip, tds_rb_diff.hip).
+// tds_rb_step.h — one statement of World::step for worlds of free rigid bodies (tds_rb.hip, tds_rb_diff.hip,
+// tds_rb_vjp.hip).
 //
 // Reference: src/world.hpp:293-366 (step: gravity impulse, pairwise narrowphase, num_solver_iterations sweeps of
 // RigidBodyConstraintSolver::resolve_collision over the contacts, integrate), src/rigid_body.hpp:26-123,
@@ -6,7 +7,8 @@
 //
 // tds_rb_world_steps<T, R>(M, S, steps) is a __host__ __device__ template over the state scalar T and a state
 // accessor S; R is the real type of the model table RbDev<R>.  tds_rb_diff.hip instantiates it for T = TdsDual<K> and
-// double, on the device and on the host.  It is the arithmetic of tds_rb_kernel (tds_rb.hip), which keeps its own
+// double, tds_rb_vjp.hip for TdsRev (reverse mode) and double, each on the device and on the host.  It is the
+// arithmetic of tds_rb_kernel (tds_rb.hip), which keeps its own
 // statement: instantiated from this template, the kernel's f64 build compiled to the same code, but its f32 build
 // vectorised differently and changed results in the last bits ("Rigid-body rollouts").  The model table,
 // its builder and the vector helpers are shared.
@@ -116,6 +118,17 @@ __host__ __device__ __forceinline__ TdsDual<K> rb_sqrt(const TdsDual<K> &x) {
   return tds_sqrt(x);
 }
 
+// Hooks of a recording scalar type (reverse mode, tds_rb_vjp.hip overloads them for TdsRev): the tape position at the top
+// of a collision sphere's narrowphase, and the return to it where the sphere ends without an impulse.  Nothing computed
+// since the mark is then read again and no state was written, so what a tape recorded in between is dead.  Every other
+// scalar type has no tape: the hooks are empty and compile to nothing.
+template <typename T>
+__host__ __device__ __forceinline__ int rb_tape_mark(const T *) {
+  return 0;
+}
+template <typename T>
+__host__ __device__ __forceinline__ void rb_tape_rewind(const T *, int) {}
+
 // `steps` World::step calls on the world behind S
 template <typename T, typename R, typename S>
 __host__ __device__ __forceinline__ void tds_rb_world_steps(const RbDev<R> &M, S &s, int steps) {
@@ -156,6 +169,7 @@ __host__ __device__ __forceinline__ void tds_rb_world_steps(const RbDev<R> &M, S
           const T pe[3] = {s.get(eb, 0), s.get(eb, 1), s.get(eb, 2)};
           const R rad = M.radius[eb];
           for (int sx = 0; sx < M.ns[eb]; ++sx) {
+          const int mark = rb_tape_mark((const T *)nullptr);
           T ctr[3];
           if (M.type[eb] == TDS_GEOM_SPHERE) {
             ctr[0] = pe[0]; ctr[1] = pe[1]; ctr[2] = pe[2];
@@ -202,7 +216,10 @@ __host__ __device__ __forceinline__ void tds_rb_world_steps(const RbDev<R> &M, S
             }
           }
           // RigidBodyConstraintSolver::resolve_collision (rb_constraint_solver.hpp:112-165)
-          if (!(got && dist < R(0))) continue;
+          if (!(got && dist < R(0))) {
+            rb_tape_rewind((const T *)nullptr, mark);
+            continue;
+          }
           T ra[3], rb[3], wa[3], wb[3], va[3], vb[3], rel[3], t3[3];
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
@@ -221,7 +238,10 @@ __host__ __device__ __forceinline__ void tds_rb_world_steps(const RbDev<R> &M, S
 #pragma unroll
           for (int k = 0; k < 3; ++k) rel[k] = va[k] - vb[k];
           const T nrv = dot3(nbv, rel);
-          if (!(nrv < R(0))) continue;
+          if (!(nrv < R(0))) {
+            rb_tape_rewind((const T *)nullptr, mark);
+            continue;
+          }
           T t1[3], t2[3], x1[3], x2[3], sum[3];
           cross3(ra, nbv, t1);
           cross3(rb, nbv, t2);
@@ -237,7 +257,10 @@ __host__ __device__ __forceinline__ void tds_rb_world_steps(const RbDev<R> &M, S
           const T ang = dot3(nbv, sum);
           const T denom = s.inv_mass(i) + s.inv_mass(j) + ang;
           const T impulse = (-(R(1) + s.restitution()) * nrv - baumgarte) / denom;
-          if (!(impulse > R(0))) continue;
+          if (!(impulse > R(0))) {
+            rb_tape_rewind((const T *)nullptr, mark);
+            continue;
+          }
           T iv[3], miv[3];
 #pragma unroll
           for (int k = 0; k < 3; ++k) {

@@ -154,6 +154,10 @@ def lib():
             [C.c_void_p] * 3
         L.tds_rb_jvp_host.argtypes = [RP, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3
+        L.tds_rb_vjp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, PP] + [C.c_void_p] * 5 + \
+            [C.c_int, C.c_size_t]
+        L.tds_rb_vjp_host.argtypes = [RP] + [C.c_int] * 3 + [C.c_void_p, C.c_int, PP] + [C.c_void_p] * 5 + [C.c_int]
+        L.tds_rb_vjp_plan.argtypes = [RP] + [C.c_int] * 4 + [C.c_size_t, C.POINTER(C.c_longlong)]
         DP = C.POINTER(DynOut)
         L.tds_hip_dynamics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [DP]
         L.tds_hip_inverse_dynamics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
@@ -386,6 +390,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
+    "tds_rb_vjp", "tds_rb_vjp_host", "tds_rb_vjp_plan",
 ]
 
 
@@ -1059,6 +1064,49 @@ def rb_jvp_host(m: _model.RbModel, s0, steps: int, v=None, params=(), theta=None
     _rb_check(lib().tds_rb_jvp_host(C.byref(m), n, int(steps), s0.ctypes.data, p, sel, thp, k, v3.ctypes.data,
                                     sT.ctypes.data, jv.ctypes.data))
     return sT, (jv[:, 0] if squeeze else jv)
+
+
+def _rb_every(steps, every):
+    """every None: the final state alone (every = steps)"""
+    return int(steps) if every is None else int(every)
+
+
+def rb_vjp_host(m: _model.RbModel, s0, steps: int, gs, params=(), theta=None, every=None, tape_cap: int = 0):
+    """Reverse-mode rollout derivative on the CPU (tds_rb_vjp_host; the checker of RigidBodySim.vjp, needs no GPU).
+
+    s0 [N, num_bodies, 13]; the state after every `every`-th step is recorded (None: the final state alone), gs
+    [N, n_rec, num_bodies * 13] (or anything of that many entries: [N, num_bodies, 13] for one record) is the cotangent on
+    the records; theta None (the model's values), [p] or [N, p].  Returns (s [N, n_rec, num_bodies, 13], gs0
+    [N, num_bodies, 13], gtheta [N, p]).  tape_cap: entries one step's tape may hold (0: the model's bound); a world
+    that overflows gets NaN gradients and the call raises."""
+    import numpy as np
+
+    nb = m.num_bodies
+    ns = nb * _model.TDS_RB_STATE
+    s0 = np.ascontiguousarray(s0, dtype=np.float64).reshape(-1, nb, _model.TDS_RB_STATE)
+    n, p = s0.shape[0], len(params)
+    every = _rb_every(steps, every)
+    n_rec = int(steps) // every if every >= 1 and steps >= 1 else 1
+    gs = np.ascontiguousarray(gs, dtype=np.float64)
+    if gs.size != n * n_rec * ns:
+        raise ValueError(f"gs: expected [{n}, {n_rec}, {ns}], got {tuple(gs.shape)}")
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    s = np.zeros((n, n_rec, nb, _model.TDS_RB_STATE))
+    gs0 = np.zeros_like(s0)
+    gth = np.zeros((n, max(p, 1)))
+    _rb_check(lib().tds_rb_vjp_host(C.byref(m), n, int(steps), every, s0.ctypes.data, p, sel,
+                                    None if th is None else th.ctypes.data, gs.ctypes.data, s.ctypes.data,
+                                    gs0.ctypes.data, gth.ctypes.data, int(tape_cap)))
+    return s, gs0, gth[:, :p]
+
+
+def rb_vjp_plan(m: _model.RbModel, n: int, steps: int, p: int = 0, tape_cap: int = 0, work_bytes: int = 0):
+    """(tape capacity, worlds per pass, steps per window W, bytes of work buffer) a RigidBodySim.vjp call would choose
+    (tds_rb_vjp_plan; needs no GPU)"""
+    out = (C.c_longlong * 4)()
+    _rb_check(lib().tds_rb_vjp_plan(C.byref(m), int(n), int(steps), int(p), int(tape_cap), int(work_bytes), out))
+    return tuple(int(x) for x in out)
 
 
 def jacobian_tangents(m: _model.Model) -> int:
@@ -2070,6 +2118,41 @@ class RigidBodySim:
         else:
             sT = self.jvp(s0, None, steps, params, theta)[0]
         return sT, (jv[:, 0] if squeeze else jv)
+
+    def vjp(self, s0, gs, steps: int, params=(), theta=None, every=None, tape_cap: int = 0, work_bytes: int = 0):
+        """(s, gs0, gtheta): `steps` World::steps from s0 [N, num_bodies, 13] (any N), the state after every `every`-th
+        step recorded in s [N, n_rec, num_bodies, 13] (every None: the final state alone), and the gradients of
+        sum(gs * s) in s0 (gs0 [N, num_bodies, 13]) and theta (gtheta [N, p]) in reverse mode (tds_rb_vjp).  gs: the
+        cotangent on the records, [N, n_rec, num_bodies * 13] or any shape of that many entries.  params, theta: as
+        jvp's.  tape_cap: entries one step's tape of one world may hold (0: the model's bound); work_bytes: the bound on
+        the work buffer (0: 8 GiB): it decides windows and passes, never the results (hip_backend.rb_vjp_plan).  A world
+        that overflows its tape gets NaN gradients and the call raises.  The resident state is not touched.  f64
+        handles only; the call waits for its launches."""
+        import torch
+
+        nb = self.model.num_bodies
+        ns = nb * _model.TDS_RB_STATE
+        assert s0.is_cuda and s0.dtype == torch.float64
+        s0 = s0.reshape(-1, nb, _model.TDS_RB_STATE).contiguous()
+        n, p = s0.shape[0], len(params)
+        every = _rb_every(steps, every)
+        n_rec = int(steps) // every if every >= 1 and steps >= 1 else 1
+        assert gs.is_cuda and gs.dtype == torch.float64 and gs.numel() == n * n_rec * ns, (tuple(gs.shape), n, n_rec, ns)
+        gs = gs.contiguous()
+        sel = param_spec(params)
+        th = None
+        if theta is not None:
+            assert theta.is_cuda and theta.dtype == torch.float64
+            th = (theta.unsqueeze(0).expand(n, p) if theta.dim() == 1 else theta).contiguous()
+            assert tuple(th.shape) == (n, p), (tuple(th.shape), n, p)
+        s = torch.empty((n, n_rec, nb, _model.TDS_RB_STATE), dtype=torch.float64, device=s0.device)
+        gs0 = torch.empty_like(s0)
+        gth = torch.empty((n, p), dtype=torch.float64, device=s0.device)
+        _rb_check(lib().tds_rb_vjp(self.h, n, int(steps), every, C.c_void_p(s0.data_ptr()), p, sel,
+                                   None if th is None else C.c_void_p(th.data_ptr()), C.c_void_p(gs.data_ptr()),
+                                   C.c_void_p(s.data_ptr()), C.c_void_p(gs0.data_ptr()),
+                                   C.c_void_p(gth.data_ptr()) if p else None, int(tape_cap), int(work_bytes)))
+        return s, gs0, gth
 
     def jacobian(self, s0, steps: int, wrt, params=(), theta=None):
         """dense d s_T / d [s0 entries wrt | theta]: [N, num_bodies * 13, len(wrt) + p] from unit directions.  wrt: a
