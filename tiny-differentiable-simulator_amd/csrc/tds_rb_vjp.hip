@@ -5,7 +5,8 @@
 // `every`-th step recorded, one cotangent gs on the recorded states, and its gradients in s0 and in theta.  The
 // derivative is that of the algorithm as executed, as in forward mode: every test of the step reads values only.
 //
-// The form is tds_traj_vjp.hip's:
+// The form is that of tds_rollout_vjp.h, which holds the chained sweep, its seed and the launch loop over chunks and
+// windows; this unit supplies the kernels that are its own:
 //   primal      one lane per world, the double instantiation with the values in LDS [component][lane] as
 //               tds_rb_jvp_kernel<0> keeps them; the state after every step goes into a state store [n][steps][nb * 13]
 //               in the work buffer, s is copied out of it.
@@ -16,10 +17,9 @@
 //               without an impulse leaves no entries (rb_tape_mark / rb_tape_rewind).  The values stay in LDS; the
 //               variable indices live in the work buffer [component][lane], lane minor (one coalesced 256 B run per
 //               wave-uniform access), as tds_rb_jvp keeps its tangents.  Tape layout [wavefront][position][lane].
-//   chained     one wavefront per 64 worlds walks t from the window's last step to its first: zero the ring and the
-//   sweep       input parts, seed lambda (+ gs at a recorded step), tds_vjp_sweep, scatter: the state part is the next
-//               lambda (t = 0: gs0), the theta part accumulates into gtheta by plain read-modify-write (a world
-//               belongs to one lane, t descending).  lambda [nb * 13][n] lives in the work buffer.
+//   chained     tds_rollout_vjp_sweep over RbVjpProblem: every world inside [0, n) is live; the scatter's state part
+//   sweep       is the next lambda (t = 0: gs0), its theta part accumulates into gtheta.  lambda [nb * 13][n] lives in
+//               the work buffer.
 //   NaN pass    NaN gradients for the worlds one of whose steps overflowed its tape.
 // Only copies and lambda cross window and chunk boundaries, and chunks are whole wavefronts: the results do not depend
 // on W or the chunk.  The unit is built without FP contraction (Makefile), as tds_rb_diff.hip: device and host round
@@ -33,10 +33,7 @@
 #include <vector>
 
 #include "tds_rb_diff.h"
-#include "tds_rev.h"
-
-// the sweep of tds_vjp_kernels.h needs the articulated side's internals for its other templates only
-#include "tds_vjp_kernels.h"
+#include "tds_rollout_vjp.h"
 
 // found by argument-dependent lookup where tds_rb_world_steps<TdsRev> is instantiated
 __host__ __device__ __forceinline__ TdsRev rb_sqrt(const TdsRev &x) { return tds_sqrt(x); }
@@ -66,22 +63,6 @@ struct RbVjpArgs {
   int *overflow;                  // set where a lane's tape overflows
 };
 
-// c into an adjoint's far part / its value (device: as tds_vjp_sweep_kernel seeds and reads them)
-__host__ __device__ inline void rb_vjp_add(double *p, double c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsafeAtomicAdd(p, c);
-#else
-  *p += c;
-#endif
-}
-__host__ __device__ inline double rb_vjp_ld(const double *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  return *p;
-#endif
-}
-
 // the state entering step t of world w
 __host__ __device__ inline const double *rb_vjp_state(const RbVjpArgs &a, long long w, int t) {
   return t > 0 ? a.store + ((size_t)w * a.steps + (t - 1)) * a.ns : a.s0 + (size_t)w * a.ns;
@@ -98,32 +79,22 @@ __host__ __device__ __forceinline__ void rb_vjp_record(const RbVjpArgs &a, const
   tds_rb_world_steps<TdsRev>(M, acc, 1);
 }
 
-// seeds of step t's sweep: adj[y_h] += lambda_h (+ gs_h where step t is recorded).  yi: the variables of the step's
-// outputs, lam: lambda, adj: the lane's adjoints; entry h at [h * stride]
-__host__ __device__ inline void rb_vjp_seed(const RbVjpArgs &a, long long w, int t, const int *yi, long long ys,
-                                            const double *lam, long long ls, double *adj, long long as) {
-  const bool rec = (t + 1) % a.every == 0;
-  const double *g = a.gs + ((size_t)w * a.n_rec + (rec ? (t + 1) / a.every - 1 : 0)) * a.ns;
-  for (int h = 0; h < a.ns; ++h) {
-    const int v = yi[h * ys];
-    if (v < 0) continue;  // a constant
-    double c = lam[h * ls];
-    if (rec) c += g[h];
-    rb_vjp_add(adj + v * as, c);
+// the rollout as tds_rollout_vjp.h sees it: every world inside [0, n) is live
+struct RbVjpProblem {
+  const RbVjpArgs &a;
+  __host__ __device__ TdsRolloutShape shape() const { return {a.n, a.ns, a.every, a.n_rec, a.gs}; }
+  __device__ bool live(long long w) const { return w < a.n; }
+  // the input adjoints of step t's sweep: the state part is the next lambda (t = 0: gs0), theta's is added to gtheta
+  __host__ __device__ void scatter(int w, int t, const double *adj, long long as, double *lam, long long ls) const {
+    if (t > 0) {
+      for (int h = 0; h < a.ns; ++h) lam[h * ls] = tds_rollout_vjp_load(adj + h * as);
+    } else if (a.gs0) {
+      for (int h = 0; h < a.ns; ++h) a.gs0[(size_t)w * a.ns + h] = tds_rollout_vjp_load(adj + h * as);
+    }
+    if (a.gtheta)
+      for (int j = 0; j < a.p; ++j) a.gtheta[(size_t)w * a.p + j] += tds_rollout_vjp_load(adj + (a.ns + j) * as);
   }
-}
-
-// the input adjoints of step t's sweep: the state part is the next lambda (t = 0: gs0), theta's is added to gtheta
-__host__ __device__ inline void rb_vjp_scatter(const RbVjpArgs &a, long long w, int t, const double *adj, long long as,
-                                               double *lam, long long ls) {
-  if (t > 0) {
-    for (int h = 0; h < a.ns; ++h) lam[h * ls] = rb_vjp_ld(adj + h * as);
-  } else if (a.gs0) {
-    for (int h = 0; h < a.ns; ++h) a.gs0[(size_t)w * a.ns + h] = rb_vjp_ld(adj + h * as);
-  }
-  if (a.gtheta)
-    for (int j = 0; j < a.p; ++j) a.gtheta[(size_t)w * a.p + j] += rb_vjp_ld(adj + (a.ns + j) * as);
-}
+};
 
 __host__ __device__ inline void rb_vjp_nan(const RbVjpArgs &a, long long w) {
   const double nan = __builtin_nan("");
@@ -163,12 +134,7 @@ __global__ __launch_bounds__(64) void tds_rb_vjp_primal_kernel(const RbDev<doubl
 __global__ __launch_bounds__(256) void tds_rb_vjp_select_kernel(const double *__restrict__ store,
                                                                 double *__restrict__ s, long long n_items, int steps,
                                                                 int every, int n_rec, int ns) {
-  const long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (it >= n_items) return;
-  const long long w = it / n_rec, r = it % n_rec;
-  const double *src = store + (w * steps + (r + 1) * every - 1) * ns;
-  double *dst = s + it * ns;
-  for (int i = 0; i < ns; ++i) dst[i] = src[i];
+  tds_rollout_vjp_select(store, s, n_items, steps, every, n_rec, ns);
 }
 
 // ---------------------------------------------------------------- recording
@@ -229,34 +195,11 @@ __global__ __launch_bounds__(64) void tds_rb_vjp_record_kernel(const RbDev<doubl
 }
 
 // ---------------------------------------------------------------- chained sweep
-// steps t1 - 1 .. t0 of worlds e0 + 64 blockIdx.x ..: tds_vjp_sweep per step, lambda [ns][n] between them
+// steps t1 - 1 .. t0 of worlds e0 + 64 blockIdx.x ..: lambda [ns][n] between them
 __global__ __launch_bounds__(64) void tds_rb_vjp_sweep_kernel(RbVjpArgs a, int e0, int nblk, int t0, int t1, int cap,
                                                               const int *lens, const int *yidx, TdsRevIdx *ix,
                                                               TdsRevPart *pd, double *adj, double *lam) {
-  const int l = threadIdx.x, nin = a.ns + a.p;
-  const long long blk = blockIdx.x, world = e0 + blk * 64 + l;
-  __shared__ double ring[kVjpRing * 64];  // the near parts of the adjoints, [slot][lane]
-  __shared__ int top_s;                   // the wavefront's longest tape of the step
-  const bool live = world < a.n;
-  double *adj_w = adj + blk * ((long long)nin + cap) * 64;
-  double *adj_l = adj_w + l, *ring_l = ring + l, *lam_l = lam + world;
-  for (int t = t1 - 1; t >= t0; --t) {
-    const long long wave = (long long)(t - t0) * nblk + blk;
-    const int len_t = live ? lens[wave * 64 + l] : -1;
-    const int len = len_t > 0 ? len_t : 0;  // a lane without a tape sweeps nothing
-    __syncthreads();
-    if (l == 0) top_s = 0;
-    __syncthreads();
-    if (len > 0) atomicMax(&top_s, len);
-    __syncthreads();
-    const int top = top_s;
-    const TdsRevTape tp = {ix + wave * cap * 64, pd + wave * cap * 64, adj_w, 64, cap, nin};
-    for (int s = 0; s < kVjpRing; ++s) ring_l[s * 64] = 0.0;
-    for (int i = 0; i < nin; ++i) adj_l[(long long)i * 64] = 0.0;
-    if (len_t >= 0) rb_vjp_seed(a, world, t, yidx + wave * a.ns * 64 + l, 64, lam_l, a.n, adj_l, 64);
-    tds_vjp_sweep(tp, ring_l, l, len, top);
-    if (len_t >= 0) rb_vjp_scatter(a, world, t, adj_l, 64, lam_l, a.n);
-  }
+  tds_rollout_vjp_sweep(RbVjpProblem{a}, e0, nblk, t0, t1, cap, a.ns + a.p, lens, yidx, ix, pd, adj, lam);
 }
 
 // the last pass: NaN gradients where a step's tape overflowed
@@ -283,8 +226,6 @@ int rb_vjp_cap_bound(const tds_rb_model_t *m, int p) {
   return b > (1 << 30) ? 1 << 30 : (int)b;
 }
 
-inline size_t rb_vjp_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the work buffer: overflow flag | state store | over | lambda | lengths | output variables | variable indices | tape
 // indices | tape partials | adjoints, for windows of W steps of `chunk` worlds
 struct RbVjpLayout {
@@ -292,15 +233,15 @@ struct RbVjpLayout {
   RbVjpLayout(int n, int steps, int nb, int p, size_t cap, size_t chunk, size_t W) {
     const size_t ns = (size_t)nb * TDS_RB_STATE, rec = W * chunk;
     store = 256;
-    over = store + rb_vjp_align((size_t)n * steps * ns * sizeof(double));
-    lam = over + rb_vjp_align((size_t)n * sizeof(int));
-    lens = lam + rb_vjp_align((size_t)n * ns * sizeof(double));
-    yidx = lens + rb_vjp_align(rec * sizeof(int));
-    vi = yidx + rb_vjp_align(rec * ns * sizeof(int));
-    ix = vi + rb_vjp_align(rec * nb * RB_NCD * sizeof(int));
-    pd = ix + rb_vjp_align(rec * cap * sizeof(TdsRevIdx));
-    adj = pd + rb_vjp_align(rec * cap * sizeof(TdsRevPart));
-    total = adj + rb_vjp_align(chunk * (ns + p + cap) * sizeof(double));
+    over = store + tds_vjp_align((size_t)n * steps * ns * sizeof(double));
+    lam = over + tds_vjp_align((size_t)n * sizeof(int));
+    lens = lam + tds_vjp_align((size_t)n * ns * sizeof(double));
+    yidx = lens + tds_vjp_align(rec * sizeof(int));
+    vi = yidx + tds_vjp_align(rec * ns * sizeof(int));
+    ix = vi + tds_vjp_align(rec * nb * RB_NCD * sizeof(int));
+    pd = ix + tds_vjp_align(rec * cap * sizeof(TdsRevIdx));
+    adj = pd + tds_vjp_align(rec * cap * sizeof(TdsRevPart));
+    total = adj + tds_vjp_align(chunk * (ns + p + cap) * sizeof(double));
   }
 };
 
@@ -405,31 +346,25 @@ int rb_vjp_run(tds_rb_sim *s, RbVjpArgs a, const RbSel &sel, const RbVjpPlan &pl
     RB_VJP_TRY(hipGetLastError());
   }
 
-  // the far parts start at zero; every sweep leaves those of its tape's variables at zero again (inputs: zeroed before
-  // each sweep), so one fill serves all windows and chunks
-  RB_VJP_TRY(hipMemsetAsync(ws + lay.adj, 0, lay.total - lay.adj, st));
   int *lens = (int *)(ws + lay.lens), *yidx = (int *)(ws + lay.yidx), *vi = (int *)(ws + lay.vi);
   TdsRevIdx *ix = (TdsRevIdx *)(ws + lay.ix);
   TdsRevPart *pd = (TdsRevPart *)(ws + lay.pd);
-  const int n_win = (steps + pl.W - 1) / pl.W, max_blk = (int)(pl.chunk / 64);
-  for (long long e0 = 0; e0 < n; e0 += pl.chunk) {
-    const long long left = ((long long)n - e0 + 63) / 64;
-    const int nblk = left < max_blk ? (int)left : max_blk;
-    for (int w = n_win - 1; w >= 0; --w) {
-      const int t0 = w * pl.W, t1 = t0 + pl.W < steps ? t0 + pl.W : steps;
-      hipLaunchKernelGGL(tds_rb_vjp_record_kernel, dim3((unsigned)((t1 - t0) * nblk)), dim3(64), lds, st, Mp, a, sel,
-                         (int)e0, nblk, t0, cap, over, lens, yidx, vi, ix, pd);
-      RB_VJP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(tds_rb_vjp_sweep_kernel, dim3((unsigned)nblk), dim3(64), 0, st, a, (int)e0, nblk, t0, t1, cap,
-                         lens, yidx, ix, pd, (double *)(ws + lay.adj), lam);
-      RB_VJP_TRY(hipGetLastError());
-    }
-  }
+  double *adj = (double *)(ws + lay.adj);
+  auto record = [&](long long e0, int nblk, int t0, int t1) {
+    hipLaunchKernelGGL(tds_rb_vjp_record_kernel, dim3((unsigned)((t1 - t0) * nblk)), dim3(64), lds, st, Mp, a, sel,
+                       (int)e0, nblk, t0, cap, over, lens, yidx, vi, ix, pd);
+    return hipGetLastError();
+  };
+  auto sweep = [&](long long e0, int nblk, int t0, int t1, long long) {
+    hipLaunchKernelGGL(tds_rb_vjp_sweep_kernel, dim3((unsigned)nblk), dim3(64), 0, st, a, (int)e0, nblk, t0, t1, cap,
+                       lens, yidx, ix, pd, adj, lam);
+    return hipGetLastError();
+  };
+  RB_VJP_TRY(tds_rollout_vjp_backward(st, n, steps, pl.chunk, pl.W, adj, lay.total - lay.adj, record, sweep));
   hipLaunchKernelGGL(tds_rb_vjp_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, over);
   RB_VJP_TRY(hipGetLastError());
-  int overflow = 0;  // the call reports an overflow: it waits for its launches
-  RB_VJP_TRY(hipMemcpyAsync(&overflow, a.overflow, sizeof(int), hipMemcpyDeviceToHost, st));
-  RB_VJP_TRY(hipStreamSynchronize(st));
+  int overflow = 0;
+  RB_VJP_TRY(tds_rollout_vjp_overflow(st, a.overflow, &overflow));
   if (overflow)
     return tds_rb_fail(TDS_ERR_UNSUPPORTED, "tds_rb_vjp: a world's tape exceeds the capacity (tape_cap) of one step");
   return TDS_OK;
@@ -475,10 +410,7 @@ int rb_vjp_host_run(const RbDev<double> &M, RbVjpArgs a, const RbSel &sel, int c
       }
       for (int bd = 0; bd < nb; ++bd)
         for (int c = 0; c < RB_NC; ++c) yi[bd * TDS_RB_STATE + rb_hbm(c)] = wr[0].get(bd, c).i;
-      std::fill(adj.begin(), adj.begin() + nin + len, 0.0);
-      rb_vjp_seed(b, 0, t, yi.data(), 1, lam.data(), 1, adj.data(), 1);
-      tds_rev_sweep_host(tp, len);
-      rb_vjp_scatter(b, 0, t, adj.data(), 1, lam.data(), 1);
+      tds_rollout_vjp_host_step(RbVjpProblem{b}, tp, len, 0, t, yi.data(), lam.data());
     }
     if (over_e) rb_vjp_nan(b, 0);
     over |= over_e;

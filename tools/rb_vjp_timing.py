@@ -5,9 +5,9 @@ shot gradient) and at k = 91 (the full state Jacobian).
 
     python tools/rb_vjp_timing.py [parent library]
 
-With the path of a libtds_hip.so built from the parent commit, the three existing calls are timed from that library
-as well, alternated call by call with this tree's: the columns show whether they have moved, and the parent's own
-spread over its five calls is the margin.  RB_N, RB_STEPS, RB_TAPE_CAP (default 32768: the fixed shot's longest step
+With the path of a libtds_hip.so built from the parent commit, every call is timed from that library as well,
+alternated call by call with this tree's: the columns show whether they have moved, and the parent's own spread over
+its five calls is the margin.  RB_N, RB_STEPS, RB_TAPE_CAP (default 32768: the fixed shot's longest step
 records 11 765 entries, the hardest of the random shots more) and RB_WORK_GIB (a comma-separated list of work-buffer bounds, default "8,32") change the run."""
 import ctypes as C
 import os
@@ -27,7 +27,7 @@ REPS = 5
 
 
 class Handle:
-    """a rigid-body handle of library L through the C ABI alone (the parent's library has no reverse mode)"""
+    """a rigid-body handle of library L through the C ABI alone"""
 
     def __init__(self, L, m, n, s0):
         self.L, self.n = L, n
@@ -37,6 +37,8 @@ class Handle:
         L.tds_rb_step.argtypes = [C.c_void_p, C.c_int]
         L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tds_rb_vjp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
         L.tds_rb_last_error.restype = C.c_char_p
         self.h = C.c_void_p()
         self.check(L.tds_rb_create(C.byref(m), n, 0, 0, C.byref(self.h)))
@@ -53,6 +55,12 @@ class Handle:
     def jvp(self, x, v, steps, sT, jv):
         self.check(self.L.tds_rb_jvp(self.h, self.n, steps, x.data_ptr(), 0, None, None, v.shape[1], v.data_ptr(),
                                      sT.data_ptr(), jv.data_ptr()))
+
+
+    def vjp(self, x, gs, steps, sT, gs0, cap, work_bytes):
+        """one cotangent on the final state, no parameters"""
+        self.check(self.L.tds_rb_vjp(self.h, self.n, steps, steps, x.data_ptr(), 0, None, None, gs.data_ptr(),
+                                     sT.data_ptr(), gs0.data_ptr(), None, cap, work_bytes))
 
 
 def one(fn):
@@ -108,16 +116,18 @@ def main():
         ts = timed([(lambda h=h: call(h)) for _, h in libs])
         for (name, _), t in zip(libs, ts):
             med[case, name] = show(f"{case}, {name}", t)
-    sim = hb.RigidBodySim(m, 1)
     gs = torch.zeros((n, 1, ns), dtype=torch.float64, device="cuda")
     gs[:, 0, BILLIARD_TARGET_BALL * 13:BILLIARD_TARGET_BALL * 13 + 3] = 1.0
+    gs0 = torch.empty_like(x)
     best = None
     for wb in budgets:
         plan = hb.rb_vjp_plan(m, n, steps, 0, cap, wb)
-        (t,) = timed([lambda: sim.vjp(x, gs, steps, tape_cap=cap, work_bytes=wb)])
-        v = show(f"tds_rb_vjp, {wb / (1 << 30):g} GiB: {plan[1]} worlds x {plan[2]} steps", t)
+        ts = timed([(lambda h=h: h.vjp(x, gs, steps, sT, gs0, cap, wb)) for _, h in libs])
+        for (name, _), t in zip(libs, ts):
+            v = show(f"tds_rb_vjp, {wb / (1 << 30):g} GiB: {plan[1]} worlds x {plan[2]} steps, {name}", t)
+            if name == "this tree":
+                best = v if best is None else min(best, v)
         print(f"    work buffer {plan[3] / 1e9:.2f} GB, tape capacity {plan[0]}")
-        best = v if best is None else min(best, v)
     k2, kf = med["tds_rb_jvp k = 2", "this tree"], med[f"tds_rb_jvp k = {ns}", "this tree"]
     per_col = (kf - k2) / (ns - 2)
     print(f"forward mode costs {per_col:.2f} ms per further column past k = 2; one tds_rb_vjp ({best:.2f} ms) costs as "
