@@ -584,8 +584,15 @@ int tds_hip_vjp_host_tape(const tds_model_t *model, int n, const double *x, int 
    scalars a selection params[p] names, in that order (system identification: examples/pendulum_sys_id.cpp).  The step
    reads theta_i in place of the blob's values for environment i; every other scalar comes from the blob.  Derivative,
    scope, refusals and error handling as for tds_hip_jacobian / tds_hip_vjp.  A selection with an unknown kind, a link
-   or comp out of range, a duplicate entry or a base kind on a fixed base gives TDS_ERR_INVALID_ARG.  dt, cfm, erp,
-   geometry and visuals are not selectable. */
+   or comp out of range, a duplicate entry or a base kind on a fixed base gives TDS_ERR_INVALID_ARG.
+   The contact model is selectable too (kinds 16..21; 12..15 are unknown kinds): the solver's cfm and erp, and per
+   collision shape — `link` is then the GEOM index — its radius, a capsule's length, a box's extents and the translation
+   of its frame X_trans.  A geom index or comp out of range, a length on anything but a capsule, an extent on anything
+   but a box, a radius on a shape that is none of sphere, capsule, box: TDS_ERR_INVALID_ARG.  A geom of a model without a plane is selectable, its derivative is exactly zero.
+   A box's contact points use rad = radius > 1e-2 ? radius : 1e-2, a branch of the primal: at or below 1e-2 the
+   derivative along the radius is exactly zero.
+   dt, the plane (normal, constant), the shapes' rotations, visuals and the rigid-body worlds (tds_rb_*: their radii
+   and erp) are not selectable. */
 enum {
   TDS_PARAM_LINK_MASS = 0,       /* links[link].mass */
   TDS_PARAM_LINK_COM = 1,        /* links[link].com[comp], comp 0..2 */
@@ -599,7 +606,14 @@ enum {
   TDS_PARAM_BASE_INERTIA = 8,    /* base_inertia, comp as for links (floating base only) */
   TDS_PARAM_GRAVITY = 9,         /* gravity[comp] (link 0) */
   TDS_PARAM_FRICTION = 10,       /* friction (link 0, comp 0) */
-  TDS_PARAM_RESTITUTION = 11     /* restitution (link 0, comp 0) */
+  TDS_PARAM_RESTITUTION = 11,    /* restitution (link 0, comp 0) */
+  /* 12..15: unknown kinds */
+  TDS_PARAM_CFM = 16,            /* cfm (link 0, comp 0) */
+  TDS_PARAM_ERP = 17,            /* erp (link 0, comp 0) */
+  TDS_PARAM_GEOM_RADIUS = 18,    /* geoms[link].radius (sphere, capsule, box; link = geom index, here and below) */
+  TDS_PARAM_GEOM_LENGTH = 19,    /* geoms[link].length (capsule only) */
+  TDS_PARAM_GEOM_EXTENT = 20,    /* geoms[link].extents[comp], comp 0..2 (box only) */
+  TDS_PARAM_GEOM_TRANS = 21      /* geoms[link].X_trans[comp], comp 0..2 */
 };
 typedef struct tds_param {
   int32_t kind, link, comp, pad_; /* TDS_PARAM_*; link 0 and comp 0 where the kind has none */
@@ -624,7 +638,8 @@ int tds_hip_params_apply(const tds_model_t *model, int p, const tds_param_t *par
    tds_hip_vjp*, tds_hip_trajectory_*, tds_hip_policy_trajectory_*, tds_hip_dynamics, tds_hip_contacts, ...) take theta
    explicitly or read the handle's own blob: they IGNORE installed variants.
    Every variant must have the base model's STRUCTURE: outside the fields a selection can change (X_T, mass, centre of
-   mass, inertia, joint springs, gravity, friction, restitution, and the frames of contact points and visuals) its
+   mass, inertia, joint springs, gravity, friction, restitution, cfm, erp, and the frames and radii of contact points —
+   which is where a shape's radius, length, extents and X_trans go — and the frames of visuals) its
    device model equals the base's — a mass on a massless root link, for instance, changes how the root chain is
    treated; such a variant is TDS_ERR_INVALID_ARG, the message names the variant and the field.  A map entry outside
    [0, n_variants), n_variants > num_envs, n_variants != num_envs with a NULL map, or a bad selection:

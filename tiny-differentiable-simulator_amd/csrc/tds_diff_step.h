@@ -197,8 +197,8 @@ TDS_HD inline void tds_d_quat_rotate(const T *q, const U *v, T *o) {
 
 // ---------------------------------------------------------------- transforms and spatial algebra
 // ref: math/transform.hpp:123-131: (A B).t = A.t + A.R B.t, (A B).R = A.R B.R
-template <typename T, typename U>
-TDS_HD inline void tds_d_xf_mul(const TdsDXf<T> &a, const U *br, const U *bt, TdsDXf<T> &o) {
+template <typename T, typename U, typename V>
+TDS_HD inline void tds_d_xf_mul(const TdsDXf<T> &a, const U *br, const V *bt, TdsDXf<T> &o) {
   T rt[3];
   for (int i = 0; i < 3; ++i) rt[i] = a.r[3 * i] * bt[0] + a.r[3 * i + 1] * bt[1] + a.r[3 * i + 2] * bt[2];
   for (int k = 0; k < 3; ++k) o.t[k] = a.t[k] + rt[k];
@@ -347,11 +347,15 @@ TDS_HD inline void tds_d_abi_inv_mul(const TdsDAbi<T> &A, const TdsDSv<T> &f, Td
 
 // ---------------------------------------------------------------- parameter views
 // Every read of a selectable model parameter (tds_param_t, include/tds_hip.h: masses, COMs, inertias, X_T
-// translations, springs, gravity, friction, restitution) goes through a view P, passed by value.  TdsBlobView reads
+// translations, springs, gravity, friction, restitution, and the contact model's cfm, erp and collision shapes: radius,
+// capsule length, box extents, X_trans) goes through a view P, passed by value.  TdsBlobView reads
 // the blob as double constants: the code of the plain instantiations, tds_diff_step(m, w, x, y).  TdsOverlayView reads
 // a TdsParamOverlay<T, B>: T-typed copies seeded from the blob (tds_param_seed), the selected entries replaced by
 // active theta (tds_param_set); the overlay lives in the lane's work object (tds_dparam.hip).
+// geom_scalar<T>: the type a view's shape reads have (the contact points' offsets are formed in it).
 struct TdsBlobView {  // no state: passed by value, it adds nothing to the plain instantiations' code
+  template <typename T>
+  using geom_scalar = double;
   TDS_HD const double *xt(const tds_model_t *m, int i) const { return m->links[i].X_T_trans; }
   template <typename T>
   TDS_HD void link_rbi(const tds_model_t *m, int i, TdsDAbi<T> &o) const {
@@ -370,6 +374,12 @@ struct TdsBlobView {  // no state: passed by value, it adds nothing to the plain
   TDS_HD T neg_gravity(const tds_model_t *m, int k) const { return T(-m->gravity[k]); }
   TDS_HD double friction(const tds_model_t *m) const { return m->friction; }
   TDS_HD double restitution(const tds_model_t *m) const { return m->restitution; }
+  TDS_HD double cfm(const tds_model_t *m) const { return m->cfm; }
+  TDS_HD double erp(const tds_model_t *m) const { return m->erp; }
+  TDS_HD double geom_radius(const tds_model_t *m, int g) const { return m->geoms[g].radius; }
+  TDS_HD double geom_length(const tds_model_t *m, int g) const { return m->geoms[g].length; }
+  TDS_HD const double *geom_extents(const tds_model_t *m, int g) const { return m->geoms[g].extents; }
+  TDS_HD const double *geom_trans(const tds_model_t *m, int g) const { return m->geoms[g].X_trans; }
 };
 
 // the rigid-body ABI of inertia.hpp:121-130 with T-typed mass, COM and inertia (tds_d_abi_rbi's expression order)
@@ -390,6 +400,13 @@ template <typename T, class B>
 struct TdsParamOverlay {
   T lxt[B::NL][3], lmass[B::NL], lcom[B::NL][3], linertia[B::NL][9], lstiff[B::NL], ldamp[B::NL];
   T bmass, bcom[3], binertia[9], grav[3], fric, rest;
+  // the contact model: solver softness, and the shapes of the geoms that give contact points.  A shape's slot is its
+  // rank among the model's spheres, capsules and boxes (gslot; -1: a geom without contact points, and every geom of a
+  // model without a plane — nothing reads those).  Each has at least one point, so at most NC slots are in use.
+  T cfm, erp, gradius[B::NC], glength[B::NC], gextent[B::NC][3], gtrans[B::NC][3];
+  signed char gslot[TDS_MAX_GEOMS];
+  T gspare;    // where the theta of a shape that nothing reads goes (tds_param_slot)
+  T gnone[3];  // zeros: what the frame of a geom without contact points reads as its translation
 };
 
 // the view of an overlay (a pointer to it, passed by value); the model argument is not read
@@ -409,7 +426,22 @@ struct TdsOverlayView {
   TDS_HD U neg_gravity(const tds_model_t *, int k) const { return -o->grav[k]; }
   TDS_HD const T &friction(const tds_model_t *) const { return o->fric; }
   TDS_HD const T &restitution(const tds_model_t *) const { return o->rest; }
+  template <typename U>
+  using geom_scalar = T;
+  TDS_HD const T &cfm(const tds_model_t *) const { return o->cfm; }
+  TDS_HD const T &erp(const tds_model_t *) const { return o->erp; }
+  // (radius, length and extents are read for geoms with contact points only: their slots are >= 0.  The frame of a
+  //  geom without contact points is formed and dropped, as it always was: its translation reads as 0)
+  TDS_HD const T &geom_radius(const tds_model_t *, int g) const { return o->gradius[o->gslot[g]]; }
+  TDS_HD const T &geom_length(const tds_model_t *, int g) const { return o->glength[o->gslot[g]]; }
+  TDS_HD const T *geom_extents(const tds_model_t *, int g) const { return o->gextent[o->gslot[g]]; }
+  TDS_HD const T *geom_trans(const tds_model_t *, int g) const { return o->gslot[g] < 0 ? o->gnone : o->gtrans[o->gslot[g]]; }
 };
+
+// whether a geom gives plane contact points (world.hpp:206-282 pairs it with the plane; meshes are ignored)
+TDS_HD inline bool tds_geom_has_points(const tds_geom_t &G) {
+  return G.type == TDS_GEOM_SPHERE || G.type == TDS_GEOM_CAPSULE || G.type == TDS_GEOM_BOX;
+}
 
 // the overlay holds the blob's values, all constant
 template <typename T, class B>
@@ -424,6 +456,17 @@ TDS_HD inline void tds_param_seed(const tds_model_t *m, TdsParamOverlay<T, B> &o
   for (int k = 0; k < 3; ++k) o.bcom[k] = T(m->base_com[k]), o.grav[k] = T(m->gravity[k]);
   for (int k = 0; k < 9; ++k) o.binertia[k] = T(m->base_inertia[k]);
   o.fric = T(m->friction), o.rest = T(m->restitution);
+  o.cfm = T(m->cfm), o.erp = T(m->erp), o.gspare = T(0.0);
+  for (int k = 0; k < 3; ++k) o.gnone[k] = T(0.0);
+  int ns = 0;
+  for (int g = 0; g < m->num_geoms; ++g) {
+    const tds_geom_t &G = m->geoms[g];
+    o.gslot[g] = -1;
+    if (!m->has_plane || !tds_geom_has_points(G) || ns >= B::NC) continue;  // (tds_diff_check: the points fit NC)
+    o.gradius[ns] = T(G.radius), o.glength[ns] = T(G.length);
+    for (int k = 0; k < 3; ++k) o.gextent[ns][k] = T(G.extents[k]), o.gtrans[ns][k] = T(G.X_trans[k]);
+    o.gslot[g] = (signed char)ns++;
+  }
 }
 
 // inertia entry `comp` (0..5 = xx, yy, zz, xy, xz, yz) of a row-major 3x3: its index and its mirror's
@@ -433,9 +476,13 @@ TDS_HD inline int tds_param_inertia_index(int comp, int mirror) {
   return mirror ? 3 * c + r : 3 * r + c;
 }
 
-// the overlay's entry (entries: an inertia entry and its mirror) of a selection; NULL for a kind it does not know
+// the overlay's entry (entries: an inertia entry and its mirror) of a selection; NULL for a kind it does not know.
+// A shape the step does not read (no plane, or no contact points) has no slot of its own: its theta lands in
+// o.gspare, which nothing reads, and its derivative is exactly zero.
 template <typename T, class B>
 TDS_HD inline T *tds_param_slot(TdsParamOverlay<T, B> &o, const tds_param_t &q, int mirror) {
+  const int gs = q.kind >= TDS_PARAM_GEOM_RADIUS && q.kind <= TDS_PARAM_GEOM_TRANS ? o.gslot[q.link] : 0;
+  if (gs < 0) return &o.gspare;
   switch (q.kind) {
     case TDS_PARAM_LINK_MASS: return &o.lmass[q.link];
     case TDS_PARAM_LINK_COM: return &o.lcom[q.link][q.comp];
@@ -449,6 +496,12 @@ TDS_HD inline T *tds_param_slot(TdsParamOverlay<T, B> &o, const tds_param_t &q, 
     case TDS_PARAM_GRAVITY: return &o.grav[q.comp];
     case TDS_PARAM_FRICTION: return &o.fric;
     case TDS_PARAM_RESTITUTION: return &o.rest;
+    case TDS_PARAM_CFM: return &o.cfm;
+    case TDS_PARAM_ERP: return &o.erp;
+    case TDS_PARAM_GEOM_RADIUS: return &o.gradius[gs];
+    case TDS_PARAM_GEOM_LENGTH: return &o.glength[gs];
+    case TDS_PARAM_GEOM_EXTENT: return &o.gextent[gs][q.comp];
+    case TDS_PARAM_GEOM_TRANS: return &o.gtrans[gs][q.comp];
     default: return nullptr;
   }
 }
@@ -475,6 +528,12 @@ inline double tds_param_value(const tds_model_t *m, const tds_param_t &q) {
     case TDS_PARAM_BASE_INERTIA: return m->base_inertia[tds_param_inertia_index(q.comp, 0)];
     case TDS_PARAM_GRAVITY: return m->gravity[q.comp];
     case TDS_PARAM_FRICTION: return m->friction;
+    case TDS_PARAM_CFM: return m->cfm;
+    case TDS_PARAM_ERP: return m->erp;
+    case TDS_PARAM_GEOM_RADIUS: return m->geoms[q.link].radius;
+    case TDS_PARAM_GEOM_LENGTH: return m->geoms[q.link].length;
+    case TDS_PARAM_GEOM_EXTENT: return m->geoms[q.link].extents[q.comp];
+    case TDS_PARAM_GEOM_TRANS: return m->geoms[q.link].X_trans[q.comp];
     default: return m->restitution;
   }
 }
@@ -484,16 +543,27 @@ inline int tds_param_check(const tds_model_t *m, int p, const tds_param_t *param
   if (p < 0 || (p > 0 && !params)) return *why = "parameter derivatives: NULL or negative parameter selection", 1;
   for (int j = 0; j < p; ++j) {
     const tds_param_t &q = params[j];
-    if (q.kind < TDS_PARAM_LINK_MASS || q.kind > TDS_PARAM_RESTITUTION)
+    if (q.kind < TDS_PARAM_LINK_MASS || q.kind > TDS_PARAM_GEOM_TRANS ||
+        (q.kind > TDS_PARAM_RESTITUTION && q.kind < TDS_PARAM_CFM))
       return *why = "parameter derivatives: unknown parameter kind", 1;
-    const bool on_link = q.kind <= TDS_PARAM_LINK_DAMPING;
+    const bool on_link = q.kind <= TDS_PARAM_LINK_DAMPING, on_geom = q.kind >= TDS_PARAM_GEOM_RADIUS;
     const int ncomp = q.kind == TDS_PARAM_LINK_INERTIA || q.kind == TDS_PARAM_BASE_INERTIA ? 6
                       : q.kind == TDS_PARAM_LINK_COM || q.kind == TDS_PARAM_LINK_XT_TRANS || q.kind == TDS_PARAM_BASE_COM ||
-                                q.kind == TDS_PARAM_GRAVITY
+                                q.kind == TDS_PARAM_GRAVITY || q.kind == TDS_PARAM_GEOM_EXTENT || q.kind == TDS_PARAM_GEOM_TRANS
                           ? 3
                           : 1;
-    if (on_link ? (q.link < 0 || q.link >= m->num_links) : q.link != 0)
+    if (on_geom) {
+      if (q.link < 0 || q.link >= m->num_geoms || q.link >= TDS_MAX_GEOMS)
+        return *why = "parameter derivatives: geom index out of range", 1;
+      if (q.kind == TDS_PARAM_GEOM_LENGTH && m->geoms[q.link].type != TDS_GEOM_CAPSULE)
+        return *why = "parameter derivatives: a length needs a capsule", 1;
+      if (q.kind == TDS_PARAM_GEOM_EXTENT && m->geoms[q.link].type != TDS_GEOM_BOX)
+        return *why = "parameter derivatives: an extent needs a box", 1;
+      if (q.kind == TDS_PARAM_GEOM_RADIUS && !tds_geom_has_points(m->geoms[q.link]))
+        return *why = "parameter derivatives: a radius needs a sphere, a capsule or a box", 1;
+    } else if (on_link ? (q.link < 0 || q.link >= m->num_links) : q.link != 0) {
       return *why = "parameter derivatives: link index out of range", 1;
+    }
     if (q.comp < 0 || q.comp >= ncomp) return *why = "parameter derivatives: component index out of range", 1;
     if (q.kind >= TDS_PARAM_BASE_MASS && q.kind <= TDS_PARAM_BASE_INERTIA && !m->is_floating)
       return *why = "parameter derivatives: base parameters need a floating base", 1;
@@ -734,28 +804,33 @@ TDS_HD inline void tds_d_point_jacobian(const tds_model_t *m, TdsDiffWork<T, B> 
 }
 
 // ref: world.hpp:206-282 (plane = multi body a, the robot b) and contact_point.hpp:96-198 (plane-sphere / capsule / box)
-template <typename T, class B>
-TDS_HD inline void tds_d_contacts(const tds_model_t *m, TdsDiffWork<T, B> &w) {
+// The shapes are read through the view.  A box's rad = radius > 1e-2 ? radius : 1e-2 is a branch of the primal: at or
+// below 1e-2 the constant is taken and the derivative along the radius is exactly zero.
+template <typename T, class B, class P>
+TDS_HD inline void tds_d_contacts(const tds_model_t *m, P p, TdsDiffWork<T, B> &w) {
+  typedef typename P::template geom_scalar<T> S;
   w.n_c = 0;
   const double *n = m->plane_normal;
   for (int g = 0; g < m->num_geoms; ++g) {
     const tds_geom_t &G = m->geoms[g];
     TdsDXf<T> tr;
-    tds_d_xf_mul(G.link >= 0 ? w.Xw[G.link] : w.base, G.X_rot, G.X_trans, tr);  // world.hpp:242
+    tds_d_xf_mul(G.link >= 0 ? w.Xw[G.link] : w.base, G.X_rot, p.geom_trans(m, g), tr);  // world.hpp:242
     T orn[4];
     tds_d_matrix_to_quat(tr.r, orn);  // world.hpp:244-245
     tds_d_quat_normalize(orn);
     int np = 0;
-    double off[8][3], rad = G.radius;
+    S off[8][3], rad = tds_geom_has_points(G) ? p.geom_radius(m, g) : S(0.0);
     if (G.type == TDS_GEOM_SPHERE) {
-      np = 1, off[0][0] = off[0][1] = off[0][2] = 0.0;
+      np = 1, off[0][0] = off[0][1] = off[0][2] = S(0.0);
     } else if (G.type == TDS_GEOM_CAPSULE) {  // :127-161
       np = 2;
-      for (int e = 0; e < 2; ++e) off[e][0] = off[e][1] = 0.0, off[e][2] = (e == 0 ? 0.5 : -0.5) * G.length;
+      for (int e = 0; e < 2; ++e)
+        off[e][0] = off[e][1] = S(0.0), off[e][2] = (e == 0 ? 0.5 : -0.5) * p.geom_length(m, g);
     } else if (G.type == TDS_GEOM_BOX) {  // :163-198, geometry.hpp:244-259
       np = 8;
-      rad = G.radius > 1e-2 ? G.radius : 1e-2;
-      const double dx = G.extents[0] * 0.5 - rad, dy = G.extents[1] * 0.5 - rad, dz = G.extents[2] * 0.5 - rad;
+      if (!(rad > 1e-2)) rad = S(1e-2);  // rad = radius > 1e-2 ? radius : 1e-2
+      const S dx = p.geom_extents(m, g)[0] * 0.5 - rad, dy = p.geom_extents(m, g)[1] * 0.5 - rad,
+              dz = p.geom_extents(m, g)[2] * 0.5 - rad;
       for (int c = 0; c < 8; ++c) off[c][0] = (c & 4) ? -dx : dx, off[c][1] = (c & 2) ? -dy : dy, off[c][2] = (c & 1) ? -dz : dz;
     }
     for (int e = 0; e < np; ++e) {
@@ -770,8 +845,8 @@ TDS_HD inline void tds_d_contacts(const tds_model_t *m, TdsDiffWork<T, B> &w) {
       // :96-125  t = -(pos . (-n) + constant); point_b = pos - r n; distance = t - r
       const int c = w.n_c++;
       T t = -((pos[0] * -n[0] + pos[1] * -n[1] + pos[2] * -n[2]) + m->plane_constant);
-      for (int k = 0; k < 3; ++k) w.cp_b[c][k] = pos[k] - rad * n[k];
-      w.cp_dist[c] = t - rad;
+      for (int k = 0; k < 3; ++k) w.cp_b[c][k] = tds_sub_c(pos[k], rad * n[k]);
+      w.cp_dist[c] = tds_sub_c(t, rad);
       w.cp_link[c] = G.link;
     }
   }
@@ -809,7 +884,7 @@ TDS_HD inline int tds_d_resolve(const tds_model_t *m, P p, TdsDiffWork<T, B> &w)
     }
     // rel_vel = -vel (:315); b rows (:321-325, :365-370), J rows (:300-307, :378-384); inactive contacts: zero rows
     const T nrv = -(nrm[0] * vel[0] + nrm[1] * vel[1] + nrm[2] * vel[2]);
-    w.b[i] = hit ? (-(1.0 + p.restitution(m)) * nrv - m->erp * w.cp_dist[i] / m->dt) : T(0.0);
+    w.b[i] = hit ? (-(1.0 + p.restitution(m)) * nrv - p.erp(m) * w.cp_dist[i] / m->dt) : T(0.0);
     w.b[nc + i] = hit ? (f1[0] * vel[0] + f1[1] * vel[1] + f1[2] * vel[2]) : T(0.0);
     w.b[2 * nc + i] = hit ? (f2[0] * vel[0] + f2[1] * vel[1] + f2[2] * vel[2]) : T(0.0);
     for (int d = 0; d < nd; ++d) {
@@ -841,7 +916,7 @@ TDS_HD inline int tds_d_resolve(const tds_model_t *m, P p, TdsDiffWork<T, B> &w)
       T Ju = T(0.0), Arr = T(0.0);
       for (int d = 0; d < nd; ++d) Ju = Ju + w.J[r][d] * u[d], Arr = Arr + w.J[r][d] * w.W[r][d];
       const T delta = Ju - Arr * w.p[r];
-      T x = (w.b[r] - delta) / (Arr + m->cfm);
+      T x = (w.b[r] - delta) / tds_add_c(Arr, p.cfm(m));
       if (r < nc) {  // normal: [0, 1e5]
         x = tds_clamp(x, T(0.0), T(100000.0));
       } else {  // friction: +-mu max(p_normal, 0)
@@ -917,7 +992,7 @@ TDS_HD inline int tds_diff_step_view(const tds_model_t *m, P p, TdsDiffWork<T, B
     }
   }
   if (m->has_plane) {  // world.step (world.hpp:293-366)
-    tds_d_contacts(m, w);
+    tds_d_contacts(m, p, w);
     if (tds_d_resolve(m, p, w)) return -1;
   }
   if (m->is_floating) {  // integrate_euler (integrator.hpp:23-89): quaternion += quat_velocity(q, omega, dt), normalised

@@ -157,6 +157,17 @@ TDS_HD inline TdsDual<K> tds_cos(const TdsDual<K> &a) {
   return r;
 }
 
+// a + b, a - b where b is a parameter read through a view (tds_diff_step.h): a double with the blob's view, a T with an
+// overlay's.  Plain sums here; TdsRev (tds_rev.h) overloads them so that a constant T records what a double would.
+template <typename A, typename Bt>
+TDS_HD inline A tds_add_c(const A &a, const Bt &b) {
+  return a + b;
+}
+template <typename A, typename Bt>
+TDS_HD inline A tds_sub_c(const A &a, const Bt &b) {
+  return a - b;
+}
+
 // clamps on the value (Algebra::min / max of the reference pick one operand whole, tangents included)
 template <typename T>
 TDS_HD inline T tds_clamp(const T &x, const T &lo, const T &hi) {

@@ -728,8 +728,8 @@ __device__ __forceinline__ void tds_reset_state(T *xr, const DevModel<T> *mdl, c
 // VAR: per-environment model VARIANTS (tds_hip_set_model_variants): mdl_arg points to an ARRAY of models of one structure
 // and ctl.variant [n_envs] names each environment's entry.  The lane group of an environment reads the model's VALUES —
 // what a parameter selection can change: X_T, mass, centre of mass, inertia, joint springs, gravity, friction,
-// restitution, and the contact points' and visuals' frames (re-based where fixed links are folded) — through its own
-// entry; the STRUCTURE — dimensions, indices, flags, and every constant no selection reaches — still comes from entry 0
+// restitution, cfm, erp / dt, and the contact points' radii and frames and the visuals' frames (re-based where fixed
+// links are folded) — through its own entry; the STRUCTURE — dimensions, indices, flags, and every constant no selection reaches — still comes from entry 0
 // through scalar loads, so that every branch on it stays wave-uniform (the host checks that the entries agree in all of
 // it).  One wavefront per workgroup, straight-line and step loop; the workgroup's constant table (TdsLds::cw) is the
 // first lane group's and is not used.
@@ -1124,7 +1124,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
     pf_cp_anc = md->anc_dofs[pf_cp_link >= 0 ? pf_cp_link : 0];
 #pragma unroll
     for (int c = 0; c < 3; ++c) pf_cp_loc[c] = mdv->cp_local[c][kc];
-    pf_cp_rad = md->cp_radius[kc];
+    pf_cp_rad = mdv->cp_radius[kc];
     const int kv = lane < pf_nv ? lane : 0;
     pf_vis_link = md->vis_link[kv];
 #pragma unroll
@@ -1139,8 +1139,8 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
       pf_plane_n[c] = md->plane_n[c];
     }
     pf_plane_c = md->plane_c;
-    pf_cfm = md->cfm;
-    pf_erp_dt = md->erp_over_dt;
+    pf_cfm = mdv->cfm;
+    pf_erp_dt = mdv->erp_over_dt;
     pf_rest = mdv->restitution;
     pf_mu = mdv->friction;
     pf_iters = md->pgs_iterations;
@@ -1455,7 +1455,7 @@ void tds_step_kernel(const DevModel<T> *__restrict__ mdl_arg, TdsLds L_arg,
             loc[0] = mdv->cp_local[0][k];
             loc[1] = mdv->cp_local[1][k];
             loc[2] = mdv->cp_local[2][k];
-            rad = mdl->cp_radius[k];
+            rad = mdv->cp_radius[k];
           }
           T ctr[3];
           mat3_mulv(Rl, loc, ctr);

@@ -144,6 +144,10 @@ struct TdsRev {
 };
 
 TDS_HD inline double tds_value(const TdsRev &x) { return x.v; }
+// tds_add_c / tds_sub_c (tds_dual.h): a constant b keeps a's index and records nothing, as a double b does — a
+// parameter that is not selected costs the tape no entry
+TDS_HD inline TdsRev tds_add_c(const TdsRev &a, const TdsRev &b) { return b.i < 0 ? TdsRev(a.v + b.v, a.i) : a + b; }
+TDS_HD inline TdsRev tds_sub_c(const TdsRev &a, const TdsRev &b) { return b.i < 0 ? TdsRev(a.v - b.v, a.i) : a - b; }
 TDS_HD inline TdsRev tds_sqrt(const TdsRev &a) {
   const double r = sqrt(a.v);
   return TdsRev::un(r, a, 0.5 / r);

@@ -39,7 +39,14 @@ inline void tds_param_apply_one(tds_model_t *m, const tds_param_t &q, double t) 
       break;
     case TDS_PARAM_GRAVITY: m->gravity[q.comp] = t; break;
     case TDS_PARAM_FRICTION: m->friction = t; break;
-    default: m->restitution = t; break;
+    case TDS_PARAM_RESTITUTION: m->restitution = t; break;
+    case TDS_PARAM_CFM: m->cfm = t; break;
+    case TDS_PARAM_ERP: m->erp = t; break;
+    case TDS_PARAM_GEOM_RADIUS: m->geoms[q.link].radius = t; break;
+    case TDS_PARAM_GEOM_LENGTH: m->geoms[q.link].length = t; break;
+    case TDS_PARAM_GEOM_EXTENT: m->geoms[q.link].extents[q.comp] = t; break;
+    case TDS_PARAM_GEOM_TRANS: m->geoms[q.link].X_trans[q.comp] = t; break;
+    default: break;  // (a checked selection has no other kind)
   }
 }
 
@@ -57,13 +64,15 @@ struct TdsFieldSpan {
 
 // what a variant build reads through the environment's own entry — every field a parameter selection can reach: the
 // selectable scalars themselves, and the contact points' / visuals' frames, which folding a fixed link re-bases through
-// its X_T.  (oct_tab and gravb are derived from them too; the general kernel's variant builds read neither.)
+// its X_T.  The contact model's parameters arrive as cfm, erp_over_dt (= erp / dt), cp_radius (a shape's radius; a
+// box's clamped one) and cp_local (a shape's X_trans, a capsule's length, a box's extents and radius).
+// (oct_tab and gravb are derived from them too; the general kernel's variant builds read neither.)
 template <typename T>
 inline const std::vector<TdsFieldSpan> &tds_variant_value_fields() {
   static const std::vector<TdsFieldSpan> v = {TDS_SPAN(friction),  TDS_SPAN(restitution), TDS_SPAN(grav),     TDS_SPAN(X_T),
                                               TDS_SPAN(mass),      TDS_SPAN(com),         TDS_SPAN(inertia),  TDS_SPAN(stiffness),
                                               TDS_SPAN(damping),   TDS_SPAN(cp_local),    TDS_SPAN(vis_X),    TDS_SPAN(oct_tab),
-                                              TDS_SPAN(gravb)};
+                                              TDS_SPAN(gravb),     TDS_SPAN(cfm),         TDS_SPAN(erp_over_dt), TDS_SPAN(cp_radius)};
   return v;
 }
 // the integer fields, by name (what the message of a refused variant names)

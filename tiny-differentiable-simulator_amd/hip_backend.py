@@ -307,12 +307,21 @@ PARAM_KINDS = {
     "stiffness": (4, True, 1), "damping": (5, True, 1), "base_mass": (6, False, 1), "base_com": (7, False, 3),
     "base_inertia": (8, False, 6), "gravity": (9, False, 3), "friction": (10, False, 1), "restitution": (11, False, 1),
 }
+# the contact model's kinds, in a table of their own (all_params lists PARAM_KINDS only): name -> (code, on a GEOM,
+# number of components).  The index of the geom kinds is the geom's, not a link's.
+CONTACT_PARAM_KINDS = {
+    "cfm": (16, False, 1), "erp": (17, False, 1), "geom_radius": (18, True, 1), "geom_length": (19, True, 1),
+    "geom_extent": (20, True, 3), "geom_trans": (21, True, 3),
+}
+GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX = 0, 2, 4  # TDS_GEOM_*: the shapes that give contact points
 
 
 def param_spec(params):
     """a parameter selection as a tds_param_t array: entries are tds_param_t, or tuples (kind name, link[, comp]) for
     the link kinds and (kind name[, comp]) for the others, e.g. ("mass", 3), ("com", 3, 2), ("gravity", 2),
-    ("friction",).  Inertia comps 0..5 = xx, yy, zz, xy, xz, yz.  The library checks ranges and duplicates."""
+    ("friction",).  Inertia comps 0..5 = xx, yy, zz, xy, xz, yz.  The contact model's kinds (CONTACT_PARAM_KINDS):
+    ("cfm",), ("erp",), and with a GEOM index ("geom_radius", g), ("geom_length", g), ("geom_extent", g, comp),
+    ("geom_trans", g, comp).  The library checks ranges, shapes and duplicates."""
     if isinstance(params, C.Array) and params._type_ is Param:
         return params
     out = (Param * max(len(params), 1))()
@@ -321,11 +330,11 @@ def param_spec(params):
             out[j] = q
             continue
         name, rest = q[0], list(q[1:])
-        if name not in PARAM_KINDS:
-            raise ValueError(f"unknown parameter kind {name!r} (one of {', '.join(PARAM_KINDS)})")
-        code, on_link, nc = PARAM_KINDS[name]
+        if name not in PARAM_KINDS and name not in CONTACT_PARAM_KINDS:
+            raise ValueError(f"unknown parameter kind {name!r} (one of {', '.join([*PARAM_KINDS, *CONTACT_PARAM_KINDS])})")
+        code, on_link, nc = PARAM_KINDS[name] if name in PARAM_KINDS else CONTACT_PARAM_KINDS[name]
         if on_link and not rest:
-            raise ValueError(f"parameter {q!r}: kind {name!r} needs a link index")
+            raise ValueError(f"parameter {q!r}: kind {name!r} needs a {'link' if name in PARAM_KINDS else 'geom'} index")
         link = rest.pop(0) if on_link else 0
         comp = rest.pop(0) if rest else 0
         if rest:
@@ -344,6 +353,23 @@ def all_params(m: _model.Model):
         for link in (range(m.num_links) if on_link else [None]):
             for c in range(nc):
                 sel.append((name,) + ((link,) if on_link else ()) + ((c,) if nc > 1 else ()))
+    return sel
+
+
+def contact_params(m: _model.Model):
+    """every selectable parameter of a model's contact model: cfm, erp, and per collision shape (sphere, capsule, box)
+    its radius, a capsule's length, a box's extents, and the translation of its frame"""
+    sel = [("cfm",), ("erp",)]
+    for g in range(m.num_geoms):
+        t = m.geoms[g].type
+        if t not in (GEOM_SPHERE, GEOM_CAPSULE, GEOM_BOX):
+            continue
+        sel.append(("geom_radius", g))
+        if t == GEOM_CAPSULE:
+            sel.append(("geom_length", g))
+        if t == GEOM_BOX:
+            sel += [("geom_extent", g, c) for c in range(3)]
+        sel += [("geom_trans", g, c) for c in range(3)]
     return sel
 
 

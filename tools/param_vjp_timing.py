@@ -1,5 +1,6 @@
 """Times, in one process, the parameter derivatives of Ant x 4096 against the plain ones: vjp (k = 1, the baseline),
-vjp_params with the 14 link masses and with every selectable parameter, jvp_params over [x | the 14 masses] (one
+vjp_params with the 14 link masses, with every parameter of all_params and with those plus every contact parameter
+(contact_params: cfm, erp, the shapes), jvp_params over [x | the 14 masses] (one
 unit direction per input: the dense Jacobian in [x | theta]), and the dense Jacobian.  Prints one line per case: the
 wall time per call (torch.cuda events around `--reps` calls, after one warm-up call that also sizes the handle's work
 buffer), then the tape lengths the host template records for a sample of the records (parameter mode, every
@@ -40,6 +41,8 @@ def main():
     every = hb.all_params(m)
     th_m = torch.from_numpy(hb.params_get(m, masses)).cuda()
     th_a = torch.from_numpy(hb.params_get(m, every)).cuda()
+    every_c = every + hb.contact_params(m)
+    th_c = torch.from_numpy(hb.params_get(m, every_c)).cuda()
     w = torch.from_numpy(rng.normal(size=(args.n, 1, m.output_dim))).cuda()
     nall = m.input_dim + len(masses)
     eye = torch.eye(nall, dtype=torch.float64, device="cuda").expand(args.n, nall, nall).contiguous()
@@ -48,6 +51,7 @@ def main():
         "vjp_k1": lambda: sim.vjp(x, w),
         "vjp_params_masses": lambda: sim.vjp_params(x, th_m, masses, w),
         "vjp_params_every": lambda: sim.vjp_params(x, th_a, every, w),
+        "vjp_params_every_and_contact": lambda: sim.vjp_params(x, th_c, every_c, w),
         "jvp_params_masses_dense": lambda: sim.jvp_params(x, th_m, masses, eye),
         "jacobian": lambda: sim.jacobian(x),
         # y at theta: k = 0 runs the double step over a double overlay; one direction runs the dual kernel
@@ -77,9 +81,11 @@ def main():
     zeros = np.zeros((sample.shape[0], m.output_dim))
     _, lens_p = hb.vjp_params_host(m, sample, hb.params_get(m, every), every, zeros, tape_len=True)
     _, lens_m = hb.vjp_params_host(m, sample, hb.params_get(m, masses), masses, zeros, tape_len=True)
+    _, lens_c = hb.vjp_params_host(m, sample, hb.params_get(m, every_c), every_c, zeros, tape_len=True)
     _, lens = hb.vjp_host(m, sample, zeros, tape_len=True)
     print(json.dumps({"tape_len_max": {"plain": int(lens.max()), "masses": int(lens_m.max()),
-                                       "every": int(lens_p.max())}, "p_every": len(every)}))
+                                       "every": int(lens_p.max()), "every_and_contact": int(lens_c.max())},
+                      "p_every": len(every), "p_every_and_contact": len(every_c)}))
 
 
 def device_used():

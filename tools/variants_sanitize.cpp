@@ -101,6 +101,42 @@ int main(int argc, char **argv) {
            TDS_ERR_INVALID_ARG);
     EXPECT(strstr(tds_internal::g_err, "variant 1") != nullptr && strstr(tds_internal::g_err, "root_last") != nullptr);
   }
+  // ---- the contact model's kinds: one applied variant each (the Ant: geom 0 the torso's sphere, 1.. the legs' capsules;
+  //      the extent on a copy whose torso is a box and which keeps one leg's capsule beside it)
+  {
+    EXPECT(m[0].num_geoms > 1 && m[0].geoms[0].type == TDS_GEOM_SPHERE && m[0].geoms[1].type == TDS_GEOM_CAPSULE);
+    const tds_param_t csel[] = {{TDS_PARAM_CFM, 0, 0, 0},         {TDS_PARAM_ERP, 0, 0, 0},
+                                {TDS_PARAM_GEOM_RADIUS, 0, 0, 0}, {TDS_PARAM_GEOM_LENGTH, 1, 0, 0},
+                                {TDS_PARAM_GEOM_TRANS, 1, 2, 0},  {TDS_PARAM_GEOM_EXTENT, 0, 1, 0}};
+    const double cth[] = {1e-3, 0.3, 0.3, 0.5, 0.05, 0.4};
+    for (int e = 0; e < n; ++e) map[(size_t)e] = e % 2;
+    for (int j = 0; j < 6; ++j) {
+      memcpy(&m[2], &m[0], sizeof(tds_model_t));
+      if (csel[j].kind == TDS_PARAM_GEOM_EXTENT) {
+        EXPECT(tds_hip_params_apply(&m[2], 1, &csel[j], &cth[j], &m[1]) == TDS_ERR_INVALID_ARG);  // an extent of a sphere
+        m[2].geoms[0].type = TDS_GEOM_BOX;
+        m[2].num_geoms = 2;  // (the box's 8 points and one leg's 2: within the 17 of the Ant's class)
+        for (int k = 0; k < 3; ++k) m[2].geoms[0].extents[k] = 0.5;
+      }
+      const double theta[2] = {tds_param_value(&m[2], csel[j]), cth[j]};
+      EXPECT(tds_hip_params_apply(&m[2], 1, &csel[j], &cth[j], &m[1]) == TDS_OK);
+      EXPECT(tds_param_value(&m[1], csel[j]) == cth[j]);
+      EXPECT(tds_hip_params_apply(&m[1], 1, &csel[j], &theta[0], &m[1]) == TDS_OK);
+      EXPECT(memcmp(&m[2], &m[1], sizeof(tds_model_t)) == 0);
+      EXPECT(tds_hip_model_variants_host(&m[2], TDS_DTYPE_F64, n, 2, 1, &csel[j], theta, map.data(), nullptr) == TDS_OK);
+      EXPECT(tds_hip_model_variants_host(&m[2], TDS_DTYPE_F32, n, 2, 1, &csel[j], theta, map.data(), nullptr) == TDS_OK);
+    }
+    const tds_param_t bad_geom = {TDS_PARAM_GEOM_RADIUS, m[0].num_geoms, 0, 0}, bad_len = {TDS_PARAM_GEOM_LENGTH, 0, 0, 0},
+                      bad_comp = {TDS_PARAM_GEOM_TRANS, 1, 3, 0}, dup[2] = {csel[0], csel[0]};
+    EXPECT(tds_hip_params_apply(&m[0], 1, &bad_geom, cth, &m[1]) == TDS_ERR_INVALID_ARG);
+    EXPECT(tds_hip_params_apply(&m[0], 1, &bad_len, cth, &m[1]) == TDS_ERR_INVALID_ARG);
+    EXPECT(tds_hip_params_apply(&m[0], 1, &bad_comp, cth, &m[1]) == TDS_ERR_INVALID_ARG);
+    EXPECT(tds_hip_params_apply(&m[0], 2, dup, cth, &m[1]) == TDS_ERR_INVALID_ARG);
+    for (int kind = 12; kind < 16; ++kind) {
+      const tds_param_t unknown = {kind, 0, 0, 0};
+      EXPECT(tds_hip_params_apply(&m[0], 1, &unknown, cth, &m[1]) == TDS_ERR_INVALID_ARG);
+    }
+  }
   printf("variants_sanitize: ok (device model: %zu B double, %zu B float)\n", sizeof(DevModel<double>), sizeof(DevModel<float>));
   return 0;
 }
