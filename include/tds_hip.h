@@ -875,6 +875,33 @@ int tds_hip_contacts_host(const tds_model_t *model, int n, const double *x, cons
    tds_hip_last_error). */
 int tds_hip_contact_layout(const tds_model_t *model, int32_t *link, int32_t *geom, double *dirs);
 
+/* Forward-mode derivatives of the contact query in [x | theta]: for directions v [n][k][input_dim + p] the tangents
+   of every output `dout` names, [n][k][...the output's shape...], and (optionally) the primal outputs `out` names, at
+   theta_dev [n][p] (the selection params_host [p] of tds_hip_jvp_params, the contact kinds included; theta_dev NULL:
+   the model's values).  k = 0 gives the primal at per-environment theta only (dout, v_dev may then be NULL).
+   Convention: the derivative of the algorithm as executed (tds_hip_jvp's): the primal takes every branch — contact
+   activation distance < 0, the [0, 1e5] clamp of the normal rows, the friction box, the action and max_force clamps —
+   by value, and the tangent is that of the taken branch; a separated point has exactly zero tangents in rows, rhs,
+   impulse and force; quaternion entries of x are differentiated raw.  An environment whose M is not positive definite
+   has NaN in rows .. qd_post and in their tangents.  delassus and its tangent are computed only where one of them is
+   asked for.  Scope, refusals and messages: those of tds_hip_jvp_params; selection errors: tds_hip_params_get's.
+   Enqueued on the handle's stream as one launch.  The host waits only where the work buffer (shared with every other
+   derivative and query call: calls on the stream use it in turn) grows, or, with p > 0, where the selection is copied
+   into it (a blocking copy after a wait for the stream, as in tds_hip_jvp_params).  Work items are (environment,
+   block of K directions), K = tds_hip_contacts_jvp_tangents(model); at most 16384 lanes per launch, more items are
+   walked with the grid's stride.  The primal is written by the items of the first block. */
+int tds_hip_contacts_jvp(tds_hip_sim_t *sim, int n, const void *x_dev, int p, const tds_param_t *params_host,
+                         const void *theta_dev, int k, const void *v_dev, const tds_contact_out_t *out,
+                         const tds_contact_out_t *dout);
+/* The same template on the CPU (host arrays, needs no GPU): the checker.  Returns TDS_ERR_INVALID_ARG where some
+   environment's M was not positive definite, after writing every output. */
+int tds_hip_contacts_jvp_host(const tds_model_t *model, int n, const double *x, int p, const tds_param_t *params,
+                              const double *theta, int k, const double *v, const tds_contact_out_t *out,
+                              const tds_contact_out_t *dout);
+/* K: the tangents a work item of tds_hip_contacts_jvp carries for this model's class; a refused model gives minus its
+   TDS_ERR_* code. */
+int tds_hip_contacts_jvp_tangents(const tds_model_t *model);
+
 /* Batched inverse kinematics (the reference's TinyInverseKinematics::compute of src/tiny_inverse_kinematics.h:140-247,
    for n environments at once): from q_init [n][dof_q], move the actuated coordinates until the k body points (link
    links[j], point body_points[j][3] in the link's own frame; the same for every environment) reach

@@ -9,4 +9,4 @@ from .hip_backend import params_apply  # noqa: F401,E402
 from . import ranks  # noqa: F401,E402
 from . import vec_env  # noqa: F401,E402
 from .vec_env import VectorizedAntEnv, VectorizedLaikagoEnv, VectorizedEnv  # noqa: F401,E402
-from .autograd import step_fn, param_step_fn, rb_rollout_fn, trajectory_fn, policy_trajectory_fn  # noqa: F401,E402
+from .autograd import step_fn, param_step_fn, rb_rollout_fn, trajectory_fn, policy_trajectory_fn, contact_fn  # noqa: F401,E402

@@ -15,7 +15,10 @@ in the state entries ``wrt`` (overwritten by u) and the parameters theta: see DE
 
 ``trajectory_fn(sim, steps, wrt, params, every)(x0, z, theta, u)`` is an articulated-body trajectory (forward_zero
 chained), differentiable in the record entries ``wrt`` (overwritten by z) and the parameters theta: see DESIGN.md,
-"Articulated trajectories"."""
+"Articulated trajectories".
+
+``contact_fn(sim, want, params)(x, theta)`` is the contact query (impulses, forces, ...), differentiable in x and theta:
+see DESIGN.md, "Derivatives of the contact query"."""
 
 _StepFunction = None
 _StepFunctionReverse = None
@@ -24,6 +27,7 @@ _RbRolloutFunction = None
 _RbRolloutReverseFunction = None
 _TrajectoryFunction = None
 _TrajectoryReverseFunction = None
+_ContactFunction = None
 
 
 def _function():
@@ -508,5 +512,76 @@ def policy_trajectory_fn(sim, steps: int, layer_sizes=None, activations=None, us
             raise ValueError("policy_trajectory_fn: theta given but no params selected")
         return _policy_trajectory_function().apply(x0, policy, theta, sim, int(steps), int(every), net, spec,
                                                    bool(obs_raw))
+
+    return f
+
+
+def _contact_function():
+    """the autograd.Function of contact_fn, built on first use"""
+    global _ContactFunction
+    if _ContactFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class ContactFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, theta, sim, want, params):
+                xd = x.detach().contiguous()
+                th = None if theta is None else theta.detach().contiguous()
+                n, nin, p = xd.shape[0], sim.input_dim, len(params)
+                need_x, need_th = ctx.needs_input_grad[0], theta is not None and ctx.needs_input_grad[1]
+                ctx.need, ctx.shared, ctx.nin = (need_x, need_th), th is not None and th.dim() == 1, nin
+                if not (need_x or need_th):
+                    res = sim.contacts_jvp(xd, None, want=want, params=params, theta=th)
+                    return tuple(res[k] for k in want)
+                # one unit direction per input that requires grad: the columns of J over [x | theta]
+                cols = list(range(nin) if need_x else ()) + list(range(nin, nin + p) if need_th else ())
+                v = torch.zeros((n, len(cols), nin + p), dtype=torch.float64, device=xd.device)
+                v[:, torch.arange(len(cols)), torch.tensor(cols)] = 1.0
+                tan, res = sim.contacts_jvp(xd, v, want=want, params=params, theta=th, want_primal=True)
+                ctx.save_for_backward(*[tan[k].reshape(n, len(cols), -1) for k in want])  # J^T per output
+                return tuple(res[k] for k in want)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, *grads):
+                g = None
+                for jt, gy in zip(ctx.saved_tensors, grads):
+                    if gy is None:
+                        continue
+                    t = torch.bmm(jt, gy.to(jt.dtype).reshape(jt.shape[0], -1, 1)).squeeze(2)
+                    g = t if g is None else g + t
+                need_x, need_th = ctx.need
+                gx = g[:, :ctx.nin] if need_x and g is not None else None
+                gth = g[:, (ctx.nin if need_x else 0):] if need_th and g is not None else None
+                if gth is not None and ctx.shared:  # one theta for every environment: its gradient sums over them
+                    gth = gth.sum(0)
+                return gx, gth, None, None, None
+
+        _ContactFunction = ContactFunction
+    return _ContactFunction
+
+
+def contact_fn(sim, want=("force",), params=()):
+    """(x, theta=None) -> the contact query's outputs `want` (hip_backend.CONTACT_OUTPUTS; a tensor for one name, a
+    tuple for several) at the records x [N, input_dim] and the model parameters theta, differentiable in both.
+
+    params: the selection (hip_backend.param_spec, the contact kinds ("cfm",), ("erp",), ("geom_radius", g), ...
+    included).  theta: [p], shared by every environment (its gradient is summed over them), or [N, p]; None: the
+    model's values.  Forward mode, as step_fn / param_step_fn(mode="forward"): where an input requires grad the forward
+    pass forms the needed columns of J over [x | theta] with HipSim.contacts_jvp and backward is J^T grad by bmm, so a
+    forward pass that is differentiated costs ceil((input_dim + p) / K) blocks of K = contacts_jvp_tangents(model)
+    directions per environment (input_dim or p of them where only x or only theta requires grad) and one backward
+    costs no further launch.  Reverse mode is not built for the query."""
+    from . import hip_backend
+
+    names = hip_backend._contact_want(want)
+    sel = hip_backend.param_spec(params)
+    spec = [sel[j] for j in range(len(params))]
+    fn = _contact_function()
+
+    def f(x, theta=None):
+        out = fn.apply(x, theta, sim, names, spec)
+        return out[0] if len(names) == 1 else out
 
     return f

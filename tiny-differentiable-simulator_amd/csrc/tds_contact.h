@@ -1,8 +1,11 @@
 // tds_contact.h — one single-source, scalar-templated statement of the batched contact query (tds_contact.hip): what
 // the step forward_zero(x) does about its plane contacts — the contact points, their point Jacobians, the constraint
 // rows J and right-hand side b, the Delassus matrix A = J M^-1 J^T + cfm 1, the PGS impulses p, the world-frame contact
-// forces and the velocities before and after the solve.  Instantiated over double on the host (the checker) and on
-// the device.
+// forces and the velocities before and after the solve.  Instantiated over double and the blob's view on the host (the
+// checker) and on the device (tds_contact.hip), and over TdsDual<K> and an overlay of parameters for the query's
+// forward-mode derivatives in [x | theta] (tds_contact_jvp.hip): every selectable scalar of the contact model
+// (friction, restitution, cfm, erp, the shapes' radius, length, extents and X_trans) is read through the view P, the
+// contact points' offsets are formed in P::geom_scalar<T>; dt, the plane and the shapes' rotations are blob constants.
 //
 // It is built from tds_dyn.h: the kinematics, CRBA, bias (RNEA), the Cholesky solve for qdd (with tds_dyn.h's
 // floating-base arrangement, so that qd_pre is the reference's ABA's) and the point Jacobian, on the state reached
@@ -29,6 +32,20 @@ static inline TDS_HD int tds_contact_count(const tds_model_t *m) {
   if (m->has_plane)
     for (int g = 0; g < m->num_geoms; ++g) nc += tds_contact_points(m->geoms[g].type);
   return nc;
+}
+
+// the outputs a set of pointers asks for (those with extent: without contact points only qd_pre and qd_post)
+static inline int tds_contact_what(const tds_contact_out_t *o, int nc) {
+  int what = (o->qd_pre ? TDS_CT_QD_PRE : 0) | (o->qd_post ? TDS_CT_QD_POST : 0);
+  if (nc)
+    what |= (o->contacts ? TDS_CT_CONTACTS : 0) | (o->jac ? TDS_CT_JAC : 0) | (o->rows ? TDS_CT_ROWS : 0) |
+            (o->rhs ? TDS_CT_RHS : 0) | (o->delassus ? TDS_CT_DELASSUS : 0) | (o->impulse ? TDS_CT_IMPULSE : 0) |
+            (o->force ? TDS_CT_FORCE : 0);
+  return what;
+}
+
+static inline int tds_contact_any(const tds_contact_out_t *o) {
+  return o->contacts || o->jac || o->rows || o->rhs || o->delassus || o->impulse || o->force || o->qd_pre || o->qd_post;
 }
 
 // component offsets of one environment's state: tds_dyn.h's, then the record x, then the contact quantities
@@ -146,6 +163,36 @@ TDS_HD inline void tds_contact_matrix_to_quat(const T *m, T *q) {
   q[0] = e[0], q[1] = e[1], q[2] = e[2], q[3] = -e[3];
 }
 
+// ---------------------------------------------------------------- the shapes' scalars through the view
+// radius, capsule length, box extents and X_trans of geometry g (G = m->geoms[g], which the caller holds) as the view
+// gives them: p.geom_*(m, g).  The blob's view has overloads that read G itself: the same doubles, and the primal kernel
+// keeps its code to the instruction (through the view's own m->geoms[g] the compiler forms the addresses anew:
+// tds_contact_kernel 13 815 -> 13 989 instructions, 174 -> 240 SGPR spills).
+template <class P>
+TDS_HD inline decltype(auto) tds_contact_radius(P p, const tds_model_t *m, int g, const tds_geom_t &) {
+  return p.geom_radius(m, g);
+}
+template <class P>
+TDS_HD inline decltype(auto) tds_contact_length(P p, const tds_model_t *m, int g, const tds_geom_t &) {
+  return p.geom_length(m, g);
+}
+template <class P>
+TDS_HD inline decltype(auto) tds_contact_extents(P p, const tds_model_t *m, int g, const tds_geom_t &) {
+  return p.geom_extents(m, g);
+}
+template <class P>
+TDS_HD inline decltype(auto) tds_contact_trans(P p, const tds_model_t *m, int g, const tds_geom_t &) {
+  return p.geom_trans(m, g);
+}
+TDS_HD inline double tds_contact_radius(TdsBlobView, const tds_model_t *, int, const tds_geom_t &G) { return G.radius; }
+TDS_HD inline double tds_contact_length(TdsBlobView, const tds_model_t *, int, const tds_geom_t &G) { return G.length; }
+TDS_HD inline const double *tds_contact_extents(TdsBlobView, const tds_model_t *, int, const tds_geom_t &G) {
+  return G.extents;
+}
+TDS_HD inline const double *tds_contact_trans(TdsBlobView, const tds_model_t *, int, const tds_geom_t &G) {
+  return G.X_trans;
+}
+
 // ---------------------------------------------------------------- narrowphase, point Jacobians, rows
 // ref: world.hpp:206-282 (plane = multi body a, the robot b), contact_point.hpp:96-198; per point the ten numbers
 // world_normal_on_b | world_point_on_b | world_point_on_a | distance at L.cp, point_jacobian2(robot, link_b,
@@ -154,6 +201,7 @@ TDS_HD inline void tds_contact_matrix_to_quat(const T *m, T *q) {
 template <typename T, class P>
 TDS_HD inline void tds_contact_points_and_rows(const tds_model_t *m, P p, TdsDynMem<T> w, const TdsContactLayout &L,
                                                int rows) {
+  typedef typename P::template geom_scalar<T> S;  // the shapes' scalars: the contact points' offsets are formed in it
   const int nd = m->dof_qd, nc = L.nc;
   const double *n = m->plane_normal;
   double nrm[3] = {-n[0], -n[1], -n[2]}, f1[3], f2[3];
@@ -165,25 +213,26 @@ TDS_HD inline void tds_contact_points_and_rows(const tds_model_t *m, P p, TdsDyn
     if (!np) continue;
     TdsDXf<T> X, tr;
     tds_dyn_ld(w, G.link >= 0 ? L.D.xw + 12 * G.link : L.D.base, X);
-    tds_d_xf_mul(X, G.X_rot, G.X_trans, tr);  // world.hpp:242
+    tds_d_xf_mul(X, G.X_rot, tds_contact_trans(p, m, g, G), tr);  // world.hpp:242
     T orn[4];
     tds_contact_matrix_to_quat(tr.r, orn);  // world.hpp:244-245
     tds_d_quat_normalize(orn);
-    double rad = G.radius, dx = 0.0, dy = 0.0, dz = 0.0;
+    S rad = tds_contact_radius(p, m, g, G), dx = S(0.0), dy = S(0.0), dz = S(0.0);
     if (G.type == TDS_GEOM_CAPSULE) {  // contact_point.hpp:127-161
-      dz = 0.5 * G.length;
-    } else if (G.type == TDS_GEOM_BOX) {  // :163-198, geometry.hpp:244-259
-      rad = G.radius > 1e-2 ? G.radius : 1e-2;
-      dx = G.extents[0] * 0.5 - rad, dy = G.extents[1] * 0.5 - rad, dz = G.extents[2] * 0.5 - rad;
+      dz = 0.5 * tds_contact_length(p, m, g, G);
+    } else if (G.type == TDS_GEOM_BOX) {  // :163-198, geometry.hpp:244-259; a branch of the primal (tds_d_contacts)
+      rad = rad > 1e-2 ? rad : S(1e-2);
+      const auto ext = tds_contact_extents(p, m, g, G);
+      dx = ext[0] * 0.5 - rad, dy = ext[1] * 0.5 - rad, dz = ext[2] * 0.5 - rad;
     }
     for (int e = 0; e < np; ++e, ++c) {
       T pos[3];
       if (G.type == TDS_GEOM_SPHERE) {
         for (int k = 0; k < 3; ++k) pos[k] = tr.t[k];
       } else {
-        double off[3];
+        S off[3];
         if (G.type == TDS_GEOM_CAPSULE)
-          off[0] = 0.0, off[1] = 0.0, off[2] = e == 0 ? dz : -dz;
+          off[0] = S(0.0), off[1] = S(0.0), off[2] = e == 0 ? dz : -dz;
         else
           off[0] = (e & 4) ? -dx : dx, off[1] = (e & 2) ? -dy : dy, off[2] = (e & 1) ? -dz : dz;
         T ro[3];
@@ -214,7 +263,7 @@ TDS_HD inline void tds_contact_points_and_rows(const tds_model_t *m, P p, TdsDyn
       }
       // rel_vel = -vel (:315); b rows (:321-325, :365-370), J rows (:300-307, :378-384)
       const T nrv = -(nrm[0] * vel[0] + nrm[1] * vel[1] + nrm[2] * vel[2]);
-      w[L.b + c] = hit ? (-(1.0 + p.restitution(m)) * nrv - m->erp * dist / m->dt) : T(0.0);
+      w[L.b + c] = hit ? (-(1.0 + p.restitution(m)) * nrv - p.erp(m) * dist / m->dt) : T(0.0);
       w[L.b + nc + c] = hit ? (f1[0] * vel[0] + f1[1] * vel[1] + f1[2] * vel[2]) : T(0.0);
       w[L.b + 2 * nc + c] = hit ? (f2[0] * vel[0] + f2[1] * vel[1] + f2[2] * vel[2]) : T(0.0);
       for (int d = 0; d < nd; ++d) {
@@ -256,7 +305,7 @@ TDS_HD inline void tds_contact_solve(const tds_model_t *m, P p, TdsDynMem<T> w, 
       for (int s = 0; s <= r; ++s) {
         T a = T(0.0);
         for (int d = 0; d < nd; ++d) a = a + w[L.J + r * nd + d] * w[L.W + s * nd + d];
-        if (r == s) a = a + m->cfm;
+        if (r == s) a = a + p.cfm(m);
         w[L.A + r * nr + s] = a, w[L.A + s * nr + r] = a;
       }
   if (!(what & (TDS_CT_IMPULSE | TDS_CT_FORCE | TDS_CT_QD_POST))) return;
@@ -271,7 +320,7 @@ TDS_HD inline void tds_contact_solve(const tds_model_t *m, P p, TdsDynMem<T> w, 
       }
       const T pr = w[L.p + r];
       const T delta = Ju - Arr * pr;
-      T x = (w[L.b + r] - delta) / (Arr + m->cfm);
+      T x = (w[L.b + r] - delta) / (Arr + p.cfm(m));
       if (r < nc) {  // normal: [0, 1e5]  (:417-424)
         x = tds_clamp(x, T(0.0), T(100000.0));
       } else {  // friction: +-mu max(p_normal, 0)  (:426-436)

@@ -40,19 +40,6 @@ __global__ void __launch_bounds__(64) tds_contact_kernel(TdsContactArgs a, doubl
   }
 }
 
-int tds_contact_what(const tds_contact_out_t *o, int nc) {
-  int what = (o->qd_pre ? TDS_CT_QD_PRE : 0) | (o->qd_post ? TDS_CT_QD_POST : 0);
-  if (nc)
-    what |= (o->contacts ? TDS_CT_CONTACTS : 0) | (o->jac ? TDS_CT_JAC : 0) | (o->rows ? TDS_CT_ROWS : 0) |
-            (o->rhs ? TDS_CT_RHS : 0) | (o->delassus ? TDS_CT_DELASSUS : 0) | (o->impulse ? TDS_CT_IMPULSE : 0) |
-            (o->force ? TDS_CT_FORCE : 0);
-  return what;
-}
-
-int tds_contact_any(const tds_contact_out_t *o) {
-  return o->contacts || o->jac || o->rows || o->rhs || o->delassus || o->impulse || o->force || o->qd_pre || o->qd_post;
-}
-
 }  // namespace
 
 extern "C" {

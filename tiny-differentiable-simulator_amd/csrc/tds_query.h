@@ -1,6 +1,6 @@
 // tds_query.h — what the one-lane-per-environment query units share (tds_dyn.hip: dynamics queries, tds_ik.hip:
-// inverse kinematics, tds_contact.hip: the contact query): the mapping, the record transfers of their kernels, the
-// launch plan and the host checkers' stride-1 state.
+// inverse kinematics, tds_contact.hip: the contact query, tds_contact_jvp.hip: its derivatives): the mapping, the
+// record transfers of their kernels, the launch plan and the host checkers' stride-1 state.
 //
 // MAPPING.  One lane per environment, workgroups of W <= 64 lanes (one wavefront, narrowed so that a small batch still
 // reaches every compute unit: tds_query_width), at most kQueryLanes lanes per launch and the grid's stride beyond.  An
@@ -66,6 +66,40 @@ __device__ inline void tds_query_emit(double *tile, TdsDynMem<double> w, int off
     for (int idx = t; idx < nv * tc; idx += W) {
       const int e = idx / tc, c = idx - e * tc;
       out[(size_t)(e0 + e) * nc + c0 + c] = tile[e * kTileS + c];
+    }
+    __syncthreads();
+  }
+}
+
+// The two transfers for records that are `stride` doubles apart in HBM (one direction's [nc] of [n][k][nc], or the
+// leading part of a wider record): `in` / `out` point at environment 0's record.  (Functions of their own, so that the
+// kernels of the contiguous transfers above keep their code.)
+__device__ inline void tds_query_ingest_strided(double *tile, TdsDynMem<double> w, int off, const double *in, int nc,
+                                                size_t stride, int e0, int nv) {
+  const int W = blockDim.x, t = threadIdx.x;
+  for (int c0 = 0; c0 < nc; c0 += kTileC) {
+    const int tc = nc - c0 < kTileC ? nc - c0 : kTileC;
+    for (int idx = t; idx < nv * tc; idx += W) {
+      const int e = idx / tc, c = idx - e * tc;
+      tile[e * kTileS + c] = in[(size_t)(e0 + e) * stride + c0 + c];
+    }
+    __syncthreads();
+    if (t < nv)
+      for (int c = 0; c < tc; ++c) w[off + c0 + c] = tile[t * kTileS + c];
+    __syncthreads();
+  }
+}
+__device__ inline void tds_query_emit_strided(double *tile, TdsDynMem<double> w, int off, double *out, int nc,
+                                              size_t stride, int e0, int nv, int bad) {
+  const int W = blockDim.x, t = threadIdx.x;
+  for (int c0 = 0; c0 < nc; c0 += kTileC) {
+    const int tc = nc - c0 < kTileC ? nc - c0 : kTileC;
+    if (t < nv)
+      for (int c = 0; c < tc; ++c) tile[t * kTileS + c] = bad ? __builtin_nan("") : w[off + c0 + c];
+    __syncthreads();
+    for (int idx = t; idx < nv * tc; idx += W) {
+      const int e = idx / tc, c = idx - e * tc;
+      out[(size_t)(e0 + e) * stride + c0 + c] = tile[e * kTileS + c];
     }
     __syncthreads();
   }

@@ -169,6 +169,10 @@ def lib():
         L.tds_hip_contacts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, CP]
         L.tds_hip_contacts_host.argtypes = [P, C.c_int, C.c_void_p, CP]
         L.tds_hip_contact_layout.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p]
+        cj_tail = [C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p, CP, CP]
+        L.tds_hip_contacts_jvp.argtypes = [C.c_void_p] + cj_tail
+        L.tds_hip_contacts_jvp_host.argtypes = [P] + cj_tail
+        L.tds_hip_contacts_jvp_tangents.argtypes = [P]
         IP = C.POINTER(IkOptions)
         L.tds_hip_ik_default_options.argtypes = [IP]
         L.tds_hip_ik_default_options.restype = None
@@ -414,6 +418,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
+    "tds_hip_contacts_jvp", "tds_hip_contacts_jvp_host", "tds_hip_contacts_jvp_tangents",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
     "tds_rb_vjp", "tds_rb_vjp_host", "tds_rb_vjp_plan",
@@ -660,6 +665,52 @@ def contacts_host(m: _model.Model, x, want=CONTACT_OUTPUTS, out=None):
     res, o = _host_outputs(contact_shapes(m, n), want, out, struct=ContactOut)
     _check(lib().tds_hip_contacts_host(C.byref(m), n, x.ctypes.data, C.byref(o)))
     return res
+
+
+def contacts_jvp_tangents(m: _model.Model) -> int:
+    """K: the directions a work item of HipSim.contacts_jvp carries for this model (tds_hip_contacts_jvp_tangents)"""
+    k = lib().tds_hip_contacts_jvp_tangents(C.byref(m))
+    if k < 0:
+        _check(-k)
+    return k
+
+
+def contact_tangent_shapes(m: _model.Model, n: int, k: int) -> dict:
+    """shapes of the tangents of a contact query over n records and k directions: [n, k, *output shape]"""
+    return {name: (n, k) + s[1:] for name, s in contact_shapes(m, n).items()}
+
+
+def contacts_jvp_host(m: _model.Model, x, v, want=CONTACT_OUTPUTS, params=(), theta=None, want_primal: bool = False,
+                      out=None, out_primal=None):
+    """Forward-mode derivatives of the contact query in [x | theta] on the CPU (tds_hip_contacts_jvp_host; the checker
+    of HipSim.contacts_jvp, needs no GPU).
+
+    x [N, input_dim]; v [N, k, input_dim + p]: directions over the record and the selection `params` (param_spec; the
+    contact kinds included); theta [p] or [N, p]: the selection's values (None: the model's).  Returns a dict of the
+    wanted outputs' tangents [N, k, *shape] (contact_tangent_shapes), with want_primal (tangents, primal): the outputs
+    themselves at theta as well.  v None: the primal dict alone (k = 0).  An environment whose M is not positive
+    definite has NaN in rows .. qd_post and their tangents; the call then raises after writing (pass out / out_primal,
+    dicts of arrays to write the tangents / the primal into, to see what it wrote)."""
+    import numpy as np
+
+    want = _contact_want(want)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
+    n, p = x.shape[0], len(params)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    thp = None if th is None or p == 0 else th.ctypes.data
+    primal, po = _host_outputs(contact_shapes(m, n), want, out_primal, struct=ContactOut)
+    if v is None:
+        _check(lib().tds_hip_contacts_jvp_host(C.byref(m), n, x.ctypes.data, p, sel, thp, 0, None, C.byref(po), None))
+        return primal
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.ndim != 3 or v.shape[0] != n or v.shape[2] != m.input_dim + p or v.shape[1] < 1:
+        raise ValueError(f"v: expected [{n}, k >= 1, {m.input_dim + p}], got {tuple(v.shape)}")
+    k = v.shape[1]
+    tan, to = _host_outputs(contact_tangent_shapes(m, n, k), want, out, struct=ContactOut)
+    _check(lib().tds_hip_contacts_jvp_host(C.byref(m), n, x.ctypes.data, p, sel, thp, k, v.ctypes.data,
+                                           C.byref(po) if want_primal else None, C.byref(to)))
+    return (tan, primal) if want_primal else tan
 
 
 def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points=None, q_reference=None,
@@ -1727,6 +1778,50 @@ class HipSim:
         res, o = _dev_outputs(contact_shapes(self.model, n), want, out, x.device, struct=ContactOut)
         _check(lib().tds_hip_contacts(self.h, n, C.c_void_p(x.data_ptr()), C.byref(o)))
         return res
+
+    def contacts_jvp(self, x, v, want=CONTACT_OUTPUTS, params=(), theta=None, out=None, want_primal: bool = False):
+        """Forward-mode derivatives of the contact query in [x | theta] (tds_hip_contacts_jvp): for directions v
+        [N, k, input_dim + p] over the record and the selection `params` (param_spec, the contact kinds included) the
+        tangents of the wanted CONTACT_OUTPUTS, a dict of tensors [N, k, *shape] (contact_tangent_shapes); with
+        want_primal (tangents, primal): the outputs themselves as well.  theta [p] or [N, p]: the selection's values
+        (None: the model's).  v None: the primal dict at theta alone.  out: a dict of tangent tensors to write into.
+        The derivative of the algorithm as executed (contact activation, PGS projections and the actuation clamps
+        follow the primal's branch; a separated point has zero tangents).  Any N; f64 handles only; one launch over
+        (environment, block of contacts_jvp_tangents(model) directions) items (async)."""
+        want = _contact_want(want)
+        x = _dev_records(x, self.input_dim, "x")
+        n, p = x.shape[0], len(params)
+        sel = param_spec(params)
+        th = None if theta is None or p == 0 else self._theta(theta, n, p)
+        thp = None if th is None else C.c_void_p(th.data_ptr())
+        primal, po = _dev_outputs(contact_shapes(self.model, n), want if (want_primal or v is None) else (), None,
+                                  x.device, struct=ContactOut)
+        if v is None:
+            _check(lib().tds_hip_contacts_jvp(self.h, n, C.c_void_p(x.data_ptr()), p, sel, thp, 0, None, C.byref(po),
+                                              None))
+            return primal
+        import torch
+
+        assert v.is_cuda and v.dtype == torch.float64 and v.dim() == 3 and v.shape[1] >= 1 and \
+            tuple(v.shape[::2]) == (n, self.input_dim + p), "v: expected [N, k >= 1, input_dim + p]"
+        v, k = v.contiguous(), v.shape[1]
+        tan, to = _dev_outputs(contact_tangent_shapes(self.model, n, k), want, out, x.device, struct=ContactOut)
+        _check(lib().tds_hip_contacts_jvp(self.h, n, C.c_void_p(x.data_ptr()), p, sel, thp, k, C.c_void_p(v.data_ptr()),
+                                          C.byref(po), C.byref(to)))
+        return (tan, primal) if want_primal else tan
+
+    def contacts_jacobian(self, x, want, cols=None, params=(), theta=None):
+        """The dense derivative of one contact output: [N, *shape, n_cols], columns `cols` indexing into [x | theta]
+        (None: all input_dim + p), from identity directions through contacts_jvp."""
+        import torch
+
+        n, nall = x.shape[0], self.input_dim + len(params)
+        cols = torch.arange(nall, device=x.device) if cols is None else torch.as_tensor(cols, device=x.device).long()
+        v = torch.zeros((n, cols.numel(), nall), dtype=torch.float64, device=x.device)
+        v[:, torch.arange(cols.numel(), device=x.device), cols] = 1.0
+        (name,) = _contact_want(want)
+        t = self.contacts_jvp(x, v, want=(name,), params=params, theta=theta)[name]
+        return t.movedim(1, -1).contiguous()
 
     def contact_forces(self, x):
         """force [N, n_c, 3]: the world-frame contact force on the robot at each contact point of the step from x"""
