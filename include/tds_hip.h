@@ -1016,6 +1016,12 @@ int tds_hip_launch_plan_host(const tds_model_t *model, int dtype, int num_envs, 
    code. */
 #define TDS_OCT_WINDOW_PLAN_INTS 3
 int tds_hip_oct_window_plan_host(int max_contacts, int pgs_iterations, int long_window_option, int *out, int n_out);
+/* The same walk with the main wavefront's first sweep in the instantiation specialised for the contact count where option
+   oct_sweep_na = `sweep_na_option` sends it there (step-loop build for one wavefront per SIMD).  out[TDS_OCT_SWEEP_NA_PLAN_INTS]:
+   barriers the main wavefront takes, barriers the helper takes, 1 if the first sweep is a specialised one. */
+#define TDS_OCT_SWEEP_NA_PLAN_INTS 3
+int tds_hip_oct_sweep_na_plan_host(int max_contacts, int pgs_iterations, int long_window_option, int sweep_na_option, int *out,
+                                   int n_out);
 
 /* ======================================================================================
  * Multi-GPU: the global batch of environments is cut into equal contiguous shards, one per rank /

@@ -276,6 +276,7 @@ int launch(tds_hip_sim *s, const void *x, void *y, const void *actions, void *fb
   else if (!y_stride_set) ctl.y_stride = s->model.output_dim;  // (the kernels read the stride as it is: never 0)
   ctl.flags |= ctl_flags;
   if (s->opt.get(TDS_OPT_OCT_LONG_WINDOW, 1) != 0) ctl.flags |= TDS_CTL_OCT_LONG_WINDOW;
+  if (s->opt.get(TDS_OPT_OCT_SWEEP_NA, 1) != 0) ctl.flags |= TDS_CTL_OCT_SWEEP_NA;
   ctl.nsub = nsub;
   ctl.reset_mode = reset_mode;
   ctl.settle_steps = s->model.settle_steps < 0 ? 0 : s->model.settle_steps;
@@ -2184,6 +2185,7 @@ int tds_hip_profile_phases(tds_hip_sim_t *s, long long *cycles_host, int n) {
   ctl.nsub = 1;
   ctl.y_stride = s->model.output_dim;
   if (s->opt.get(TDS_OPT_OCT_LONG_WINDOW, 1) != 0) ctl.flags |= TDS_CTL_OCT_LONG_WINDOW;
+  if (s->opt.get(TDS_OPT_OCT_SWEEP_NA, 1) != 0) ctl.flags |= TDS_CTL_OCT_SWEEP_NA;
   if (s->opt.is_set(TDS_OPT_GRAM_STAMP_AT)) ctl.flags |= (int)s->opt.v[TDS_OPT_GRAM_STAMP_AT] << 8;  // (stamp 10 inside tds_gram_solve)
   // (profiling builds of the kernels, -DTDS_PROF_LOOP: the stamps of iteration K / 2 of a K-step launch of the two-wavefront
   //  step-loop kernel — TDS_HIP_PROF_LOOP=K; the library's own kernels have no such build and ignore the request)
@@ -2343,6 +2345,17 @@ int tds_hip_oct_window_plan_host(int max_contacts, int pgs_iterations, int long_
   out[1] = tds_oct_help_barriers(max_contacts, pgs_iterations);
   out[2] = tds_oct_long_window(max_contacts, pgs_iterations, long_window_option) ? 1 : 0;
   return TDS_OCT_WINDOW_PLAN_INTS;
+}
+
+int tds_hip_oct_sweep_na_plan_host(int max_contacts, int pgs_iterations, int long_window_option, int sweep_na_option, int *out,
+                                   int n_out) {
+  if (!out || n_out < TDS_OCT_SWEEP_NA_PLAN_INTS || max_contacts < 0 || pgs_iterations < 0)
+    return fail(TDS_ERR_INVALID_ARG, "sweep plan: bad arguments");
+  out[0] = tds_oct_main_barriers_sweep_na(max_contacts, pgs_iterations, long_window_option, sweep_na_option);
+  out[1] = tds_oct_help_barriers(max_contacts, pgs_iterations);
+  const bool lw = tds_oct_long_window(max_contacts, pgs_iterations, long_window_option);
+  out[2] = pgs_iterations > 0 && tds_oct_sweep_na(max_contacts, 0, tds_oct_main_windows(lw, 0, 0), sweep_na_option) ? 1 : 0;
+  return TDS_OCT_SWEEP_NA_PLAN_INTS;
 }
 
 }  // extern "C"

@@ -48,6 +48,9 @@ struct TdsLds {
 // 8-lane kernel (tds_oct.hip), two-wavefront builds: the first row window of a step runs on through a short second one
 // (option oct_long_window, default on; tds_oct_windows.h)
 #define TDS_CTL_OCT_LONG_WINDOW 4
+// 8-lane kernel, step-loop build for one wavefront per SIMD: the first sweep of a step in the instantiation specialised for the
+// wavefront's contact count (option oct_sweep_na, default on; tds_oct_windows.h)
+#define TDS_CTL_OCT_SWEEP_NA 16
 struct TdsStepCtl {
   int nsub;                   // normal steps in this launch (0 for a pure reset launch)
   int reset_mode;             // TDS_RESET_*
@@ -72,7 +75,7 @@ struct TdsStepCtl {
   int flags;                  // bit 0: the first step observes the raw base x, y (state fresh from reset())
                               // TDS_CTL_RESET_CALL: the launch is tds_hip_reset (the environment's own reset():
                               // its observation keeps the base x, y where the model says so), not an auto-reset
-                              // TDS_CTL_OCT_LONG_WINDOW: see there
+                              // TDS_CTL_OCT_LONG_WINDOW, TDS_CTL_OCT_SWEEP_NA: see there
   // step-loop launches only: per-step RECORD RINGS (tds_hip_step_many_rings).  With a ring set, EVERY step of the launch
   // does the whole output work of step_forward_original + VectorizedEnvironment::step — visual poses, y record,
   // reward / done, observation (locomotion_contact_simulation.h:273-303, ars_vectorized_environment.h:240-289) — and

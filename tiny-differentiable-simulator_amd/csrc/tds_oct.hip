@@ -129,6 +129,11 @@ __device__ int tds_oct_prof_iter = 500;
 #ifndef TDS_OCT_HELP_SCHUR
 #define TDS_OCT_HELP_SCHUR 1
 #endif
+// The first Gauss-Seidel sweep of the same build, specialised for NA = 1 .. 4 (main_sweep; run-time option oct_sweep_na, default 1):
+//   TDS_OCT_SWEEP_NA       0 compiles the four instantiations out; every statement then stands where it stood
+#ifndef TDS_OCT_SWEEP_NA
+#define TDS_OCT_SWEEP_NA 1
+#endif
 
 namespace {
 
@@ -296,6 +301,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // behind (2); the helper's next write to it is behind (1b) of the next step.
   constexpr bool POSES_LATE = LOOP && BUILD == 3 && TDS_OCT_POSES_LATE != 0;
   constexpr bool HELP_SCHUR = LOOP && BUILD == 3 && TDS_OCT_HELP_SCHUR != 0;
+  // SWEEP_NA: main_sweep's instantiations with NA as a template constant (the same build only)
+  constexpr bool SWEEP_NA = LOOP && BUILD == 3 && TDS_OCT_SWEEP_NA != 0;
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -1444,17 +1451,20 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //      the first: the same immediate offsets off the same bases — instead of returning to the window loop for a window of
   //      one to four rows.  They are second-tangent rows (8 >= 2 NA): the friction arm with xs2 only.  The second window's
   //      barrier is taken in position 7, in front of the request for position 8's operands.
-  auto main_sweep = [&](auto firstc, int w0, int bo, bool lw) {
+  //      SWEEP_NA (NAC = 1 .. 4; the first iteration's sweep from position 0 where it covers all 3 NA rows — one window, or the
+  //      long window): NA is a template constant, the rows are straight-line — every row's kind static, no compare, no branch —,
+  //      and the normal rows' clamped impulses stay in registers for their friction rows (the stores xw[k] stay: later
+  //      iterations read them): no address select, no read, no canonicalising maximum, no wait for the LDS behind the sum.
+  //      The long window's second barrier stands where it stands in the generic chain: position 7, in front of position 8's
+  //      request.  The same process() as the generic chain: the same expressions, contracted alike.
+  auto main_sweep = [&](auto firstc, auto nac, int w0, int bo, bool lw) {
       constexpr bool FIRST = decltype(firstc)::value;
+      constexpr int NAC = decltype(nac)::value;
       constexpr int KMAX = (FIRST && W2) ? 12 : 8;
       OCT_MARK("sweep");
       const T *const Zs = E + O.win + bo;
       T *const xw = E + O.xs + w0;  // the window's impulses
       const T my_hip = sw_hip, mu = sw_mu, rest = sw_rest;
-      // rows 0 .. wn - 1 of the window exist, rows 0 .. k_n - 1 are normal rows, rows k_t2 .. are second tangents (compared with
-      // the row index 0 .. 7 only: no clamping)
-      const int wn = 3 * NA - w0, k_n = NA - w0, k_t2 = 2 * NA - w0;
-      const T *const xs1 = xw - NA, *const xs2 = xw - 2 * NA;  // the impulse of a first / second tangent row's normal row
       struct Ops { T zs, zm, b, a, g, hl, sd, xo; };
       auto request = [&](auto kc, Ops &o) {
         constexpr int k = decltype(kc)::value;
@@ -1469,7 +1479,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           o.xo = xw[k];
         }
       };
-      auto process = [&](auto kc, const Ops &o, auto normalc) {
+      auto process = [&](auto kc, const Ops &o, auto normalc) -> T {
         constexpr int k = decltype(kc)::value;
         constexpr bool NORMAL = decltype(normalc)::value;
         const T zl = o.hl == my_hip ? o.zs : T(0);
@@ -1483,7 +1493,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         T sd = T(0);
         if constexpr (!NORMAL) {
           sd = o.sd;
-          if constexpr (SD_LATE) asm volatile("" : "+v"(jw), "+v"(sd));
+          // (NAC > 0: sd is a register of this chain, known to be canonical — pinned, it would be canonicalised again)
+          if constexpr (SD_LATE && NAC == 0) asm volatile("" : "+v"(jw), "+v"(sd));
         }
         T xn;
         if constexpr (FIRST) xn = (o.b - jw) * o.a;
@@ -1502,47 +1513,82 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         u += zl * dx;
         urm += o.zm * dx;
         xw[k] = xn;  // (every lane the same value to the same slot)
+        return xn;
       };
       Ops ops[2];
-      auto rows = [&](auto self, auto kc) -> void {
-        constexpr int k = decltype(kc)::value;
-        if constexpr (k < 8) {
-          if (k >= wn) return;
+      if constexpr (NAC > 0) {
+        constexpr int NR = 3 * NAC;
+        // (the barrier inside the chain — position 7, where a position 8 follows — is the one the host's walk counts)
+        static_assert((NR > 8 ? 1 : 0) == tds_oct_sweep_na_inner_barriers(NAC), "tds_oct_windows.h: barriers inside the specialised sweep");
+        T xnorm[NAC];  // the normal rows' impulses
+        request(std::integral_constant<int, 0>{}, ops[0]);
+        static_for<0, NR>([&](auto kc) {
+          constexpr int k = decltype(kc)::value;
           Ops &cur = ops[k & 1];
-          // (the next row's operands in front of the branch on the row's kind: requested inside both arms, the arms' loads
-          //  into the same registers cost a wait each)
-          if constexpr (k < 7) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
-          if (k < k_n) {
-            process(kc, cur, std::true_type{});
+          if constexpr (k + 1 < NR) {
+            if constexpr (k == 7) OCT_BAR_W(30, false);  // (the second window's barrier: NR > 8 is the long window)
+            request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
+          }
+          // (fences: the next row's requests in front of this row's arithmetic, which covers their round trip, and none of the
+          //  next row's arithmetic inside this row — left to itself the back end issues the requests behind this row's store,
+          //  folds the next row's product into this row and waits for the round trip at the top of the 8-lane sum; in the
+          //  generic chain the branches on the row's kind stand where the fences stand here)
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (k < NAC) {
+            xnorm[k] = process(kc, cur, std::true_type{});
           } else {
-            cur.sd = (k >= k_t2 ? xs2 : xs1)[k];
-            if constexpr (k == 7 && KMAX > 8) {
-              // (the second window's barrier, in the friction arm: a long window's position 7 is a friction row — 3 NA <= 12,
-              //  so k_n = NA <= 4.  Behind the request for the normal row's impulse the barrier's wait for the LDS is the one
-              //  this row sits out anyway; it completes the position's own operand reads — the last reads of the first buffer —
-              //  in front of the barrier, and position 8's operands then arrive under the whole of this row's arithmetic)
-              if (lw) {
-                OCT_BAR_W(30, false);
-                request(std::integral_constant<int, 8>{}, ops[0]);
-              }
-            }
+            cur.sd = xnorm[k < 2 * NAC ? k - NAC : k - 2 * NAC];
             process(kc, cur, std::false_type{});
           }
-          self(self, std::integral_constant<int, k + 1>{});
-        } else if constexpr (k < KMAX) {
-          // positions 8 .. 11 of a long first window (position 8 exists whenever the window is long)
-          if (k == 8 ? !lw : k >= wn) return;
-          Ops &cur = ops[k & 1];
-          if constexpr (k + 1 < KMAX) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
-          cur.sd = xs2[k];
-          process(kc, cur, std::false_type{});
-          self(self, std::integral_constant<int, k + 1>{});
-        }
-      };
-      request(std::integral_constant<int, 0>{}, ops[0]);
-      rows(rows, std::integral_constant<int, 0>{});
-      OCT_SYNC();
-      OCT_MARK("sweep_end");
+          __builtin_amdgcn_sched_barrier(0);
+        });
+        OCT_SYNC();
+        OCT_MARK("sweep_end");
+      } else {
+        // rows 0 .. wn - 1 of the window exist, rows 0 .. k_n - 1 are normal rows, rows k_t2 .. are second tangents (compared with
+        // the row index 0 .. 7 only: no clamping)
+        const int wn = 3 * NA - w0, k_n = NA - w0, k_t2 = 2 * NA - w0;
+        const T *const xs1 = xw - NA, *const xs2 = xw - 2 * NA;  // the impulse of a first / second tangent row's normal row
+        auto rows = [&](auto self, auto kc) -> void {
+          constexpr int k = decltype(kc)::value;
+          if constexpr (k < 8) {
+            if (k >= wn) return;
+            Ops &cur = ops[k & 1];
+            // (the next row's operands in front of the branch on the row's kind: requested inside both arms, the arms' loads
+            //  into the same registers cost a wait each)
+            if constexpr (k < 7) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
+            if (k < k_n) {
+              process(kc, cur, std::true_type{});
+            } else {
+              cur.sd = (k >= k_t2 ? xs2 : xs1)[k];
+              if constexpr (k == 7 && KMAX > 8) {
+                // (the second window's barrier, in the friction arm: a long window's position 7 is a friction row — 3 NA <= 12,
+                //  so k_n = NA <= 4.  Behind the request for the normal row's impulse the barrier's wait for the LDS is the one
+                //  this row sits out anyway; it completes the position's own operand reads — the last reads of the first buffer —
+                //  in front of the barrier, and position 8's operands then arrive under the whole of this row's arithmetic)
+                if (lw) {
+                  OCT_BAR_W(30, false);
+                  request(std::integral_constant<int, 8>{}, ops[0]);
+                }
+              }
+              process(kc, cur, std::false_type{});
+            }
+            self(self, std::integral_constant<int, k + 1>{});
+          } else if constexpr (k < KMAX) {
+            // positions 8 .. 11 of a long first window (position 8 exists whenever the window is long)
+            if (k == 8 ? !lw : k >= wn) return;
+            Ops &cur = ops[k & 1];
+            if constexpr (k + 1 < KMAX) request(std::integral_constant<int, k + 1>{}, ops[(k + 1) & 1]);
+            cur.sd = xs2[k];
+            process(kc, cur, std::false_type{});
+            self(self, std::integral_constant<int, k + 1>{});
+          }
+        };
+        request(std::integral_constant<int, 0>{}, ops[0]);
+        rows(rows, std::integral_constant<int, 0>{});
+        OCT_SYNC();
+        OCT_MARK("sweep_end");
+      }
   };
 
   // (the step's done flag on every lane of the environment, for main_pool: under the Ant's rule it never passes through LDS)
@@ -1875,8 +1921,20 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           const int nw = tds_oct_main_windows(lw, pit, w0);
           OCT_BAR_W(30, (pit | w0) == 0);
           if ((pit | w0) == 0) OCT_STAMP(12, tid);
-          if (pit == 0) main_sweep(std::true_type{}, w0, bo, nw == 2);
-          else main_sweep(std::false_type{}, w0, bo, false);
+          if (pit == 0) {
+            // (SWEEP_NA: wave-uniform; tds_oct_sweep_na: the sweep that starts here covers every row of the iteration and takes
+            //  the barriers the generic chain takes — none inside for one window, the long window's one in position 7)
+            if (SWEEP_NA && tds_oct_sweep_na(NA, w0, nw, ctl.flags & TDS_CTL_OCT_SWEEP_NA)) {
+              if (NA == 1) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 1 : 0>{}, 0, 0, false);
+              else if (NA == 2) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 2 : 0>{}, 0, 0, false);
+              else if (NA == 3) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 3 : 0>{}, 0, 0, true);
+              else main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 4 : 0>{}, 0, 0, true);
+            } else {
+              main_sweep(std::true_type{}, std::integral_constant<int, 0>{}, w0, bo, nw == 2);
+            }
+          } else {
+            main_sweep(std::false_type{}, std::integral_constant<int, 0>{}, w0, bo, false);
+          }
           if ((pit | w0) == 0) OCT_STAMP(13, u);
           // (a long window took two windows' rows and barriers: the buffers' turn comes out where it was)
           w0 += 8 * nw;
@@ -1952,8 +2010,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         rows_leg(bo, rw);
         rows_root(bo, rw);
         OCT_SYNC();
-        if (pit == 0) main_sweep(std::true_type{}, w0, bo, false);
-        else main_sweep(std::false_type{}, w0, bo, false);
+        if (pit == 0) main_sweep(std::true_type{}, std::integral_constant<int, 0>{}, w0, bo, false);
+        else main_sweep(std::false_type{}, std::integral_constant<int, 0>{}, w0, bo, false);
         bo = 8 * OctLds::ZW - bo;
       }
     }

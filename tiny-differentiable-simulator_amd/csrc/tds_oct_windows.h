@@ -53,6 +53,18 @@ __host__ __device__ inline int tds_oct_main_windows(bool long_window, int pit, i
 __host__ __device__ inline int tds_oct_help_first_w0(int pit) { return pit == 0 ? 8 : 0; }
 __host__ __device__ inline bool tds_oct_help_has_windows(int NA, int pgs_iters) { return NA > 0 && pgs_iters > 0; }
 
+// main wavefront, step-loop build for one wavefront per SIMD (option oct_sweep_na, default on): the first iteration's sweep that
+// starts at position w0 and covers nw windows runs in the instantiation specialised for NA (tds_oct.hip: main_sweep, NAC) —
+// exactly when that sweep holds ALL 3 NA rows of the iteration: NA = 1, 2 (one window) and NA = 3, 4 as a long window (nw = 2;
+// with option oct_long_window off they stay two ordinary windows on the generic chain).  The instantiation takes the barriers
+// the generic chain takes for the same (NA, nw): tds_oct_sweep_na_inner_barriers inside the sweep, the one at the window's top
+// in the caller's loop — the decision changes no count.
+__host__ __device__ inline bool tds_oct_sweep_na(int NA, int w0, int nw, int opt) {
+  return opt != 0 && w0 == 0 && NA >= 1 && NA <= 4 && (nw == 2 || 3 * NA <= 8);
+}
+// (barriers INSIDE the specialised sweep: the long window's second one, in position 7 — rows 3 NA > 8)
+__host__ __device__ constexpr int tds_oct_sweep_na_inner_barriers(int NA) { return 3 * NA > 8 ? 1 : 0; }
+
 // the two walks, as the kernel's loops do them: window barriers of one step
 inline int tds_oct_main_barriers(int NA, int pgs_iters, int opt) {
   const bool lw = tds_oct_long_window(NA, pgs_iters, opt);
@@ -62,6 +74,20 @@ inline int tds_oct_main_barriers(int NA, int pgs_iters, int opt) {
     for (int w0 = 0; w0 < nr;) {
       const int nw = tds_oct_main_windows(lw, pit, w0);
       b += nw;  // one at the top of the window; a long window's second one inside position 7
+      w0 += 8 * nw;
+    }
+  return b;
+}
+// the main wavefront's walk with the specialised first sweep where it is taken (sweep_na_opt: option oct_sweep_na)
+inline int tds_oct_main_barriers_sweep_na(int NA, int pgs_iters, int opt, int sweep_na_opt) {
+  const bool lw = tds_oct_long_window(NA, pgs_iters, opt);
+  const int nr = 3 * NA;
+  int b = 0;
+  for (int pit = 0; pit < pgs_iters; ++pit)
+    for (int w0 = 0; w0 < nr;) {
+      const int nw = tds_oct_main_windows(lw, pit, w0);
+      if (pit == 0 && tds_oct_sweep_na(NA, w0, nw, sweep_na_opt)) b += 1 + tds_oct_sweep_na_inner_barriers(NA);  // top + inside
+      else b += nw;
       w0 += 8 * nw;
     }
   return b;

@@ -406,7 +406,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_shard_local_envs", "tds_hip_shard_first_env", "tds_hip_shard_wire_bytes", "tds_hip_shard_set_block",
     "tds_hip_shard_step", "tds_hip_shard_step_many", "tds_hip_shard_step_many_prepare", "tds_hip_shard_group_step", "tds_hip_shard_flush", "tds_hip_shard_gathered", "tds_hip_shard_gathered_step",
     "tds_hip_shard_ring_plan", "tds_hip_shard_gathered_offset", "tds_hip_shard_exchange_form", "tds_hip_shard_peer_count",
-    "tds_hip_single_step_kernel", "tds_hip_launch_plan_host", "tds_hip_oct_window_plan_host",
+    "tds_hip_single_step_kernel", "tds_hip_launch_plan_host", "tds_hip_oct_window_plan_host", "tds_hip_oct_sweep_na_plan_host",
     "tds_hip_jvp", "tds_hip_jacobian", "tds_hip_jacobian_host", "tds_hip_jacobian_tangents",
     "tds_hip_vjp", "tds_hip_vjp_host", "tds_hip_vjp_host_tape",
     "tds_hip_params_get", "tds_hip_params_apply", "tds_hip_set_model_variants", "tds_hip_model_variants",
@@ -482,6 +482,17 @@ def oct_window_plan_host(max_contacts: int, pgs_iterations: int, long_window: in
     if rc != 3:
         _check(rc)
     return dict(main_barriers=out[0], help_barriers=out[1], long_window=bool(out[2]))
+
+
+def oct_sweep_na_plan_host(max_contacts: int, pgs_iterations: int, long_window: int = 1, sweep_na: int = 1):
+    """the same walk with the main wavefront's first sweep specialised for the contact count where option oct_sweep_na sends it
+    there (tds_hip_oct_sweep_na_plan_host; no device needed): dict main_barriers / help_barriers / specialised"""
+    out = (C.c_int * 3)()
+    lib().tds_hip_oct_sweep_na_plan_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
+    rc = lib().tds_hip_oct_sweep_na_plan_host(int(max_contacts), int(pgs_iterations), int(long_window), int(sweep_na), out, 3)
+    if rc != 3:
+        _check(rc)
+    return dict(main_barriers=out[0], help_barriers=out[1], specialised=bool(out[2]))
 
 
 def default_option(key: str, value) -> None:
