@@ -830,6 +830,42 @@ int tds_hip_inverse_dynamics_host(const tds_model_t *model, int n, const double 
 int tds_hip_point_jacobian_host(const tds_model_t *model, int n, const double *q, int link, const double *point,
                                 int is_local, double *jac);
 
+/* Forward-mode derivatives of tds_hip_dynamics and tds_hip_inverse_dynamics in their inputs and in model parameters.
+   The input of the dynamics call is  z = [q (dof_q) | qd (dof_qd) | tau (dof_qd - (6 on a floating base)) | theta (p)],
+   that of the inverse-dynamics call  z = [q (dof_q) | qd (dof_qd) | qdd (dof_qd) | theta (p)].  For directions
+   v [n][k][z] the tangents of every output `dout` names are written as [n][k][...the output's shape...]
+   (dtau [n][k][dof_qd]), and (optionally, in the same call) the primal outputs `out` names (tau_dev), at
+   theta_dev [n][p]: the selection params_host [p] of tds_hip_jvp_params, every kind tds_hip_params_get accepts;
+   theta_dev NULL: the model's values.  k = 0 gives the primal at per-environment theta only (dout / dtau_dev and v_dev
+   may then be NULL).  A NULL qd, tau or qdd stands for zeros in value; its columns of v still seed tangents.
+   Convention: the derivative of the statement as executed (tds_hip_jvp's); quaternion entries of a floating base's q
+   are differentiated raw.  The kinds the unconstrained dynamics do not read (friction, restitution, cfm, erp, the
+   collision shapes) give exactly zero tangents.  An environment whose M is not positive definite has NaN in qdd and in
+   qdd's tangents, and nowhere else.  Scope, refusals and messages: those of tds_hip_dynamics / tds_hip_inverse_dynamics
+   (bias and inverse dynamics need a fixed base); selection errors: tds_hip_params_get's.
+   Enqueued on the handle's stream as one launch.  The host waits only where the work buffer (shared with every other
+   derivative and query call: calls on the stream use it in turn) grows, or, with p > 0, where the selection is copied
+   into it (a blocking copy after a wait for the stream, as in tds_hip_jvp_params).  Work items are (environment,
+   block of K directions), K = tds_hip_dynamics_jvp_tangents(model); at most 16384 lanes per launch, more items are
+   walked with the grid's stride.  The primal is written by the items of the first block. */
+int tds_hip_dynamics_jvp(tds_hip_sim_t *sim, int n, const void *q_dev, const void *qd_dev, const void *tau_dev, int p,
+                         const tds_param_t *params_host, const void *theta_dev, int k, const void *v_dev,
+                         const tds_dyn_out_t *out, const tds_dyn_out_t *dout);
+int tds_hip_inverse_dynamics_jvp(tds_hip_sim_t *sim, int n, const void *q_dev, const void *qd_dev, const void *qdd_dev,
+                                 int p, const tds_param_t *params_host, const void *theta_dev, int k, const void *v_dev,
+                                 void *tau_dev, void *dtau_dev);
+/* The same template on the CPU (host arrays, need no GPU): the checkers.  tds_hip_dynamics_jvp_host returns
+   TDS_ERR_INVALID_ARG where some environment's M was not positive definite, after writing every output. */
+int tds_hip_dynamics_jvp_host(const tds_model_t *model, int n, const double *q, const double *qd, const double *tau,
+                              int p, const tds_param_t *params, const double *theta, int k, const double *v,
+                              const tds_dyn_out_t *out, const tds_dyn_out_t *dout);
+int tds_hip_inverse_dynamics_jvp_host(const tds_model_t *model, int n, const double *q, const double *qd,
+                                      const double *qdd, int p, const tds_param_t *params, const double *theta, int k,
+                                      const double *v, double *tau, double *dtau);
+/* K: the tangents a work item of the two device calls carries for this model's class; a refused model gives minus its
+   TDS_ERR_* code. */
+int tds_hip_dynamics_jvp_tangents(const tds_model_t *model);
+
 /* Batched contact query: what the step forward_zero(x) does about its plane contacts, for n records x [n][input_dim]
    (f64, the record of tds_hip_jvp / tds_hip_jacobian / tds_hip_step_host), per environment.  n_c is the model's number
    of plane contact points, a constant of the model: every point of every geometry (sphere 1, capsule 2, box 8, in

@@ -18,7 +18,11 @@ chained), differentiable in the record entries ``wrt`` (overwritten by z) and th
 "Articulated trajectories".
 
 ``contact_fn(sim, want, params)(x, theta)`` is the contact query (impulses, forces, ...), differentiable in x and theta:
-see DESIGN.md, "Derivatives of the contact query"."""
+see DESIGN.md, "Derivatives of the contact query".
+
+``dynamics_fn(sim, want, params)(q, qd, tau, theta)`` and ``inverse_dynamics_fn(sim, params)(q, qd, qdd, theta)`` are the
+batched dynamics queries (qdd, the mass matrix, ...; tau = ID), differentiable in every argument: see DESIGN.md,
+"Derivatives of the dynamics queries"."""
 
 _StepFunction = None
 _StepFunctionReverse = None
@@ -28,6 +32,7 @@ _RbRolloutReverseFunction = None
 _TrajectoryFunction = None
 _TrajectoryReverseFunction = None
 _ContactFunction = None
+_DynamicsFunction = None
 
 
 def _function():
@@ -583,5 +588,112 @@ def contact_fn(sim, want=("force",), params=()):
     def f(x, theta=None):
         out = fn.apply(x, theta, sim, names, spec)
         return out[0] if len(names) == 1 else out
+
+    return f
+
+
+def _dynamics_function():
+    """the autograd.Function of dynamics_fn and inverse_dynamics_fn, built on first use"""
+    global _DynamicsFunction
+    if _DynamicsFunction is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class DynamicsFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, q, qd, u, theta, sim, want, params, inverse):
+                from . import hip_backend
+
+                det = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+                qv, qdv, uv, th = det(q), det(qd), det(u), det(theta)
+                m, n, p = sim.model, q.shape[0], len(params)
+                widths = (m.dof_q, m.dof_qd, m.dof_qd if inverse else hip_backend.dyn_tau_dim(m), p)
+                need = tuple(t is not None and ctx.needs_input_grad[i] for i, t in enumerate((q, qd, u, theta)))
+                ctx.need, ctx.widths, ctx.shared = need, widths, th is not None and th.dim() == 1
+
+                def call(v):
+                    if inverse:
+                        r = sim.inverse_dynamics_jvp(qv, qdv, uv, v, params=params, theta=th, want_primal=True)
+                        return r if v is None else ({"tau": r[0]}, {"tau": r[1]})
+                    return sim.dynamics_jvp(qv, qdv, uv, v, want=want, params=params, theta=th, want_primal=True)
+
+                if not any(need):
+                    res = call(None)
+                    return (res,) if inverse else tuple(res[k] for k in want)
+                # one unit direction per input that requires grad: the columns of J over [q | qd | u | theta]
+                starts = [sum(widths[:i]) for i in range(4)]
+                cols = [c for i in range(4) if need[i] for c in range(starts[i], starts[i] + widths[i])]
+                v = torch.zeros((n, len(cols), sum(widths)), dtype=torch.float64, device=qv.device)
+                v[:, torch.arange(len(cols)), torch.tensor(cols)] = 1.0
+                tan, res = call(v)
+                ctx.save_for_backward(*[tan[k].reshape(n, len(cols), -1) for k in want])  # J^T per output
+                return tuple(res[k] for k in want)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, *grads):
+                g = None
+                for jt, gy in zip(ctx.saved_tensors, grads):
+                    if gy is None:
+                        continue
+                    t = torch.bmm(jt, gy.to(jt.dtype).reshape(jt.shape[0], -1, 1)).squeeze(2)
+                    g = t if g is None else g + t
+                out, o = [], 0
+                for need, width in zip(ctx.need, ctx.widths):
+                    out.append(g[:, o:o + width] if need and g is not None else None)
+                    o += width if need else 0
+                if out[3] is not None and ctx.shared:  # one theta for every environment: its gradient sums over them
+                    out[3] = out[3].sum(0)
+                return (*out, None, None, None, None)
+
+        _DynamicsFunction = DynamicsFunction
+    return _DynamicsFunction
+
+
+def _dynamics_fn(sim, names, params, inverse):
+    from . import hip_backend
+
+    sel = hip_backend.param_spec(params)
+    spec = [sel[j] for j in range(len(params))]
+    fn = _dynamics_function()
+
+    def f(q, qd, u, theta):
+        if theta is not None and not spec:
+            raise ValueError("dynamics_fn: theta given but no params selected")
+        out = fn.apply(q, qd, u, theta, sim, names, spec, inverse)
+        return out[0] if len(names) == 1 else out
+
+    return f
+
+
+def dynamics_fn(sim, want=("qdd",), params=()):
+    """(q, qd=None, tau=None, theta=None) -> the dynamics queries' outputs `want` (hip_backend.DYN_OUTPUTS; a tensor for
+    one name, a tuple for several) at the states q [N, dof_q], qd [N, dof_qd], the torques tau [N, dyn_tau_dim(model)]
+    (None: zero) and the model parameters theta, differentiable in all four.
+
+    params: the selection (hip_backend.param_spec).  theta: [p], shared by every environment (its gradient is summed
+    over them), or [N, p]; None: the model's values.  Forward mode, as contact_fn: where an input requires grad the
+    forward pass forms the needed columns of J over [q | qd | tau | theta] with HipSim.dynamics_jvp and backward is
+    J^T grad by bmm, so a forward pass that is differentiated costs ceil(columns / K) blocks of
+    K = dynamics_jvp_tangents(model) directions per environment and one backward costs no further launch.  Reverse mode
+    is not built for the queries."""
+    from . import hip_backend
+
+    g = _dynamics_fn(sim, hip_backend._dyn_want(want), params, False)
+
+    def f(q, qd=None, tau=None, theta=None):
+        return g(q, qd, tau, theta)
+
+    return f
+
+
+def inverse_dynamics_fn(sim, params=()):
+    """(q, qd=None, qdd=None, theta=None) -> tau [N, dof_qd] = ID(q, qd, qdd) (HipSim.inverse_dynamics; fixed base only)
+    at the model parameters theta, differentiable in all four; params, theta and the cost as for dynamics_fn, through
+    HipSim.inverse_dynamics_jvp."""
+    g = _dynamics_fn(sim, ("tau",), params, True)
+
+    def f(q, qd=None, qdd=None, theta=None):
+        return g(q, qd, qdd, theta)
 
     return f

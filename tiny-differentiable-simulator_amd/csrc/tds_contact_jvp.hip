@@ -16,6 +16,7 @@
 #include "tds_contact.h"
 #include "tds_dparam.h"
 #include "tds_query.h"
+#include "tds_query_dual.h"
 
 namespace {
 
@@ -29,12 +30,6 @@ struct TdsContactJvpK<TdsBoundA> { static constexpr int K = 2; };
 template <>
 struct TdsContactJvpK<TdsBoundL> { static constexpr int K = 2; };
 
-// the scalar of K tangents; K = 0: double
-template <int K>
-struct TdsContactScalar { using type = TdsDual<K>; };
-template <>
-struct TdsContactScalar<0> { using type = double; };
-
 struct TdsContactJvpArgs {
   const tds_model_t *m;
   int n, kdirs, p, what, with_A;
@@ -42,18 +37,6 @@ struct TdsContactJvpArgs {
   const tds_param_t *params;
   tds_contact_out_t out, dout;  // primal outputs; tangents [n][kdirs][shape]
 };
-
-// the value a double or a dual is built from
-TDS_HD inline void tds_contact_set_value(double &t, double v) { t = v; }
-template <int K>
-TDS_HD inline void tds_contact_set_value(TdsDual<K> &t, double v) {
-  t = TdsDual<K>(v);
-}
-TDS_HD inline void tds_contact_set_tangent(double &, int, double) {}
-template <int K>
-TDS_HD inline void tds_contact_set_tangent(TdsDual<K> &t, int k, double d) {
-  t.d[k] = d;
-}
 
 // theta of environment env and its tangents of directions d0 .. d0 + nk - 1 (zeros past them) into the seeded overlay:
 // both slots of each selected scalar (an off-diagonal inertia entry sets its mirror too).  theta NULL: the seed's value

@@ -173,6 +173,12 @@ def lib():
         L.tds_hip_contacts_jvp.argtypes = [C.c_void_p] + cj_tail
         L.tds_hip_contacts_jvp_host.argtypes = [P] + cj_tail
         L.tds_hip_contacts_jvp_tangents.argtypes = [P]
+        dj_tail = [C.c_int] + [C.c_void_p] * 3 + [C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p]
+        L.tds_hip_dynamics_jvp.argtypes = [C.c_void_p] + dj_tail + [DP, DP]
+        L.tds_hip_inverse_dynamics_jvp.argtypes = [C.c_void_p] + dj_tail + [C.c_void_p] * 2
+        L.tds_hip_dynamics_jvp_host.argtypes = [P] + dj_tail + [DP, DP]
+        L.tds_hip_inverse_dynamics_jvp_host.argtypes = [P] + dj_tail + [C.c_void_p] * 2
+        L.tds_hip_dynamics_jvp_tangents.argtypes = [P]
         IP = C.POINTER(IkOptions)
         L.tds_hip_ik_default_options.argtypes = [IP]
         L.tds_hip_ik_default_options.restype = None
@@ -419,6 +425,8 @@ EXPORTED_SYMBOLS = [
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_hip_contacts_jvp", "tds_hip_contacts_jvp_host", "tds_hip_contacts_jvp_tangents",
+    "tds_hip_dynamics_jvp", "tds_hip_inverse_dynamics_jvp", "tds_hip_dynamics_jvp_host",
+    "tds_hip_inverse_dynamics_jvp_host", "tds_hip_dynamics_jvp_tangents",
     "tds_rb_last_error", "tds_rb_create", "tds_rb_destroy", "tds_rb_set_stream", "tds_rb_state_device",
     "tds_rb_set_state", "tds_rb_get_state", "tds_rb_step", "tds_rb_jvp", "tds_rb_jvp_host", "tds_rb_params_get",
     "tds_rb_vjp", "tds_rb_vjp_host", "tds_rb_vjp_plan",
@@ -722,6 +730,96 @@ def contacts_jvp_host(m: _model.Model, x, v, want=CONTACT_OUTPUTS, params=(), th
     _check(lib().tds_hip_contacts_jvp_host(C.byref(m), n, x.ctypes.data, p, sel, thp, k, v.ctypes.data,
                                            C.byref(po) if want_primal else None, C.byref(to)))
     return (tan, primal) if want_primal else tan
+
+
+def dynamics_jvp_tangents(m: _model.Model) -> int:
+    """K: the directions a work item of HipSim.dynamics_jvp / inverse_dynamics_jvp carries for this model
+    (tds_hip_dynamics_jvp_tangents)"""
+    k = lib().tds_hip_dynamics_jvp_tangents(C.byref(m))
+    if k < 0:
+        _check(-k)
+    return k
+
+
+def dyn_tangent_shapes(m: _model.Model, n: int, k: int) -> dict:
+    """shapes of the tangents of a dynamics query over n states and k directions: [n, k, *output shape]"""
+    return {name: (n, k) + s[1:] for name, s in dyn_shapes(m, n).items()}
+
+
+def dyn_input_dim(m: _model.Model, inverse: bool = False) -> int:
+    """columns of z without theta: [q | qd | tau] of dynamics_jvp, [q | qd | qdd] of inverse_dynamics_jvp"""
+    return m.dof_q + m.dof_qd + (m.dof_qd if inverse else dyn_tau_dim(m))
+
+
+def _host_directions(v, n, width):
+    import numpy as np
+
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.ndim != 3 or v.shape[0] != n or v.shape[2] != width or v.shape[1] < 1:
+        raise ValueError(f"v: expected [{n}, k >= 1, {width}], got {tuple(v.shape)}")
+    return v
+
+
+def dynamics_jvp_host(m: _model.Model, q, qd=None, tau=None, v=None, want=DYN_OUTPUTS, params=(), theta=None,
+                      want_primal: bool = False, out=None, out_primal=None):
+    """Forward-mode derivatives of the dynamics queries in z = [q | qd | tau | theta] on the CPU
+    (tds_hip_dynamics_jvp_host; the checker of HipSim.dynamics_jvp, needs no GPU).
+
+    q [N, dof_q], qd [N, dof_qd], tau [N, dyn_tau_dim(m)] (None: zero in value); v [N, k, dyn_input_dim(m) + p]:
+    directions over z, theta the selection `params` (param_spec); theta [p] or [N, p]: the selection's values (None: the
+    model's).  Returns a dict of the wanted DYN_OUTPUTS' tangents [N, k, *shape] (dyn_tangent_shapes), with want_primal
+    (tangents, primal): the outputs themselves at theta as well.  v None: the primal dict alone (k = 0).  An environment
+    whose M is not positive definite has NaN in qdd and its tangents; the call then raises after writing (pass out /
+    out_primal, dicts of arrays to write the tangents / the primal into, to see what it wrote)."""
+    import numpy as np
+
+    want = _dyn_want(want)
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
+    n, p = q.shape[0], len(params)
+    qd, qdp = _host_rows(qd, n, m.dof_qd)
+    tau, taup = _host_rows(tau, n, dyn_tau_dim(m))
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    thp = None if th is None or p == 0 else th.ctypes.data
+    primal, po = _host_outputs(dyn_shapes(m, n), want, out_primal, struct=DynOut)
+    if v is None:
+        _check(lib().tds_hip_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, taup, p, sel, thp, 0, None,
+                                               C.byref(po), None))
+        return primal
+    v = _host_directions(v, n, dyn_input_dim(m) + p)
+    k = v.shape[1]
+    tan, to = _host_outputs(dyn_tangent_shapes(m, n, k), want, out, struct=DynOut)
+    _check(lib().tds_hip_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, taup, p, sel, thp, k, v.ctypes.data,
+                                           C.byref(po) if want_primal else None, C.byref(to)))
+    return (tan, primal) if want_primal else tan
+
+
+def inverse_dynamics_jvp_host(m: _model.Model, q, qd=None, qdd=None, v=None, params=(), theta=None,
+                              want_primal: bool = False):
+    """Forward-mode derivatives of tau = ID(q, qd, qdd) in z = [q | qd | qdd | theta] on the CPU
+    (tds_hip_inverse_dynamics_jvp_host; the checker of HipSim.inverse_dynamics_jvp): dtau [N, k, dof_qd] for
+    directions v [N, k, dof_q + 2 dof_qd + p], with want_primal (dtau, tau); v None: tau [N, dof_qd] at theta alone.
+    Arguments as for dynamics_jvp_host; fixed base only."""
+    import numpy as np
+
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
+    n, p, nd = q.shape[0], len(params), m.dof_qd
+    qd, qdp = _host_rows(qd, n, nd)
+    qdd, qddp = _host_rows(qdd, n, nd)
+    sel = param_spec(params)
+    th = None if theta is None else _theta_rows(theta, n, p)
+    thp = None if th is None or p == 0 else th.ctypes.data
+    tau = np.zeros((n, nd), dtype=np.float64)
+    if v is None:
+        _check(lib().tds_hip_inverse_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, qddp, p, sel, thp, 0, None,
+                                                       tau.ctypes.data, None))
+        return tau
+    v = _host_directions(v, n, dyn_input_dim(m, True) + p)
+    dtau = np.zeros((n, v.shape[1], nd), dtype=np.float64)
+    _check(lib().tds_hip_inverse_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, qddp, p, sel, thp, v.shape[1],
+                                                   v.ctypes.data, tau.ctypes.data if want_primal else None,
+                                                   dtau.ctypes.data))
+    return (dtau, tau) if want_primal else dtau
 
 
 def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points=None, q_reference=None,
@@ -1777,6 +1875,85 @@ class HipSim:
         _check(lib().tds_hip_point_jacobian(self.h, n, C.c_void_p(q.data_ptr()), int(link), ptp, int(bool(local)),
                                             C.c_void_p(jac.data_ptr())))
         return jac
+
+    # -- forward-mode derivatives of the dynamics queries in [q | qd | tau or qdd | theta] -------------------------
+    def _dyn_directions(self, v, n, width):
+        import torch
+
+        assert v.is_cuda and v.dtype == torch.float64 and v.dim() == 3 and v.shape[1] >= 1 and \
+            tuple(v.shape[::2]) == (n, width), f"v: expected [N, k >= 1, {width}]"
+        return v.contiguous(), v.shape[1]
+
+    def dynamics_jvp(self, q, qd=None, tau=None, v=None, want=DYN_OUTPUTS, params=(), theta=None, out=None,
+                     want_primal: bool = False):
+        """Forward-mode derivatives of the dynamics queries in z = [q | qd | tau | theta] (tds_hip_dynamics_jvp): for
+        directions v [N, k, dyn_input_dim(model) + p] over the states, the torques and the selection `params`
+        (param_spec) the tangents of the wanted DYN_OUTPUTS, a dict of tensors [N, k, *shape] (dyn_tangent_shapes);
+        with want_primal (tangents, primal): the outputs themselves as well.  qd, tau None: zero in value (their
+        columns of v still count).  theta [p] or [N, p]: the selection's values (None: the model's).  v None: the
+        primal dict at theta alone.  out: a dict of tangent tensors to write into.  Any N; f64 handles only; one launch
+        over (environment, block of dynamics_jvp_tangents(model) directions) items (async)."""
+        want = _dyn_want(want)
+        m = self.model
+        q = _dev_records(q, m.dof_q, "q")
+        n, p = q.shape[0], len(params)
+        qd, qdp = self._dyn_rows(qd, n, m.dof_qd, "qd")
+        tau, taup = self._dyn_rows(tau, n, dyn_tau_dim(m), "tau")
+        sel = param_spec(params)
+        th = None if theta is None or p == 0 else self._theta(theta, n, p)
+        thp = None if th is None else C.c_void_p(th.data_ptr())
+        primal, po = _dev_outputs(dyn_shapes(m, n), want if (want_primal or v is None) else (), None, q.device,
+                                  struct=DynOut)
+        if v is None:
+            _check(lib().tds_hip_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, p, sel, thp, 0, None,
+                                              C.byref(po), None))
+            return primal
+        v, k = self._dyn_directions(v, n, dyn_input_dim(m) + p)
+        tan, to = _dev_outputs(dyn_tangent_shapes(m, n, k), want, out, q.device, struct=DynOut)
+        _check(lib().tds_hip_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, p, sel, thp, k,
+                                          C.c_void_p(v.data_ptr()), C.byref(po), C.byref(to)))
+        return (tan, primal) if want_primal else tan
+
+    def inverse_dynamics_jvp(self, q, qd=None, qdd=None, v=None, params=(), theta=None, want_primal: bool = False):
+        """Forward-mode derivatives of tau = ID(q, qd, qdd) in z = [q | qd | qdd | theta]
+        (tds_hip_inverse_dynamics_jvp): dtau [N, k, dof_qd] for directions v [N, k, dof_q + 2 dof_qd + p], with
+        want_primal (dtau, tau); v None: tau [N, dof_qd] at theta alone.  Arguments as for dynamics_jvp; fixed base
+        only (async)."""
+        import torch
+
+        m = self.model
+        q = _dev_records(q, m.dof_q, "q")
+        n, p, nd = q.shape[0], len(params), m.dof_qd
+        qd, qdp = self._dyn_rows(qd, n, nd, "qd")
+        qdd, qddp = self._dyn_rows(qdd, n, nd, "qdd")
+        sel = param_spec(params)
+        th = None if theta is None or p == 0 else self._theta(theta, n, p)
+        thp = None if th is None else C.c_void_p(th.data_ptr())
+        tau = torch.empty((n, nd), dtype=torch.float64, device=q.device) if (want_primal or v is None) else None
+        taup = None if tau is None else C.c_void_p(tau.data_ptr())
+        if v is None:
+            _check(lib().tds_hip_inverse_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, p, sel, thp, 0,
+                                                      None, taup, None))
+            return tau
+        v, k = self._dyn_directions(v, n, dyn_input_dim(m, True) + p)
+        dtau = torch.empty((n, k, nd), dtype=torch.float64, device=q.device)
+        _check(lib().tds_hip_inverse_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, p, sel, thp, k,
+                                                  C.c_void_p(v.data_ptr()), taup, C.c_void_p(dtau.data_ptr())))
+        return (dtau, tau) if want_primal else dtau
+
+    def dynamics_jacobian(self, q, qd=None, tau=None, want="qdd", cols=None, params=(), theta=None):
+        """The dense derivative of one dynamics output: [N, *shape, n_cols], columns `cols` indexing into
+        z = [q | qd | tau | theta] (None: all dyn_input_dim(model) + p), from identity directions through
+        dynamics_jvp."""
+        import torch
+
+        n, nall = q.shape[0], dyn_input_dim(self.model) + len(params)
+        cols = torch.arange(nall, device=q.device) if cols is None else torch.as_tensor(cols, device=q.device).long()
+        v = torch.zeros((n, cols.numel(), nall), dtype=torch.float64, device=q.device)
+        v[:, torch.arange(cols.numel(), device=q.device), cols] = 1.0
+        (name,) = _dyn_want(want)
+        t = self.dynamics_jvp(q, qd, tau, v, want=(name,), params=params, theta=theta)[name]
+        return t.movedim(1, -1).contiguous()
 
     # -- the contact query: points, Jacobians, rows, Delassus matrix, impulses, forces -----------------------------
     def contacts(self, x, want=CONTACT_OUTPUTS, out=None):
