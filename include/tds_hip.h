@@ -978,6 +978,54 @@ int tds_hip_inverse_kinematics_host(const tds_model_t *model, int n, const doubl
                                     const tds_ik_options_t *opt, double *q, int32_t *iterations, int32_t *status,
                                     double *residual);
 
+/* Batched iLQR, part 1: the backward pass of n time-varying LQ problems of horizon T (csrc/tds_lqr.hip).  All arrays
+   f64, row-major: A [n][T][nx][nx], B [n][T][nx][nu], lx [n][T+1][nx], lu [n][T][nu], lxx [n][T+1][nx][nx],
+   luu [n][T][nu][nu], lux [n][T][nu][nx] (entry T of lx and lxx: the terminal cost), mu [n] (the regularisation of
+   each problem).  From V_x = lx[T], V_xx = lxx[T], for t = T-1 .. 0:
+       Q_x  = lx + A^T V_x           Q_u  = lu + B^T V_x
+       Q_xx = lxx + A^T V_xx A       Q_ux = lux + B^T V_xx A
+       Q_uu = luu + B^T V_xx B       Q_uu + mu I = L L^T   (Cholesky)
+       k = -(Q_uu + mu I)^-1 Q_u     K = -(Q_uu + mu I)^-1 Q_ux
+       V_x  = Q_x  + K^T Q_uu k + K^T Q_u  + Q_ux^T k
+       V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K,   then V_xx <- (V_xx + V_xx^T) / 2
+       dV1 += k^T Q_u                dV2 += k^T Q_uu k / 2
+   Outputs: k [n][T][nu], K [n][T][nu][nx], dv [n][2] = (dV1, dV2), status [n] (int32).  A problem whose Cholesky meets
+   a pivot that is not positive at step t gets status t + 1, k = K = 0 over the whole horizon and dv = 0; the other
+   problems are not affected; otherwise status 0.  Every element of every product and solve is one sequential sum in
+   index order, the same on the device and in the host checker (the unit is built without FP contraction).
+   1 <= nx <= TDS_LQR_MAX_NX, 1 <= nu <= TDS_LQR_MAX_NU: larger dimensions give TDS_ERR_UNSUPPORTED.  The handle
+   supplies device, stream and error text; its model is not read.  ONE launch on the handle's stream, no host wait. */
+#define TDS_LQR_MAX_NX 40
+#define TDS_LQR_MAX_NU 16
+int tds_hip_lqr_backward(tds_hip_sim_t *sim, int n, int T, int nx, int nu, const void *A_dev, const void *B_dev,
+                         const void *lx_dev, const void *lu_dev, const void *lxx_dev, const void *luu_dev,
+                         const void *lux_dev, const void *mu_dev, void *k_dev, void *K_dev, void *dv_dev,
+                         void *status_dev);
+/* The same statement with plain loops on the CPU (host arrays, needs no GPU): the checker. */
+int tds_hip_lqr_backward_host(int n, int T, int nx, int nu, const double *A, const double *B, const double *lx,
+                              const double *lu, const double *lxx, const double *luu, const double *lux,
+                              const double *mu, double *k, double *K, double *dv, int32_t *status);
+
+/* Batched iLQR, part 2: closed-loop rollout under time-varying affine feedback.  With nsd = dof_q + dof_qd and n_act
+   the action slots of a step's record (input_dim - nsd, less the three gains of a locomotion model): x0
+   [rows][input_dim], s_nom [P][T+1][nsd], u_nom [P][T][n_act], k [P][T][n_act], K [P][T][n_act][nsd], alpha [rows],
+   problem_of_row [rows] (int32, entries in [0, P) -- the caller's promise; NULL: p = row).  s_0 = x0[:nsd], then
+       u_t     = (u_nom[p,t] + alpha k[p,t]) + K[p,t] (s_t - s_nom[p,t])      (the last sum: index order)
+       s_{t+1} = forward_zero([s_t | u_t | the rest of x0's record])[:nsd]
+   Outputs s_out [rows][T+1][nsd], u_out [rows][T][n_act].  Actions are not clamped here (the step's own clamps apply).
+   The step is the handle's forward_zero launch, rows served num_envs at a time; between the steps one small kernel
+   forms u_t, assembles the next records and stores s_t, u_t.  Scope and refusals are those of tds_hip_jacobian (the
+   same messages); a handle with model variants installed is refused.  Any rows >= 1, T >= 1; enqueued on the handle's
+   stream, no host wait except where the work buffer shared with tds_hip_jvp grows. */
+int tds_hip_feedback_rollout(tds_hip_sim_t *sim, int rows, int T, const void *x0_dev, const void *s_nom_dev,
+                             const void *u_nom_dev, const void *k_dev, const void *K_dev, const void *alpha_dev,
+                             const void *problem_of_row_dev, void *s_out_dev, void *u_out_dev);
+/* The same statement over the host step (tds_hip_jacobian_host's y): the checker; num_problems bounds problem_of_row
+   (TDS_ERR_INVALID_ARG outside).  Returns TDS_ERR_INVALID_ARG where some row's inertia was not positive definite. */
+int tds_hip_feedback_rollout_host(const tds_model_t *model, int rows, int T, int num_problems, const double *x0,
+                                  const double *s_nom, const double *u_nom, const double *k, const double *K,
+                                  const double *alpha, const int32_t *problem_of_row, double *s_out, double *u_out);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

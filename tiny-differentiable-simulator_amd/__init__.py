@@ -11,3 +11,4 @@ from . import vec_env  # noqa: F401,E402
 from .vec_env import VectorizedAntEnv, VectorizedLaikagoEnv, VectorizedEnv  # noqa: F401,E402
 from .autograd import step_fn, param_step_fn, rb_rollout_fn, trajectory_fn, policy_trajectory_fn, contact_fn  # noqa: F401,E402
 from .autograd import dynamics_fn, inverse_dynamics_fn  # noqa: F401,E402
+from .ilqr import ilqr, QuadraticCost  # noqa: F401,E402

@@ -186,6 +186,10 @@ def lib():
             [C.c_void_p] * 4
         L.tds_hip_inverse_kinematics.argtypes = [C.c_void_p] + ik_tail
         L.tds_hip_inverse_kinematics_host.argtypes = [P] + ik_tail
+        L.tds_hip_lqr_backward.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 12
+        L.tds_hip_lqr_backward_host.argtypes = [C.c_int] * 4 + [C.c_void_p] * 12
+        L.tds_hip_feedback_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
+        L.tds_hip_feedback_rollout_host.argtypes = [P, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9
         _lib = L
     return _lib
 
@@ -423,6 +427,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_dynamics", "tds_hip_inverse_dynamics", "tds_hip_point_jacobian",
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
+    "tds_hip_lqr_backward", "tds_hip_lqr_backward_host", "tds_hip_feedback_rollout", "tds_hip_feedback_rollout_host",
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_hip_contacts_jvp", "tds_hip_contacts_jvp_host", "tds_hip_contacts_jvp_tangents",
     "tds_hip_dynamics_jvp", "tds_hip_inverse_dynamics_jvp", "tds_hip_dynamics_jvp_host",
@@ -846,6 +851,105 @@ def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points
                                                  C.byref(o), res["q"].ctypes.data, res["iterations"].ctypes.data,
                                                  res["status"].ctypes.data, res["residual"].ctypes.data))
     return res
+
+
+# -- batched iLQR: the Riccati backward pass and the closed-loop rollout (csrc/tds_lqr.hip) -----------------------
+LQR_MAX_NX, LQR_MAX_NU = 40, 16
+
+
+def _lqr_shapes(A, B):
+    """(n, T, nx, nu) from A [n, T, nx, nx] and B [n, T, nx, nu], and the shapes of the other inputs by name"""
+    if len(A.shape) != 4 or len(B.shape) != 4 or A.shape[2] != A.shape[3] or tuple(B.shape[:3]) != tuple(A.shape[:3]):
+        raise ValueError(f"A: expected [n, T, nx, nx] and B [n, T, nx, nu], got {tuple(A.shape)} and {tuple(B.shape)}")
+    n, T, nx, nu = int(A.shape[0]), int(A.shape[1]), int(A.shape[2]), int(B.shape[3])
+    return (n, T, nx, nu), {"lx": (n, T + 1, nx), "lu": (n, T, nu), "lxx": (n, T + 1, nx, nx), "luu": (n, T, nu, nu),
+                            "lux": (n, T, nu, nx), "mu": (n,)}
+
+
+def lqr_backward_host(A, B, lx, lu, lxx, luu, lux, mu):
+    """The backward pass of n time-varying LQ problems on the CPU (tds_hip_lqr_backward_host; the checker of
+    HipSim.lqr_backward, needs no GPU).  A [n, T, nx, nx], B [n, T, nx, nu], lx [n, T + 1, nx], lu [n, T, nu],
+    lxx [n, T + 1, nx, nx], luu [n, T, nu, nu], lux [n, T, nu, nx], mu [n] (or a scalar).  Returns (k [n, T, nu],
+    K [n, T, nu, nx], dv [n, 2], status [n] int32): status t + 1 where the Cholesky of Q_uu + mu I failed at step t
+    (that problem's gains and dv are zero), else 0."""
+    import numpy as np
+
+    A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
+    (n, T, nx, nu), shapes = _lqr_shapes(A, B)
+    arg = {"lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux,
+           "mu": np.broadcast_to(np.asarray(mu, dtype=np.float64), (n,))}
+    for key, shape in shapes.items():
+        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
+        if arg[key].shape != shape:
+            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
+    k, K = np.zeros((n, T, nu)), np.zeros((n, T, nu, nx))
+    dv, status = np.zeros((n, 2)), np.zeros(n, dtype=np.int32)
+    _check(lib().tds_hip_lqr_backward_host(n, T, nx, nu, A.ctypes.data, B.ctypes.data,
+                                           *(arg[key].ctypes.data for key in ("lx", "lu", "lxx", "luu", "lux", "mu")),
+                                           k.ctypes.data, K.ctypes.data, dv.ctypes.data, status.ctypes.data))
+    return k, K, dv, status
+
+
+def _feedback_shapes(m, x0, s_nom):
+    """(rows, P, T) and the shapes of a feedback rollout's inputs by name"""
+    nsd, n_act, _ = trajectory_dims(m, 1)
+    if len(x0.shape) != 2 or x0.shape[1] != m.input_dim:
+        raise ValueError(f"x0: expected [rows, {m.input_dim}], got {list(x0.shape)}")
+    if len(s_nom.shape) != 3 or s_nom.shape[1] < 2 or s_nom.shape[2] != nsd:
+        raise ValueError(f"s_nom: expected [P, T + 1, {nsd}] with T >= 1, got {list(s_nom.shape)}")
+    rows, P, T = int(x0.shape[0]), int(s_nom.shape[0]), int(s_nom.shape[1]) - 1
+    return (rows, P, T, nsd, n_act), {"u_nom": (P, T, n_act), "k": (P, T, n_act), "K": (P, T, n_act, nsd),
+                                      "alpha": (rows,)}
+
+
+def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, problem_of_row=None):
+    """The closed-loop rollout on the CPU over step_host (tds_hip_feedback_rollout_host; the checker of
+    HipSim.feedback_rollout, needs no GPU).  x0 [rows, input_dim], s_nom [P, T + 1, nsd], u_nom and k [P, T, n_act],
+    K [P, T, n_act, nsd], alpha [rows] (or a scalar), problem_of_row [rows] ints in [0, P) or None (row r follows
+    problem r: rows == P).  u_t = (u_nom + alpha k) + K (s_t - s_nom), s_{t+1} = the step of [s_t | u_t | the rest of
+    x0's record].  Returns (s [rows, T + 1, nsd], u [rows, T, n_act])."""
+    import numpy as np
+
+    x0, s_nom = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(s_nom, dtype=np.float64)
+    (rows, P, T, nsd, n_act), shapes = _feedback_shapes(m, x0, s_nom)
+    arg = {"u_nom": u_nom, "k": k, "K": K, "alpha": np.broadcast_to(np.asarray(alpha, dtype=np.float64), (rows,))}
+    for key, shape in shapes.items():
+        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
+        if arg[key].shape != shape:
+            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
+    por = None
+    if problem_of_row is not None:
+        por = np.ascontiguousarray(np.asarray(problem_of_row, dtype=np.int64).reshape(-1).astype(np.int32))
+        if por.shape != (rows,):
+            raise ValueError(f"problem_of_row: expected [{rows}], got {list(por.shape)}")
+    elif rows != P:
+        raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
+    s, u = np.zeros((rows, T + 1, nsd)), np.zeros((rows, T, n_act))
+    _check(lib().tds_hip_feedback_rollout_host(C.byref(m), rows, T, P, x0.ctypes.data, s_nom.ctypes.data,
+                                               *(arg[key].ctypes.data for key in ("u_nom", "k", "K", "alpha")),
+                                               None if por is None else por.ctypes.data, s.ctypes.data, u.ctypes.data))
+    return s, u
+
+
+def trajectory_records(m: _model.Model, x0, s, u):
+    """The [N T, input_dim] records of a trajectory, problem-major (what jacobian / jacobian_host linearise): record
+    (n, t) = [s[n, t] | u[n, t] | the rest of x0[n]].  x0 [N, input_dim], s [N, T + 1, nsd] (or [N, T, nsd]),
+    u [N, T, n_act]; numpy arrays or torch tensors alike."""
+    nsd, n_act, _ = trajectory_dims(m, 1)
+    N, T = int(u.shape[0]), int(u.shape[1])
+    if tuple(x0.shape) != (N, m.input_dim) or tuple(u.shape) != (N, T, n_act) or s.shape[0] != N or \
+            s.shape[1] < T or s.shape[2] != nsd:
+        raise ValueError(f"trajectory_records: x0 {list(x0.shape)}, s {list(s.shape)}, u {list(u.shape)} do not match "
+                         f"[N, {m.input_dim}], [N, T + 1, {nsd}], [N, T, {n_act}]")
+    import numpy as np
+
+    if isinstance(x0, np.ndarray):
+        rest = np.broadcast_to(x0[:, None, nsd + n_act:], (N, T, m.input_dim - nsd - n_act))
+        return np.ascontiguousarray(np.concatenate([s[:, :T], u, rest], axis=2).reshape(N * T, m.input_dim))
+    import torch
+
+    rest = x0[:, None, nsd + n_act:].expand(N, T, m.input_dim - nsd - n_act)
+    return torch.cat([s[:, :T], u, rest], dim=2).reshape(N * T, m.input_dim).contiguous()
 
 
 def step_host(m: _model.Model, x):
@@ -2043,6 +2147,66 @@ class HipSim:
                                                 C.c_void_p(targets.data_ptr()), qrp, C.byref(o), ptr["q"],
                                                 ptr.get("iterations"), ptr.get("status"), ptr.get("residual")))
         return res
+
+    # -- batched iLQR (csrc/tds_lqr.hip) ----------------------------------------------------------------------
+    def lqr_backward(self, A, B, lx, lu, lxx, luu, lux, mu):
+        """The backward pass of n time-varying LQ problems as one launch (tds_hip_lqr_backward; arguments and results
+        as hip_backend.lqr_backward_host, CUDA float64 tensors; mu [n]).  The handle's model is not read.  Async."""
+        import torch
+
+        (n, T, nx, nu), shapes = _lqr_shapes(A, B)
+        arg = {"A": A, "B": B, "lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux, "mu": mu}
+        shapes.update({"A": (n, T, nx, nx), "B": (n, T, nx, nu)})
+        for key, shape in shapes.items():
+            t = arg[key]
+            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
+                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
+            arg[key] = t.contiguous()
+        dev = A.device
+        k = torch.empty((n, T, nu), dtype=torch.float64, device=dev)
+        K = torch.empty((n, T, nu, nx), dtype=torch.float64, device=dev)
+        dv = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        _check(lib().tds_hip_lqr_backward(self.h, n, T, nx, nu,
+                                          *(C.c_void_p(arg[key].data_ptr())
+                                            for key in ("A", "B", "lx", "lu", "lxx", "luu", "lux", "mu")),
+                                          C.c_void_p(k.data_ptr()), C.c_void_p(K.data_ptr()), C.c_void_p(dv.data_ptr()),
+                                          C.c_void_p(status.data_ptr())))
+        return k, K, dv, status
+
+    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, problem_of_row=None, check: bool = True):
+        """The closed-loop rollout under u_t = (u_nom + alpha k) + K (s_t - s_nom) (tds_hip_feedback_rollout; arguments
+        and results as hip_backend.feedback_rollout_host, CUDA float64 tensors; alpha [rows]; problem_of_row a CUDA
+        int32 tensor [rows] with entries in [0, P), or None).  Any number of rows.  check: the entries of problem_of_row
+        are verified before the launch (the one host wait of the call); a caller that built the map itself passes
+        False and the call is asynchronous."""
+        import torch
+
+        (rows, P, T, nsd, n_act), shapes = _feedback_shapes(self.model, x0, s_nom)
+        arg = {"x0": x0, "s_nom": s_nom, "u_nom": u_nom, "k": k, "K": K, "alpha": alpha}
+        shapes.update({"x0": (rows, self.input_dim), "s_nom": (P, T + 1, nsd)})
+        for key, shape in shapes.items():
+            t = arg[key]
+            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
+                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
+            arg[key] = t.contiguous()
+        if problem_of_row is not None:
+            if not (problem_of_row.is_cuda and problem_of_row.dtype == torch.int32) or \
+                    tuple(problem_of_row.shape) != (rows,):
+                raise ValueError(f"problem_of_row: expected a CUDA int32 tensor [{rows}]")
+            problem_of_row = problem_of_row.contiguous()
+            if check and not (0 <= int(problem_of_row.min()) and int(problem_of_row.max()) < P):
+                raise ValueError(f"problem_of_row: entries outside [0, {P})")
+        elif rows != P:
+            raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
+        s = torch.empty((rows, T + 1, nsd), dtype=torch.float64, device=x0.device)
+        u = torch.empty((rows, T, n_act), dtype=torch.float64, device=x0.device)
+        _check(lib().tds_hip_feedback_rollout(self.h, rows, T,
+                                              *(C.c_void_p(arg[key].data_ptr())
+                                                for key in ("x0", "s_nom", "u_nom", "k", "K", "alpha")),
+                                              C.c_void_p(problem_of_row.data_ptr()) if problem_of_row is not None
+                                              else None, C.c_void_p(s.data_ptr()), C.c_void_p(u.data_ptr())))
+        return s, u
 
     def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
         """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
