@@ -1,6 +1,7 @@
 // tds_query.h — what the one-lane-per-environment query units share (tds_dyn.hip: dynamics queries, tds_ik.hip:
-// inverse kinematics, tds_contact.hip: the contact query, tds_contact_jvp.hip: its derivatives): the mapping, the
-// record transfers of their kernels, the launch plan and the host checkers' stride-1 state.
+// inverse kinematics, tds_contact.hip: the contact query): the mapping, the record transfers of their kernels, the
+// launch plan and the host checkers' stride-1 state.  The derivatives of the queries (tds_dyn_jvp.hip,
+// tds_contact_jvp.hip) use the transfers and the width rule through their own driver, tds_query_dual.h.
 //
 // MAPPING.  One lane per environment, workgroups of W <= 64 lanes (one wavefront, narrowed so that a small batch still
 // reaches every compute unit: tds_query_width), at most kQueryLanes lanes per launch and the grid's stride beyond.  An

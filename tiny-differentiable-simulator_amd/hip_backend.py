@@ -8,6 +8,7 @@ CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 from . import model as _model
@@ -631,48 +632,201 @@ def _dev_outputs(shapes, want, out, device, struct=None, dtypes={}):
     return res, struct and struct(**{k: (t if t.numel() else nothing).data_ptr() for k, t in res.items()})
 
 
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _dev_theta_rows(theta, n, p):
+    import torch
+
+    assert theta.is_cuda and theta.dtype == torch.float64
+    if theta.dim() == 1:
+        theta = theta.unsqueeze(0).expand(n, p)
+    assert tuple(theta.shape) == (n, p), (tuple(theta.shape), n, p)
+    return theta.contiguous()
+
+
+class _HostArrays:
+    """How a query marshals its arguments and results over numpy arrays (the *_host functions); _DevArrays: the same
+    over CUDA tensors (HipSim's methods).  A query written on either is written once (_dynamics_jvp ...)."""
+
+    ptr = staticmethod(_np_ptr)
+
+    @staticmethod
+    def records(a, width, what):
+        import numpy as np
+
+        return np.ascontiguousarray(a, dtype=np.float64).reshape(-1, width)
+
+    @staticmethod
+    def rows(a, n, width, what):
+        return _host_rows(a, n, width)
+
+    @staticmethod
+    def directions(v, n, width, width_text=None):
+        import numpy as np
+
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.ndim != 3 or v.shape[0] != n or v.shape[2] != width or v.shape[1] < 1:
+            raise ValueError(f"v: expected [{n}, k >= 1, {width}], got {tuple(v.shape)}")
+        return v
+
+    @staticmethod
+    def theta(theta, n, p):
+        th = None if theta is None else _theta_rows(theta, n, p)
+        return th, None if p == 0 else _np_ptr(th)
+
+    @staticmethod
+    def outputs(shapes, want, out, like, struct=None):
+        return _host_outputs(shapes, want, out, struct)
+
+
+class _DevArrays:
+    records = staticmethod(_dev_records)
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def rows(a, n, width, what):
+        a = None if a is None or width == 0 else _dev_records(a, width, what, n)
+        return a, _DevArrays.ptr(a)
+
+    @staticmethod
+    def directions(v, n, width, width_text=None):
+        import torch
+
+        assert v.is_cuda and v.dtype == torch.float64 and v.dim() == 3 and v.shape[1] >= 1 and \
+            tuple(v.shape[::2]) == (n, width), f"v: expected [N, k >= 1, {width_text or width}]"
+        return v.contiguous()
+
+    @staticmethod
+    def theta(theta, n, p):
+        th = None if theta is None or p == 0 else _dev_theta_rows(theta, n, p)
+        return th, _DevArrays.ptr(th)
+
+    @staticmethod
+    def outputs(shapes, want, out, like, struct=None):
+        return _dev_outputs(shapes, want, out, like.device, struct)
+
+
+def _dynamics(A, call, m, q, qd, tau, want, out):
+    want = _dyn_want(want)
+    q = A.records(q, m.dof_q, "q")
+    n = q.shape[0]
+    qd, qdp = A.rows(qd, n, m.dof_qd, "qd")
+    tau, taup = A.rows(tau, n, dyn_tau_dim(m), "tau")
+    res, o = A.outputs(dyn_shapes(m, n), want, out, q, DynOut)
+    _check(call(n, A.ptr(q), qdp, taup, C.byref(o)))
+    return res
+
+
+def _inverse_dynamics(A, call, m, q, qd, qdd):
+    q = A.records(q, m.dof_q, "q")
+    n = q.shape[0]
+    qd, qdp = A.rows(qd, n, m.dof_qd, "qd")
+    qdd, qddp = A.rows(qdd, n, m.dof_qd, "qdd")
+    res, _ = A.outputs({"tau": (n, m.dof_qd)}, ("tau",), None, q)
+    _check(call(n, A.ptr(q), qdp, qddp, A.ptr(res["tau"])))
+    return res["tau"]
+
+
+def _point_jacobian(A, call, m, q, link, point, local):
+    q = A.records(q, m.dof_q, "q")
+    n = q.shape[0]
+    point, ptp = A.rows(point, n, 3, "point")
+    res, _ = A.outputs({"jac": (n, 3, m.dof_qd)}, ("jac",), None, q)
+    _check(call(n, A.ptr(q), int(link), ptp, int(bool(local)), A.ptr(res["jac"])))
+    return res["jac"]
+
+
+def _query_jvp(A, call, like, width, params, theta, v, want_primal, want, shapes, struct, out=None, out_primal=None,
+               width_text=None):
+    """What the derivative calls of the queries share behind their records (`like`: the first of them).  call(p,
+    selection, theta, k, v, primal, tangents) is the library's entry point with the records bound; width: the columns of
+    v before theta; shapes: the primal outputs', the tangents' are [n, k, ...] of them; struct: the ctypes class of the
+    output pointers (None: the one output is passed and returned bare).  A dict handed in is checked even where it is
+    not written."""
+    n, p = like.shape[0], len(params)
+    sel = param_spec(params)
+    th, thp = A.theta(theta, n, p)
+
+    def made(shapes, wanted, given):  # (the outputs, their C argument)
+        res, s = A.outputs(shapes, want if wanted or given is not None else (), given, like, struct)
+        if struct is not None:
+            return res, C.byref(s)
+        one = next(iter(res.values()), None)
+        return one, A.ptr(one)
+
+    primal, po = made(shapes, want_primal or v is None, out_primal)
+    if v is None:
+        _check(call(p, sel, thp, 0, None, po, None))
+        return primal
+    v = A.directions(v, n, width + p, width_text)
+    k = v.shape[1]
+    tan, to = made({name: (n, k) + s[1:] for name, s in shapes.items()}, True, out)
+    _check(call(p, sel, thp, k, A.ptr(v), po if want_primal else None, to))
+    return (tan, primal) if want_primal else tan
+
+
+def _dynamics_jvp(A, fn, m, q, qd, tau, v, want, params, theta, want_primal, out, out_primal):
+    want = _dyn_want(want)
+    q = A.records(q, m.dof_q, "q")
+    n = q.shape[0]
+    qd, qdp = A.rows(qd, n, m.dof_qd, "qd")
+    tau, taup = A.rows(tau, n, dyn_tau_dim(m), "tau")
+    return _query_jvp(A, functools.partial(fn, n, A.ptr(q), qdp, taup), q, dyn_input_dim(m), params, theta, v,
+                      want_primal, want, dyn_shapes(m, n), DynOut, out, out_primal)
+
+
+def _inverse_dynamics_jvp(A, fn, m, q, qd, qdd, v, params, theta, want_primal):
+    q = A.records(q, m.dof_q, "q")
+    n, nd = q.shape[0], m.dof_qd
+    qd, qdp = A.rows(qd, n, nd, "qd")
+    qdd, qddp = A.rows(qdd, n, nd, "qdd")
+    return _query_jvp(A, functools.partial(fn, n, A.ptr(q), qdp, qddp), q, dyn_input_dim(m, True), params, theta, v,
+                      want_primal, ("tau",), {"tau": (n, nd)}, None)
+
+
+def _contacts_jvp(A, fn, m, x, v, want, params, theta, want_primal, out, out_primal):
+    want = _contact_want(want)
+    x = A.records(x, m.input_dim, "x")
+    n = x.shape[0]
+    return _query_jvp(A, functools.partial(fn, n, A.ptr(x)), x, m.input_dim, params, theta, v, want_primal, want,
+                      contact_shapes(m, n), ContactOut, out, out_primal, "input_dim + p")
+
+
+def _identity_directions(n, nall, cols, device):
+    """v [n, n_cols, nall]: direction j is the unit vector of column cols[j] (None: every column)"""
+    import torch
+
+    cols = torch.arange(nall, device=device) if cols is None else torch.as_tensor(cols, device=device).long()
+    v = torch.zeros((n, cols.numel(), nall), dtype=torch.float64, device=device)
+    v[:, torch.arange(cols.numel(), device=device), cols] = 1.0
+    return v
+
+
 def dynamics_host(m: _model.Model, q, qd=None, tau=None, want=DYN_OUTPUTS):
     """The dynamics queries on the CPU (tds_hip_dynamics_host; the checker of HipSim.dynamics, needs no GPU).
 
     q [N, dof_q], qd [N, dof_qd] (None: zero), tau [N, dyn_tau_dim(m)] (None: zero), float64.  Returns a dict of the
     wanted outputs: x_world [N, num_links, 12], mass_matrix [N, dof_qd, dof_qd], bias [N, dof_qd], qdd [N, dof_qd]."""
-    import numpy as np
-
-    want = _dyn_want(want)
-    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
-    n = q.shape[0]
-    qd, qdp = _host_rows(qd, n, m.dof_qd)
-    tau, taup = _host_rows(tau, n, dyn_tau_dim(m))
-    res, out = _host_outputs(dyn_shapes(m, n), want, struct=DynOut)
-    _check(lib().tds_hip_dynamics_host(C.byref(m), n, q.ctypes.data, qdp, taup, C.byref(out)))
-    return res
+    call = functools.partial(lib().tds_hip_dynamics_host, C.byref(m))
+    return _dynamics(_HostArrays, call, m, q, qd, tau, want, None)
 
 
 def inverse_dynamics_host(m: _model.Model, q, qd=None, qdd=None):
     """tau [N, dof_qd] = ID(q, qd, qdd) on the CPU (tds_hip_inverse_dynamics_host; None: zero); fixed base only"""
-    import numpy as np
-
-    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
-    n = q.shape[0]
-    qd, qdp = _host_rows(qd, n, m.dof_qd)
-    qdd, qddp = _host_rows(qdd, n, m.dof_qd)
-    tau = np.zeros((n, m.dof_qd), dtype=np.float64)
-    _check(lib().tds_hip_inverse_dynamics_host(C.byref(m), n, q.ctypes.data, qdp, qddp, tau.ctypes.data))
-    return tau
+    call = functools.partial(lib().tds_hip_inverse_dynamics_host, C.byref(m))
+    return _inverse_dynamics(_HostArrays, call, m, q, qd, qdd)
 
 
 def point_jacobian_host(m: _model.Model, q, link: int, point, local: bool = False):
     """The world-frame Jacobian [N, 3, dof_qd] of a point [N, 3] (or [3]) on link `link` (-1: the base) on the CPU
     (tds_hip_point_jacobian_host); local: the point is given in the link's own frame"""
-    import numpy as np
-
-    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
-    n = q.shape[0]
-    pt, ptp = _host_rows(point, n, 3)
-    jac = np.zeros((n, 3, m.dof_qd), dtype=np.float64)
-    _check(lib().tds_hip_point_jacobian_host(C.byref(m), n, q.ctypes.data, int(link), ptp, int(bool(local)),
-                                             jac.ctypes.data))
-    return jac
+    call = functools.partial(lib().tds_hip_point_jacobian_host, C.byref(m))
+    return _point_jacobian(_HostArrays, call, m, q, link, point, local)
 
 
 def contacts_host(m: _model.Model, x, want=CONTACT_OUTPUTS, out=None):
@@ -715,26 +869,8 @@ def contacts_jvp_host(m: _model.Model, x, v, want=CONTACT_OUTPUTS, params=(), th
     themselves at theta as well.  v None: the primal dict alone (k = 0).  An environment whose M is not positive
     definite has NaN in rows .. qd_post and their tangents; the call then raises after writing (pass out / out_primal,
     dicts of arrays to write the tangents / the primal into, to see what it wrote)."""
-    import numpy as np
-
-    want = _contact_want(want)
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x.shape[0], len(params)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    thp = None if th is None or p == 0 else th.ctypes.data
-    primal, po = _host_outputs(contact_shapes(m, n), want, out_primal, struct=ContactOut)
-    if v is None:
-        _check(lib().tds_hip_contacts_jvp_host(C.byref(m), n, x.ctypes.data, p, sel, thp, 0, None, C.byref(po), None))
-        return primal
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    if v.ndim != 3 or v.shape[0] != n or v.shape[2] != m.input_dim + p or v.shape[1] < 1:
-        raise ValueError(f"v: expected [{n}, k >= 1, {m.input_dim + p}], got {tuple(v.shape)}")
-    k = v.shape[1]
-    tan, to = _host_outputs(contact_tangent_shapes(m, n, k), want, out, struct=ContactOut)
-    _check(lib().tds_hip_contacts_jvp_host(C.byref(m), n, x.ctypes.data, p, sel, thp, k, v.ctypes.data,
-                                           C.byref(po) if want_primal else None, C.byref(to)))
-    return (tan, primal) if want_primal else tan
+    call = functools.partial(lib().tds_hip_contacts_jvp_host, C.byref(m))
+    return _contacts_jvp(_HostArrays, call, m, x, v, want, params, theta, want_primal, out, out_primal)
 
 
 def dynamics_jvp_tangents(m: _model.Model) -> int:
@@ -756,15 +892,6 @@ def dyn_input_dim(m: _model.Model, inverse: bool = False) -> int:
     return m.dof_q + m.dof_qd + (m.dof_qd if inverse else dyn_tau_dim(m))
 
 
-def _host_directions(v, n, width):
-    import numpy as np
-
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    if v.ndim != 3 or v.shape[0] != n or v.shape[2] != width or v.shape[1] < 1:
-        raise ValueError(f"v: expected [{n}, k >= 1, {width}], got {tuple(v.shape)}")
-    return v
-
-
 def dynamics_jvp_host(m: _model.Model, q, qd=None, tau=None, v=None, want=DYN_OUTPUTS, params=(), theta=None,
                       want_primal: bool = False, out=None, out_primal=None):
     """Forward-mode derivatives of the dynamics queries in z = [q | qd | tau | theta] on the CPU
@@ -776,27 +903,8 @@ def dynamics_jvp_host(m: _model.Model, q, qd=None, tau=None, v=None, want=DYN_OU
     (tangents, primal): the outputs themselves at theta as well.  v None: the primal dict alone (k = 0).  An environment
     whose M is not positive definite has NaN in qdd and its tangents; the call then raises after writing (pass out /
     out_primal, dicts of arrays to write the tangents / the primal into, to see what it wrote)."""
-    import numpy as np
-
-    want = _dyn_want(want)
-    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
-    n, p = q.shape[0], len(params)
-    qd, qdp = _host_rows(qd, n, m.dof_qd)
-    tau, taup = _host_rows(tau, n, dyn_tau_dim(m))
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    thp = None if th is None or p == 0 else th.ctypes.data
-    primal, po = _host_outputs(dyn_shapes(m, n), want, out_primal, struct=DynOut)
-    if v is None:
-        _check(lib().tds_hip_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, taup, p, sel, thp, 0, None,
-                                               C.byref(po), None))
-        return primal
-    v = _host_directions(v, n, dyn_input_dim(m) + p)
-    k = v.shape[1]
-    tan, to = _host_outputs(dyn_tangent_shapes(m, n, k), want, out, struct=DynOut)
-    _check(lib().tds_hip_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, taup, p, sel, thp, k, v.ctypes.data,
-                                           C.byref(po) if want_primal else None, C.byref(to)))
-    return (tan, primal) if want_primal else tan
+    call = functools.partial(lib().tds_hip_dynamics_jvp_host, C.byref(m))
+    return _dynamics_jvp(_HostArrays, call, m, q, qd, tau, v, want, params, theta, want_primal, out, out_primal)
 
 
 def inverse_dynamics_jvp_host(m: _model.Model, q, qd=None, qdd=None, v=None, params=(), theta=None,
@@ -805,26 +913,8 @@ def inverse_dynamics_jvp_host(m: _model.Model, q, qd=None, qdd=None, v=None, par
     (tds_hip_inverse_dynamics_jvp_host; the checker of HipSim.inverse_dynamics_jvp): dtau [N, k, dof_qd] for
     directions v [N, k, dof_q + 2 dof_qd + p], with want_primal (dtau, tau); v None: tau [N, dof_qd] at theta alone.
     Arguments as for dynamics_jvp_host; fixed base only."""
-    import numpy as np
-
-    q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, m.dof_q)
-    n, p, nd = q.shape[0], len(params), m.dof_qd
-    qd, qdp = _host_rows(qd, n, nd)
-    qdd, qddp = _host_rows(qdd, n, nd)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    thp = None if th is None or p == 0 else th.ctypes.data
-    tau = np.zeros((n, nd), dtype=np.float64)
-    if v is None:
-        _check(lib().tds_hip_inverse_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, qddp, p, sel, thp, 0, None,
-                                                       tau.ctypes.data, None))
-        return tau
-    v = _host_directions(v, n, dyn_input_dim(m, True) + p)
-    dtau = np.zeros((n, v.shape[1], nd), dtype=np.float64)
-    _check(lib().tds_hip_inverse_dynamics_jvp_host(C.byref(m), n, q.ctypes.data, qdp, qddp, p, sel, thp, v.shape[1],
-                                                   v.ctypes.data, tau.ctypes.data if want_primal else None,
-                                                   dtau.ctypes.data))
-    return (dtau, tau) if want_primal else dtau
+    call = functools.partial(lib().tds_hip_inverse_dynamics_jvp_host, C.byref(m))
+    return _inverse_dynamics_jvp(_HostArrays, call, m, q, qd, qdd, v, params, theta, want_primal)
 
 
 def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points=None, q_reference=None,
@@ -1233,10 +1323,6 @@ def policy_network_spec(m: _model.Model, layer_sizes=None, activations=None, use
     nw = int(sum(int(ls[i - 1]) * int(ls[i]) for i in range(1, nl)))
     nb = int(sum(int(ls[i]) for i in range(nl) if ub[i]))
     return nl, ls, act, ub, nw + nb
-
-
-def _np_ptr(a):
-    return None if a is None else a.ctypes.data
 
 
 def policy_trajectory_vjp_host(m: _model.Model, x0, policy, gs, steps: int, every: int = 1, ga=None, layer_sizes=None,
@@ -1730,15 +1816,6 @@ class HipSim:
         return y, (wj[:, 0] if squeeze else wj)
 
     # -- parameter derivatives: [x | theta], theta the selected model scalars per environment ---------------------
-    def _theta(self, theta, n, p):
-        import torch
-
-        assert theta.is_cuda and theta.dtype == torch.float64
-        if theta.dim() == 1:
-            theta = theta.unsqueeze(0).expand(n, p)
-        assert tuple(theta.shape) == (n, p), (tuple(theta.shape), n, p)
-        return theta.contiguous()
-
     def jvp_params(self, x, theta, params, v=None):
         """y = f(x; theta) [N, output_dim] (v None), else (y, jv): jv = J v [N, K, output_dim] for directions v
         [N, K, input_dim + p] over [x | theta] (or [N, input_dim + p]: K = 1, jv [N, output_dim]).  theta [p] (every
@@ -1750,7 +1827,7 @@ class HipSim:
         x = x.contiguous()
         n, p = x.shape[0], len(params)
         sel = param_spec(params)
-        th = self._theta(theta, n, p)
+        th = _dev_theta_rows(theta, n, p)
         y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
         if v is None:
             _check(lib().tds_hip_jvp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), 0,
@@ -1779,7 +1856,7 @@ class HipSim:
         x = x.contiguous()
         n, k, p = x.shape[0], w3.shape[1], len(params)
         sel = param_spec(params)
-        th = self._theta(theta, n, p)
+        th = _dev_theta_rows(theta, n, p)
         y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
         wj = torch.empty((n, k, self.input_dim + p), dtype=torch.float64, device=x.device)
         _check(lib().tds_hip_vjp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), k,
@@ -1803,7 +1880,7 @@ class HipSim:
         n, p = x0.shape[0], len(params)
         nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
         sel = param_spec(params)
-        th = None if theta is None else self._theta(theta, n, p)
+        th = None if theta is None else _dev_theta_rows(theta, n, p)
         thp = None if th is None else C.c_void_p(th.data_ptr())
         up = None
         if u is not None:
@@ -1842,7 +1919,7 @@ class HipSim:
         n, p = x0.shape[0], len(params)
         nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
         sel = param_spec(params)
-        th = None if theta is None else self._theta(theta, n, p)
+        th = None if theta is None else _dev_theta_rows(theta, n, p)
         up = None
         if u is not None:
             assert u.is_cuda and u.dtype == torch.float64
@@ -1890,7 +1967,7 @@ class HipSim:
         assert tuple(policy.shape) == (n, P), (tuple(policy.shape), n, P)
         policy = policy.contiguous()
         sel = param_spec(params)
-        th = None if theta is None else self._theta(theta, n, p)
+        th = None if theta is None else _dev_theta_rows(theta, n, p)
         T = max(int(steps), 0)
         dev = x0.device
         if gs is not None:
@@ -1923,25 +2000,13 @@ class HipSim:
                                           params, theta, first_obs_raw, obs_raw)[:2]
 
     # -- dynamics queries: kinematics, mass matrix, bias, forward and inverse dynamics, point Jacobians -----------
-    def _dyn_rows(self, a, n, width, what):
-        if a is None or width == 0:
-            return None, None
-        a = _dev_records(a, width, what, n)
-        return a, C.c_void_p(a.data_ptr())
-
     def dynamics(self, q, qd=None, tau=None, want=DYN_OUTPUTS, out=None):
         """The wanted ones of x_world [N, num_links, 12], mass_matrix [N, dof_qd, dof_qd], bias [N, dof_qd] and
         qdd [N, dof_qd] at the states q [N, dof_q], qd [N, dof_qd] (None: zero), as a dict of tensors on the handle's
         device.  tau [N, dyn_tau_dim(model)] (None: zero) are the torques of qdd, the unconstrained forward dynamics.
         out: a dict of tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
-        want = _dyn_want(want)
-        q = _dev_records(q, self.model.dof_q, "q")
-        n = q.shape[0]
-        qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
-        tau, taup = self._dyn_rows(tau, n, dyn_tau_dim(self.model), "tau")
-        res, o = _dev_outputs(dyn_shapes(self.model, n), want, out, q.device, struct=DynOut)
-        _check(lib().tds_hip_dynamics(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, C.byref(o)))
-        return res
+        call = functools.partial(lib().tds_hip_dynamics, self.h)
+        return _dynamics(_DevArrays, call, self.model, q, qd, tau, want, out)
 
     def forward_kinematics(self, q):
         """x_world [N, num_links, 12]: rotation (9, row-major) and translation (3) of every link"""
@@ -1957,37 +2022,16 @@ class HipSim:
 
     def inverse_dynamics(self, q, qd=None, qdd=None):
         """tau [N, dof_qd] = ID(q, qd, qdd) (None: zero), without springs or dampers; fixed base only (async)"""
-        import torch
-
-        q = _dev_records(q, self.model.dof_q, "q")
-        n = q.shape[0]
-        qd, qdp = self._dyn_rows(qd, n, self.model.dof_qd, "qd")
-        qdd, qddp = self._dyn_rows(qdd, n, self.model.dof_qd, "qdd")
-        tau = torch.empty((n, self.model.dof_qd), dtype=torch.float64, device=q.device)
-        _check(lib().tds_hip_inverse_dynamics(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, C.c_void_p(tau.data_ptr())))
-        return tau
+        call = functools.partial(lib().tds_hip_inverse_dynamics, self.h)
+        return _inverse_dynamics(_DevArrays, call, self.model, q, qd, qdd)
 
     def point_jacobian(self, q, link: int, point, local: bool = False):
         """The world-frame Jacobian [N, 3, dof_qd] of the points [N, 3] on link `link` (-1: the base); local: the points
         are given in the link's own frame (async)"""
-        import torch
-
-        q = _dev_records(q, self.model.dof_q, "q")
-        n = q.shape[0]
-        point, ptp = self._dyn_rows(point, n, 3, "point")
-        jac = torch.empty((n, 3, self.model.dof_qd), dtype=torch.float64, device=q.device)
-        _check(lib().tds_hip_point_jacobian(self.h, n, C.c_void_p(q.data_ptr()), int(link), ptp, int(bool(local)),
-                                            C.c_void_p(jac.data_ptr())))
-        return jac
+        call = functools.partial(lib().tds_hip_point_jacobian, self.h)
+        return _point_jacobian(_DevArrays, call, self.model, q, link, point, local)
 
     # -- forward-mode derivatives of the dynamics queries in [q | qd | tau or qdd | theta] -------------------------
-    def _dyn_directions(self, v, n, width):
-        import torch
-
-        assert v.is_cuda and v.dtype == torch.float64 and v.dim() == 3 and v.shape[1] >= 1 and \
-            tuple(v.shape[::2]) == (n, width), f"v: expected [N, k >= 1, {width}]"
-        return v.contiguous(), v.shape[1]
-
     def dynamics_jvp(self, q, qd=None, tau=None, v=None, want=DYN_OUTPUTS, params=(), theta=None, out=None,
                      want_primal: bool = False):
         """Forward-mode derivatives of the dynamics queries in z = [q | qd | tau | theta] (tds_hip_dynamics_jvp): for
@@ -1997,67 +2041,25 @@ class HipSim:
         columns of v still count).  theta [p] or [N, p]: the selection's values (None: the model's).  v None: the
         primal dict at theta alone.  out: a dict of tangent tensors to write into.  Any N; f64 handles only; one launch
         over (environment, block of dynamics_jvp_tangents(model) directions) items (async)."""
-        want = _dyn_want(want)
-        m = self.model
-        q = _dev_records(q, m.dof_q, "q")
-        n, p = q.shape[0], len(params)
-        qd, qdp = self._dyn_rows(qd, n, m.dof_qd, "qd")
-        tau, taup = self._dyn_rows(tau, n, dyn_tau_dim(m), "tau")
-        sel = param_spec(params)
-        th = None if theta is None or p == 0 else self._theta(theta, n, p)
-        thp = None if th is None else C.c_void_p(th.data_ptr())
-        primal, po = _dev_outputs(dyn_shapes(m, n), want if (want_primal or v is None) else (), None, q.device,
-                                  struct=DynOut)
-        if v is None:
-            _check(lib().tds_hip_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, p, sel, thp, 0, None,
-                                              C.byref(po), None))
-            return primal
-        v, k = self._dyn_directions(v, n, dyn_input_dim(m) + p)
-        tan, to = _dev_outputs(dyn_tangent_shapes(m, n, k), want, out, q.device, struct=DynOut)
-        _check(lib().tds_hip_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, taup, p, sel, thp, k,
-                                          C.c_void_p(v.data_ptr()), C.byref(po), C.byref(to)))
-        return (tan, primal) if want_primal else tan
+        call = functools.partial(lib().tds_hip_dynamics_jvp, self.h)
+        return _dynamics_jvp(_DevArrays, call, self.model, q, qd, tau, v, want, params, theta, want_primal, out, None)
 
     def inverse_dynamics_jvp(self, q, qd=None, qdd=None, v=None, params=(), theta=None, want_primal: bool = False):
         """Forward-mode derivatives of tau = ID(q, qd, qdd) in z = [q | qd | qdd | theta]
         (tds_hip_inverse_dynamics_jvp): dtau [N, k, dof_qd] for directions v [N, k, dof_q + 2 dof_qd + p], with
         want_primal (dtau, tau); v None: tau [N, dof_qd] at theta alone.  Arguments as for dynamics_jvp; fixed base
         only (async)."""
-        import torch
-
-        m = self.model
-        q = _dev_records(q, m.dof_q, "q")
-        n, p, nd = q.shape[0], len(params), m.dof_qd
-        qd, qdp = self._dyn_rows(qd, n, nd, "qd")
-        qdd, qddp = self._dyn_rows(qdd, n, nd, "qdd")
-        sel = param_spec(params)
-        th = None if theta is None or p == 0 else self._theta(theta, n, p)
-        thp = None if th is None else C.c_void_p(th.data_ptr())
-        tau = torch.empty((n, nd), dtype=torch.float64, device=q.device) if (want_primal or v is None) else None
-        taup = None if tau is None else C.c_void_p(tau.data_ptr())
-        if v is None:
-            _check(lib().tds_hip_inverse_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, p, sel, thp, 0,
-                                                      None, taup, None))
-            return tau
-        v, k = self._dyn_directions(v, n, dyn_input_dim(m, True) + p)
-        dtau = torch.empty((n, k, nd), dtype=torch.float64, device=q.device)
-        _check(lib().tds_hip_inverse_dynamics_jvp(self.h, n, C.c_void_p(q.data_ptr()), qdp, qddp, p, sel, thp, k,
-                                                  C.c_void_p(v.data_ptr()), taup, C.c_void_p(dtau.data_ptr())))
-        return (dtau, tau) if want_primal else dtau
+        call = functools.partial(lib().tds_hip_inverse_dynamics_jvp, self.h)
+        return _inverse_dynamics_jvp(_DevArrays, call, self.model, q, qd, qdd, v, params, theta, want_primal)
 
     def dynamics_jacobian(self, q, qd=None, tau=None, want="qdd", cols=None, params=(), theta=None):
         """The dense derivative of one dynamics output: [N, *shape, n_cols], columns `cols` indexing into
         z = [q | qd | tau | theta] (None: all dyn_input_dim(model) + p), from identity directions through
         dynamics_jvp."""
-        import torch
-
-        n, nall = q.shape[0], dyn_input_dim(self.model) + len(params)
-        cols = torch.arange(nall, device=q.device) if cols is None else torch.as_tensor(cols, device=q.device).long()
-        v = torch.zeros((n, cols.numel(), nall), dtype=torch.float64, device=q.device)
-        v[:, torch.arange(cols.numel(), device=q.device), cols] = 1.0
+        nall = dyn_input_dim(self.model) + len(params)
         (name,) = _dyn_want(want)
-        t = self.dynamics_jvp(q, qd, tau, v, want=(name,), params=params, theta=theta)[name]
-        return t.movedim(1, -1).contiguous()
+        v = _identity_directions(q.shape[0], nall, cols, q.device)
+        return self.dynamics_jvp(q, qd, tau, v, want=(name,), params=params, theta=theta)[name].movedim(1, -1).contiguous()
 
     # -- the contact query: points, Jacobians, rows, Delassus matrix, impulses, forces -----------------------------
     def contacts(self, x, want=CONTACT_OUTPUTS, out=None):
@@ -2080,40 +2082,16 @@ class HipSim:
         The derivative of the algorithm as executed (contact activation, PGS projections and the actuation clamps
         follow the primal's branch; a separated point has zero tangents).  Any N; f64 handles only; one launch over
         (environment, block of contacts_jvp_tangents(model) directions) items (async)."""
-        want = _contact_want(want)
-        x = _dev_records(x, self.input_dim, "x")
-        n, p = x.shape[0], len(params)
-        sel = param_spec(params)
-        th = None if theta is None or p == 0 else self._theta(theta, n, p)
-        thp = None if th is None else C.c_void_p(th.data_ptr())
-        primal, po = _dev_outputs(contact_shapes(self.model, n), want if (want_primal or v is None) else (), None,
-                                  x.device, struct=ContactOut)
-        if v is None:
-            _check(lib().tds_hip_contacts_jvp(self.h, n, C.c_void_p(x.data_ptr()), p, sel, thp, 0, None, C.byref(po),
-                                              None))
-            return primal
-        import torch
-
-        assert v.is_cuda and v.dtype == torch.float64 and v.dim() == 3 and v.shape[1] >= 1 and \
-            tuple(v.shape[::2]) == (n, self.input_dim + p), "v: expected [N, k >= 1, input_dim + p]"
-        v, k = v.contiguous(), v.shape[1]
-        tan, to = _dev_outputs(contact_tangent_shapes(self.model, n, k), want, out, x.device, struct=ContactOut)
-        _check(lib().tds_hip_contacts_jvp(self.h, n, C.c_void_p(x.data_ptr()), p, sel, thp, k, C.c_void_p(v.data_ptr()),
-                                          C.byref(po), C.byref(to)))
-        return (tan, primal) if want_primal else tan
+        call = functools.partial(lib().tds_hip_contacts_jvp, self.h)
+        return _contacts_jvp(_DevArrays, call, self.model, x, v, want, params, theta, want_primal, out, None)
 
     def contacts_jacobian(self, x, want, cols=None, params=(), theta=None):
         """The dense derivative of one contact output: [N, *shape, n_cols], columns `cols` indexing into [x | theta]
         (None: all input_dim + p), from identity directions through contacts_jvp."""
-        import torch
-
-        n, nall = x.shape[0], self.input_dim + len(params)
-        cols = torch.arange(nall, device=x.device) if cols is None else torch.as_tensor(cols, device=x.device).long()
-        v = torch.zeros((n, cols.numel(), nall), dtype=torch.float64, device=x.device)
-        v[:, torch.arange(cols.numel(), device=x.device), cols] = 1.0
+        nall = self.input_dim + len(params)
         (name,) = _contact_want(want)
-        t = self.contacts_jvp(x, v, want=(name,), params=params, theta=theta)[name]
-        return t.movedim(1, -1).contiguous()
+        v = _identity_directions(x.shape[0], nall, cols, x.device)
+        return self.contacts_jvp(x, v, want=(name,), params=params, theta=theta)[name].movedim(1, -1).contiguous()
 
     def contact_forces(self, x):
         """force [N, n_c, 3]: the world-frame contact force on the robot at each contact point of the step from x"""
@@ -2136,7 +2114,7 @@ class HipSim:
         k, links, pts, lp, pp = _ik_targets(links, body_points)
         assert targets.is_cuda and targets.dtype == torch.float64 and tuple(targets.shape) == (n, k, 3), "targets"
         targets = targets.contiguous()
-        q_reference, qrp = self._dyn_rows(q_reference, n, self.model.dof_q, "q_reference")
+        q_reference, qrp = _DevArrays.rows(q_reference, n, self.model.dof_q, "q_reference")
         o = ik_options(method, **options)
         assert out is None or "q" in out, "out must hold q"
         shapes = _ik_shapes(self.model, n)
