@@ -134,6 +134,18 @@ __device__ int tds_oct_prof_iter = 500;
 #ifndef TDS_OCT_SWEEP_NA
 #define TDS_OCT_SWEEP_NA 1
 #endif
+// The helper's exposed waits, the same build, two parts, a switch each (-DTDS_OCT_...=0 compiles a part out, and every
+// statement then stands where it stood):
+//   TDS_OCT_HELP_ARGS       the helper reads the fields of the launch's control block that every step needs once, in front of its loop
+//   TDS_OCT_GEOM_BATCH      rows_geom's operands in two batches, one per dependent round trip
+// (Measured with them and not kept — tools/experiments/oct_root_helper_not_kept.txt: the root body's visual pose in the helper's
+//  wait at barrier (2), the root body's rigid inertia on the helper.)
+#ifndef TDS_OCT_HELP_ARGS
+#define TDS_OCT_HELP_ARGS 1
+#endif
+#ifndef TDS_OCT_GEOM_BATCH
+#define TDS_OCT_GEOM_BATCH 1
+#endif
 
 namespace {
 
@@ -303,6 +315,16 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   constexpr bool HELP_SCHUR = LOOP && BUILD == 3 && TDS_OCT_HELP_SCHUR != 0;
   // SWEEP_NA: main_sweep's instantiations with NA as a template constant (the same build only)
   constexpr bool SWEEP_NA = LOOP && BUILD == 3 && TDS_OCT_SWEEP_NA != 0;
+  // The helper's exposed waits (the same build only):
+  // HELP_ARGS: the helper's phases read the control block's every-step fields from a copy made in front of its loop (SPLIT_LOOP:
+  //   the loop is its own; `hc`, OCT_HC) — through the laundered segment pointer every field is a scalar load of its own in every
+  //   step, and where one field decides whether the next is read (help_np, help_poses_head, help_rec) a round trip of its own
+  //   that nothing covers.  What changes from step to step (ring positions, `last`) was never read from there: it follows `it`.
+  // GEOM_BATCH: rows_geom asks for everything that needs no other read first (contact point, distance, owner, direction, the
+  //   root's velocities, the two constants), then for what the owner decides (the leg's axes and velocities), a scheduling fence
+  //   behind each batch: left to itself the back end spreads the reads over the arithmetic with a wait in front of every use.
+  constexpr bool HELP_ARGS = SPLIT_LOOP && TDS_OCT_HELP_ARGS != 0;
+  constexpr bool GEOM_BATCH = LOOP && BUILD == 3 && TDS_OCT_GEOM_BATCH != 0;
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -404,6 +426,21 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   Carried car = {};
   TopConsts tc = {};
+  // HELP_ARGS: the fields of the launch's control block that the helper reads in every step, whatever the launch's form — which
+  // rings there are, where they are, whether the step is counted in — read from the kernel-argument segment once per launch and
+  // scalars from here on (no other build refers to it).  What only an exchange launch reads (the peer table, offsets, flags,
+  // epoch) stays a read per step.  The kernel has no SGPRs to spare: the back end parks these sixteen in the lanes of a VGPR in
+  // the prologue and fetches a field with one v_readlane where a step uses it — no wait (the whole block held across the loop
+  // was 40 parked SGPRs and 69 v_readlane per step; profiles/oct_root_helper_resources.txt).
+  struct HelpArgs {
+    const void *act_pool;
+    void *obs_ring, *y_ring;
+    unsigned int *peer_arrive;
+    unsigned long long *progress;
+    int act_envs, obs_slots, ring_envs, y_stride, obs_envs, ring_flags;
+  };
+  const HelpArgs hc = {ctl_arg.act_pool, ctl_arg.obs_ring, ctl_arg.y_ring, ctl_arg.peer_arrive, ctl_arg.progress, ctl_arg.act_envs,
+                       ctl_arg.obs_slots, ctl_arg.ring_envs, ctl_arg.y_stride, ctl_arg.obs_envs, ctl_arg.ring_flags};
   if constexpr (CARRY || TOP_EARLY) {
     const int lane_ = threadIdx.x & 7;
     const T *const xr_ = sm + ((threadIdx.x & 63) >> 3) * O.stride;
@@ -456,6 +493,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   const int dq = 6 + lane;  // my dof in the q / qd records
   const T *const CL = CT + lane * TB::LSTR;  // my lane's constants
   typename TdsCtlRef<LOOP>::type ctl = TdsCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(OctKernArgs, ctl));
+  // (a field of the control block as the helper's phases read it: HELP_ARGS, in the helper's own loop — the copy made in front of
+  //  that loop; everywhere else the field itself.  The condition is a compile-time constant: one arm only is compiled)
+#define OCT_HC(f) ((HELP_ARGS && ROLE == 1) ? hc.f : ctl.f)
   const T dt = CT[TB::SC + TB::DT];
   const int pgs_iters = (int)CT[TB::SC + TB::PGS_ITERATIONS];
   const bool last = it == nsteps - 1;
@@ -721,7 +761,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 
   // where this step's y record goes: the slot of a y ring (every step of a step-loop launch), else the handle's y record
   // (the last step); the last step of a ring launch leaves its record in the handle's y record as well
-  const int ystr = ctl.y_stride;
+  const int ystr = OCT_HC(y_stride);
   const int out_dim = (int)CT[TB::SC + TB::OUTPUT_DIM];
   const int nv = (int)CT[TB::SC + TB::NUM_VISUALS];
   // (worked out where a phase stores — three places — from a ring position laundered there: computed once at the top of the
@@ -733,8 +773,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     yo2 = nullptr;
     yend = ystr;
     yend2 = out_dim;
-    if (LOOP && ctl.y_ring != nullptr) {
-      yo = tds_global((TR *)ctl.y_ring) + ((size_t)ys * ctl.ring_envs + env) * ystr;
+    if (LOOP && OCT_HC(y_ring) != nullptr) {
+      yo = tds_global((TR *)OCT_HC(y_ring)) + ((size_t)ys * OCT_HC(ring_envs) + env) * ystr;
       if (last && y_out != nullptr) yo2 = y_out + (size_t)env * out_dim;
     } else if (last && y_out != nullptr) {
       yo = y_out + (size_t)env * (LOOP ? out_dim : ystr);
@@ -754,15 +794,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_MARK("help_np");
     // ================================ helper: narrowphase, visual poses ================================
     if constexpr (LOOP) {
-      if (it > 0 && ctl.obs_ring != nullptr && ctl.peer_arrive != nullptr)  // (wave-uniform; in front of the action request: the wait)
-        sig_tok = tds_peer_count_in(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
+      if (it > 0 && OCT_HC(obs_ring) != nullptr && OCT_HC(peer_arrive) != nullptr)  // (wave-uniform; in front of the action request: the wait)
+        sig_tok = tds_peer_count_in(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1);
       // The NEXT step's action block is requested here, by the helper (a different block per step: tds_hip_step_many), and goes
       // into the record's action slots in front of the visual poses' stores (help_poses) — the slots are dead since the PD
       // block, in front of barrier (1); the next PD block is behind barrier (0).  Requested by the main wavefront and held
       // until the integration, the value crossed the whole step in a register: the 256-register build spilled it to scratch
       // at the top of the step — a wait for the load itself — and reloaded it on the main wavefront's path
-      if (ctl.act_pool != nullptr && it + 1 < nsteps && valid)  // (wave-uniform but for `valid`)
-        next_act = (T)tds_global((const TR *)ctl.act_pool)[((size_t)act_blk * ctl.act_envs + env) * adim + lane];
+      if (OCT_HC(act_pool) != nullptr && it + 1 < nsteps && valid)  // (wave-uniform but for `valid`)
+        next_act = (T)tds_global((const TR *)OCT_HC(act_pool))[((size_t)act_blk * OCT_HC(act_envs) + env) * adim + lane];
     }
     if constexpr (W2) {  // my link's world transform and the root's sines / cosines, from the main wavefront
       const T *const kin = E + O.win + 8 * OctLds::ZW + lane * 12;
@@ -842,12 +882,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     if constexpr (LOOP) {
       // (loads and stores return through one in-order counter on gfx9: this wait sees the helper's record stores of the step
       //  before, issued a narrowphase and a row stage ago, and nothing of this step)
-      if (ctl.act_pool != nullptr && !last) xr[nq + nd + lane] = next_act;
+      if (OCT_HC(act_pool) != nullptr && !last) xr[nq + nd + lane] = next_act;
       // the records of step it - 1 — stored at the end of the iteration before, long acknowledged by now: the wait costs
       // nothing here, in front of this step's first stores — are counted in
-      if (it > 0 && ctl.obs_ring != nullptr) {  // (wave-uniform)
-        if (ctl.peer_arrive != nullptr) tds_peer_finish(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1, sig_tok);
-        else tds_signal_slot(ctl, (o_slot == 0 ? ctl.obs_slots : o_slot) - 1);
+      if (it > 0 && OCT_HC(obs_ring) != nullptr) {  // (wave-uniform)
+        if (OCT_HC(peer_arrive) != nullptr) tds_peer_finish(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1, sig_tok);
+        // (HELP_ARGS: this guard MIRRORS tds_signal_slot's own check — tds_step_shared.h: without the peer form it acts where there
+        //  is a progress counter only — so that a launch without one does not read the two fields per step.  Keep the two in
+        //  step: a form added to tds_signal_slot must be added here, or this guard skips it)
+        else if (!(HELP_ARGS && ROLE == 1) || hc.progress != nullptr) tds_signal_slot(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1);
       }
     }
   };
@@ -1330,6 +1373,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       const T owner = cpx[4 * OctLds::NCP + ac];
       const T *const dir = CT + TB::SC + TB::NB + 3 * tk;
       const T e[3] = {dir[0], dir[1], dir[2]};
+      T rv[6] = {}, c_rest = T(0), c_erp = T(0);  // (GEOM_BATCH: the root's velocities and the two constants, with the first batch)
+      if constexpr (GEOM_BATCH) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rv[k] = xr[nq + k];
+        c_rest = CT[TB::SC + TB::RESTITUTION];
+        c_erp = CT[TB::SC + TB::ERP_OVER_DT];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#define OCT_GEOM(early, read) (GEOM_BATCH ? (early) : (read))
       const int ol = real ? (int)owner : 8;    // owner lane; 8: the root body
       const bool on_leg = ol < 8;
       const int hl = on_leg ? (ol & ~1) : 0;   // the hip lane of the contact's leg
@@ -1341,6 +1393,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         sa[c] = swl[(hl + 1) * 6 + c];
       }
       const T qh = xr[nq + 6 + hl], qa = xr[nq + 6 + hl + 1];  // velocities before the step
+      if constexpr (GEOM_BATCH) __builtin_amdgcn_sched_barrier(0);
       // column of the point Jacobian along e: e . s_lin + P . (e x s_ang) = e . s_lin + (P x e) . s_ang  (jacobian.hpp:56-72)
       T mo[3];
       cross3(Pc, e, mo);
@@ -1353,11 +1406,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       zr[3] = dot3(e, pA3) + mo[0];
       zr[4] = dot3(e, pA4) + dot3(mo, A4);
       zr[5] = dot3(e, pA5) + dot3(mo, A5);
-      const T vrow = ((z0 * qh + z1 * qa) + (zr[0] * xr[nq + 0] + zr[1] * xr[nq + 1])) +
-                     ((zr[2] * xr[nq + 2] + zr[3] * xr[nq + 3]) + (zr[4] * xr[nq + 4] + zr[5] * xr[nq + 5]));
+      const T vrow = ((z0 * qh + z1 * qa) + (zr[0] * OCT_GEOM(rv[0], xr[nq + 0]) + zr[1] * OCT_GEOM(rv[1], xr[nq + 1]))) +
+                     ((zr[2] * OCT_GEOM(rv[2], xr[nq + 2]) + zr[3] * OCT_GEOM(rv[3], xr[nq + 3])) +
+                      (zr[4] * OCT_GEOM(rv[4], xr[nq + 4]) + zr[5] * OCT_GEOM(rv[5], xr[nq + 5])));
       // rel_vel = vel_a - vel_b = -J qd:  b_n = -(1 + e) n.rel_vel - erp dist / dt,  b_t = -t.rel_vel  (the dt qdd share of
       // the velocity: see main_fd)
-      const T crow = tk == 0 ? (T(1) + CT[TB::SC + TB::RESTITUTION]) * vrow - CT[TB::SC + TB::ERP_OVER_DT] * dist : vrow;
+      const T crow = tk == 0 ? (T(1) + OCT_GEOM(c_rest, CT[TB::SC + TB::RESTITUTION])) * vrow - OCT_GEOM(c_erp, CT[TB::SC + TB::ERP_OVER_DT]) * dist : vrow;
+#undef OCT_GEOM
       rw.z0 = z0;
       rw.z1 = z1;
 #pragma unroll
@@ -1775,20 +1830,20 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     // ---- [obs | reward | done] record (obs[0] = obs[1] = 0, ars_vectorized_environment.h:283-288): the slot of an obs ring
     //      (every step of a step-loop launch; floats on the multi-GPU wire format) and / or the caller's record (last step)
     if constexpr (LOOP) {
-      if (ctl.obs_ring != nullptr) {  // wave-uniform
+      if (OCT_HC(obs_ring) != nullptr) {  // wave-uniform
         const int slot = o_slot;
-        const int rf = ctl.ring_flags;
+        const int rf = OCT_HC(ring_flags);
         const bool f32w = (rf & TDS_RING_OBS_F32) != 0 || sizeof(TR) == 4;
-        const int np = ctl.peer_arrive != nullptr ? ctl.n_peers : 0;
+        const int np = OCT_HC(peer_arrive) != nullptr ? ctl.n_peers : 0;
         const bool rd_only = (rf & TDS_RING_PEER_REWARD_DONE) != 0;
-        if (ctl.peer_arrive != nullptr && (rf & TDS_RING_WIDE) != 0 && __all(valid)) {
+        if (OCT_HC(peer_arrive) != nullptr && (rf & TDS_RING_WIDE) != 0 && __all(valid)) {
           // Peer-store exchange, the wavefront's eight records as one row of 8-byte units (240 scalars: 960 contiguous bytes
           // on a float wire): every lane takes 8 bytes of the row — read from the environments' LDS records, converted
           // once — and the row goes out with one 8-byte-per-lane store instruction per destination and pass: this rank's
           // own block (device scope, write-through), then every peer's (system scope, over xGMI), the table's pointers by
           // scalar loads (see tds_step_shared.h: tds_obs_store_wide, the same store)
           const int wl = tid & 63;
-          const size_t row0 = ((size_t)slot * ctl.obs_envs + (size_t)blockIdx.x * 8) * (size_t)w_obs;
+          const size_t row0 = ((size_t)slot * OCT_HC(obs_envs) + (size_t)blockIdx.x * 8) * (size_t)w_obs;
           const int per_unit = f32w ? 2 : 1;
           const int n_units = (8 * w_obs) / per_unit;
           const unsigned long long *const __attribute__((address_space(4))) *tab =
@@ -1819,7 +1874,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             }
             const unsigned long long bits = ((unsigned long long)hi << 32) | (unsigned long long)lo;
             const size_t unit_at = row0 / per_unit + (size_t)uu;  // (row0 is a multiple of per_unit: TDS_RING_WIDE)
-            if (on) __hip_atomic_store(tds_global((unsigned long long *)ctl.obs_ring) + unit_at, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (on) __hip_atomic_store(tds_global((unsigned long long *)OCT_HC(obs_ring)) + unit_at, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (reward | done only: a unit travels if ANY of its columns is one of the two — on a float wire they may share a
             //  unit with an observation column)
             const bool to_peers = on && (!rd_only || tail);
@@ -1837,7 +1892,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             }
           }
         } else if (valid) {
-          const size_t at = ((size_t)slot * ctl.obs_envs + env) * w_obs;
+          const size_t at = ((size_t)slot * OCT_HC(obs_envs) + env) * w_obs;
           constexpr int NB = (w_obs + 7) / 8;
           T ov[NB];  // (read in one batch: see y_state)
 #pragma unroll
@@ -1853,11 +1908,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             const T vv = ov[k];
             // (TDS_RING_NOFENCE: device-scope write-through stores, visible to the exchange after a plain wait)
             if (rf & TDS_RING_OBS_F32) {
-              float *const pp = tds_global((float *)ctl.obs_ring) + at + i;
+              float *const pp = tds_global((float *)OCT_HC(obs_ring)) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               else OCT_ST((float)vv, pp);
             } else {
-              TR *const pp = tds_global((TR *)ctl.obs_ring) + at + i;
+              TR *const pp = tds_global((TR *)OCT_HC(obs_ring)) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               else OCT_ST((TR)vv, pp);
             }
@@ -1872,7 +1927,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         }
         // (peer-store exchange: EVERY step is counted in — the last one here, by the wavefront that has just stored it; kernel
         //  completion would tell this rank, not the peers)
-        if (last && ctl.peer_arrive != nullptr) tds_signal_slot(ctl, slot);
+        if (last && OCT_HC(peer_arrive) != nullptr) tds_signal_slot(ctl, slot);
       }
     }
     if (valid && last) {
@@ -2048,6 +2103,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     y_slot = y_slot + 1 >= ctl_arg.y_slots ? 0 : y_slot + 1;
     o_slot = o_slot + 1 >= ctl_arg.obs_slots ? 0 : o_slot + 1;
   }
+#undef OCT_HC
   };  // ================================ end of a step ================================
   // ================================ step loop ================================
   // SPLIT_LOOP: each wavefront of the workgroup in a loop of its own.  What the main wavefront carries from one step into the
