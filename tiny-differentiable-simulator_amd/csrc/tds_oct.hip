@@ -146,6 +146,26 @@ __device__ int tds_oct_prof_iter = 500;
 #ifndef TDS_OCT_GEOM_BATCH
 #define TDS_OCT_GEOM_BATCH 1
 #endif
+// Instructions of the main wavefront's chain that compute nothing, every build of the unit, three parts, a switch each
+// (-DTDS_OCT_...=0 compiles a part out, and every statement then stands where it stood; each part alone and in pairs:
+//  profiles/oct_main_diet_bench.txt, tools/experiments/oct_main_diet_not_kept.txt):
+//   TDS_OCT_SINCOS2         the joint's and the root's sines / cosines in one interleaved evaluation (tds_sincos2): the 17
+//                           constants of the routine in registers once per step instead of once per inlined copy — same bits
+//   TDS_OCT_ROOT_ZEROS      the root chain written without its structural zeros (A3 = e_x, A4 = (0, cx, sx), P x A3 = (0, Pz, -Py),
+//                           J3 = (d3, 0, 0)): without fast-math the back end keeps every x * 0 and 0 + x.  Only a product with a
+//                           literal-zero factor, or the addition of one, is left out; what remains is rounded as before — see
+//                           oct_dot3_0 for how the expressions are written — so results differ in the sign of an exact zero at most
+//   TDS_OCT_TOTALS_NOPIN    the robot's totals (main_dyn): the 8-lane sums of the summands that are not products without oct_sum's
+//                           pinning copy
+#ifndef TDS_OCT_SINCOS2
+#define TDS_OCT_SINCOS2 1
+#endif
+#ifndef TDS_OCT_ROOT_ZEROS
+#define TDS_OCT_ROOT_ZEROS 1
+#endif
+#ifndef TDS_OCT_TOTALS_NOPIN
+#define TDS_OCT_TOTALS_NOPIN 1
+#endif
 
 namespace {
 
@@ -179,9 +199,11 @@ __device__ __forceinline__ T pair_bcast(T v) { return oct_dpp<(K == 0 ? 0xA0 : 0
 //  into it, lane i would add its exact product to lane i ^ 1's rounded one and lane i ^ 1 the other way round: the two
 //  "same" sums then differ in the last bit, and with them everything that is redundant on every lane behind them; an
 //  environment's result would depend on which lane solves which constraint row, i.e. on its wavefront-mates' contacts)
-template <typename T>
+// (PIN = false: for a summand that is NOT a product — a sum, a table value: nothing can contract into the first addition, and
+//  the pin costs a copy wherever the summand itself is read again behind the sum)
+template <bool PIN = true, typename T>
 __device__ __forceinline__ T oct_sum(T v) {
-  asm volatile("" : "+v"(v));
+  if constexpr (PIN) asm volatile("" : "+v"(v));
   v += oct_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
   v += oct_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
   v += oct_dpp<0x141>(v);  // row_half_mirror
@@ -199,6 +221,72 @@ __device__ __forceinline__ float oct_bcast(float v) {
   const int b = __float_as_int(v);
   const int t = __builtin_amdgcn_update_dpp(0, b, 0x150 + K, 0xF, 0x3, false);
   return __int_as_float(__builtin_amdgcn_update_dpp(t, b, 0x150 + 8 + K, 0xF, 0xC, false));
+}
+
+// ---- TDS_OCT_ROOT_ZEROS: dot3 / cross3 / sym3_mulv / I s where components of an operand are structural zeros ----
+// -ffp-contract=on fuses as the source says: x * y + z * w is fma(x, y, rnd(z * w)) — the LEFT product is fused, the right one
+// rounded first — so dot3's a0 b0 + a1 b1 + a2 b2 is fma(a2, b2, fma(a0, b0, rnd(a1 b1))), and x * y - z * w is
+// fma(x, y, -rnd(z * w)).  With a product 0 what is left must name the SAME product as the rounded one: dot3 without its first
+// term is a2 b2 + a1 b1 (not a1 b1 + a2 b2), a cross product's component with one product gone is the other product alone.
+template <typename T>
+__device__ __forceinline__ T oct_dot3_0(const T *a, const T *b) {  // a[0] b[0] == 0
+  return a[2] * b[2] + a[1] * b[1];
+}
+template <typename T>
+__device__ __forceinline__ void oct_cross3_b0(const T *a, const T *b, T *o) {  // a x (0, b1, b2)
+  const T x = a[1] * b[2] - a[2] * b[1];
+  const T y = -(a[0] * b[2]);
+  const T z = a[0] * b[1];
+  o[0] = x;
+  o[1] = y;
+  o[2] = z;
+}
+template <typename T>
+__device__ __forceinline__ void oct_cross3_bx(const T *a, T d, T *o) {  // a x (d, 0, 0)
+  o[0] = T(0);
+  o[1] = a[2] * d;
+  o[2] = -(a[1] * d);
+}
+template <typename T>
+__device__ __forceinline__ void oct_cross3_ax_b0(T d, const T *b, T *o) {  // (d, 0, 0) x (0, b1, b2)
+  o[0] = T(0);
+  o[1] = -(d * b[2]);
+  o[2] = d * b[1];
+}
+template <typename T>
+__device__ __forceinline__ void oct_sym3_mulv_0(const T *s, const T *v, T *o) {  // v[0] == 0
+  const T x = s[2] * v[2] + s[1] * v[1];
+  const T y = s[4] * v[2] + s[3] * v[1];
+  const T z = s[5] * v[2] + s[4] * v[1];
+  o[0] = x;
+  o[1] = y;
+  o[2] = z;
+}
+// times_inertia (oct_body) of the axis (e_x | 0, p1, p2): F[3] is m * 0 - 0
+template <typename T>
+__device__ __forceinline__ void oct_times_inertia_ex(const T *I, const T *pl, T *F) {
+  T t3[3];
+  oct_cross3_b0(I + 6, pl, t3);
+  F[0] = I[0] + t3[0];
+  F[1] = I[1] + t3[1];
+  F[2] = I[2] + t3[2];
+  F[3] = T(0);
+  F[4] = I[9] * pl[1] - I[8];
+  F[5] = I[9] * pl[2] + I[7];
+}
+// ... of an axis (0, s1, s2 | s3, s4, s5)
+template <typename T>
+__device__ __forceinline__ void oct_times_inertia_0(const T *I, const T *s, T *F) {
+  T t3[3];
+  oct_sym3_mulv_0(I, s, F);
+  cross3(I + 6, s + 3, t3);
+  F[0] += t3[0];
+  F[1] += t3[1];
+  F[2] += t3[2];
+  oct_cross3_b0(I + 6, s, t3);
+  F[3] = I[9] * s[3] - t3[0];
+  F[4] = I[9] * s[4] - t3[1];
+  F[5] = I[9] * s[5] - t3[2];
 }
 
 // LDS per environment, offsets in scalars of T
@@ -325,6 +413,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //   behind each batch: left to itself the back end spreads the reads over the arithmetic with a wait in front of every use.
   constexpr bool HELP_ARGS = SPLIT_LOOP && TDS_OCT_HELP_ARGS != 0;
   constexpr bool GEOM_BATCH = LOOP && BUILD == 3 && TDS_OCT_GEOM_BATCH != 0;
+  // What the result does not need (every build): SINCOS2: main_kin's two sincos in one evaluation; ROOT_ZEROS: root_frame, the
+  // root's velocities and bias accelerations (main_kin), the root dofs' bias forces, couplings and block (main_dyn, main_dyn2)
+  // without the products and sums of the root axes' structural zeros
+  constexpr bool SINCOS2 = TDS_OCT_SINCOS2 != 0;
+  constexpr bool ROOT_ZEROS = TDS_OCT_ROOT_ZEROS != 0;
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -526,7 +619,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     A4[0] = T(0); A4[1] = cx; A4[2] = sx;
     A5[0] = sy; A5[1] = -sx * cy; A5[2] = cx * cy;
     pA3[0] = T(0); pA3[1] = P[2]; pA3[2] = -P[1];  // P x e_x
-    cross3(P, A4, pA4);
+    if constexpr (ROOT_ZEROS) oct_cross3_b0(P, A4, pA4);
+    else cross3(P, A4, pA4);
     cross3(P, A5, pA5);
   };
   auto times_inertia = [&](const T *I, const T *s, T *F) {  // (I w + h x v, m v - h x w)
@@ -580,6 +674,17 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       //  wavefront waited for behind barrier (2))
       asm volatile("" : "+v"(tau));
     }
+    // (my root angle: lanes 0, 1, 2 the three angles, the others the first)
+    auto root_angle = [&]() -> T {
+      if constexpr (CARRY) {
+        // (by value first: a conditional between array elements is a conditional between addresses, and `car` a record in scratch)
+        const T a3 = car.rq[3], a4 = car.rq[4], a5 = car.rq[5];
+        return lane == 1 ? a4 : (lane == 2 ? a5 : a3);
+      } else {
+        return xr[3 + (lane < 3 ? lane : 0)];
+      }
+    };
+    T root_s = T(0), root_c = T(0);  // (SINCOS2: the root angle's sine and cosine, evaluated beside the joint's)
     OCT_MARK("main_jcalc");
     // ---- B. jcalc (link.hpp:229-287)
 #pragma unroll
@@ -590,7 +695,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // joint's angle is multiplied by 0), t_J = S_linear q (zero for a revolute joint) — every joint type of link.hpp:229-287
       // without a branch; X_parent = X_T X_J, and where every X_T rotation is the identity (the Ant) no product at all
       T sn, cs;
-      tds_sincos(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), &sn, &cs);
+      if constexpr (SINCOS2) tds_sincos2(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), root_angle(), &sn, &cs, &root_s, &root_c);
+      else tds_sincos(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), &sn, &cs);
       const T c1 = T(1) - cs;
       const T nx = OCT_TOP(tc.nax[0], CL[TB::NAX]), ny = OCT_TOP(tc.nax[1], CL[TB::NAX + 1]), nz = OCT_TOP(tc.nax[2], CL[TB::NAX + 2]);
       T RJ[9];
@@ -624,15 +730,12 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     //         environment, broadcast (and, two-wavefront build, handed to the helper behind the links' world transforms)
     {
       T rs, rc;
-      T ang;  // (my root angle: lanes 0, 1, 2 the three angles, the others the first)
-      if constexpr (CARRY) {
-        // (by value first: a conditional between array elements is a conditional between addresses, and `car` a record in scratch)
-        const T a3 = car.rq[3], a4 = car.rq[4], a5 = car.rq[5];
-        ang = lane == 1 ? a4 : (lane == 2 ? a5 : a3);
+      if constexpr (SINCOS2) {
+        rs = root_s;
+        rc = root_c;
       } else {
-        ang = xr[3 + (lane < 3 ? lane : 0)];
+        tds_sincos(root_angle(), &rs, &rc);
       }
-      tds_sincos(ang, &rs, &rc);
       const T sx = oct_bcast<0>(rs), cx = oct_bcast<0>(rc);
       const T sy = oct_bcast<1>(rs), cy = oct_bcast<1>(rc);
       const T sz = oct_bcast<2>(rs), cz = oct_bcast<2>(rc);
@@ -650,36 +753,75 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       const T *const rqd = CARRY ? car.rqd : xr + nq;
       const T d0 = rqd[0], d1 = rqd[1], d2 = rqd[2], d3 = rqd[3], d4 = rqd[4], d5 = rqd[5];
       const T U[3] = {d0, d1, d2};
-      const T J3[3] = {d3, T(0), T(0)}, J4[3] = {A4[0] * d4, A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
-      const T W4[3] = {J3[0] + J4[0], J3[1] + J4[1], J3[2] + J4[2]};
-      const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
-      T pJ3[3], pJ4[3], pJ5[3];
-      cross3(P, J3, pJ3);
-      cross3(P, J4, pJ4);
-      cross3(P, J5, pJ5);
-      const T pW4[3] = {pJ3[0] + pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
-      const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
-      const T V3[3] = {U[0] + pJ3[0], U[1] + pJ3[1], U[2] + pJ3[2]};
-      const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
-      const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
-      T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
-      cross3(J3, J4, a45);
-      cross3(W4, J5, a55);
-      cross3(J3, pJ3, t1);
-      cross3(V3, J3, t2);
-      l3[0] = t1[0] + t2[0]; l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
-      cross3(W4, pJ4, t1);
-      cross3(V4, J4, t2);
-      l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
-      cross3(W5, pJ5, t1);
-      cross3(V5, J5, t2);
-      l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
+      if constexpr (ROOT_ZEROS) {
+        // J3 = (d3, 0, 0), J4 = (0, cx d4, sx d4): the statements of the general form below, each without its 0 * x and 0 + x
+        const T J4[3] = {T(0), A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
+        const T W4[3] = {d3, J4[1], J4[2]};
+        const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
+        T pJ3[3], pJ4[3], pJ5[3];
+        oct_cross3_bx(P, d3, pJ3);
+        oct_cross3_b0(P, J4, pJ4);
+        cross3(P, J5, pJ5);
+        const T pW4[3] = {pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
+        const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
+        const T V3[3] = {U[0], U[1] + pJ3[1], U[2] + pJ3[2]};
+        const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
+        const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
+        T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
+        oct_cross3_ax_b0(d3, J4, a45);
+        cross3(W4, J5, a55);
+        oct_cross3_ax_b0(d3, pJ3, t1);
+        oct_cross3_bx(V3, d3, t2);
+        l3[0] = T(0); l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
+        cross3(W4, pJ4, t1);
+        oct_cross3_b0(V4, J4, t2);
+        l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
+        cross3(W5, pJ5, t1);
+        cross3(V5, J5, t2);
+        l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        v5[k] = W5[k];
-        v5[3 + k] = V5[k];
-        a5[k] = a45[k] + a55[k];
-        a5[3 + k] = (l3[k] + l4[k] + l5[k]) - OCT_TOP(tc.grav[k], CT[TB::SC + TB::GRAV + k]);
+        for (int k = 0; k < 3; ++k) {
+          v5[k] = W5[k];
+          v5[3 + k] = V5[k];
+        }
+        a5[0] = a55[0];
+        a5[1] = a45[1] + a55[1];
+        a5[2] = a45[2] + a55[2];
+        a5[3] = (l4[0] + l5[0]) - OCT_TOP(tc.grav[0], CT[TB::SC + TB::GRAV + 0]);
+        a5[4] = (l3[1] + l4[1] + l5[1]) - OCT_TOP(tc.grav[1], CT[TB::SC + TB::GRAV + 1]);
+        a5[5] = (l3[2] + l4[2] + l5[2]) - OCT_TOP(tc.grav[2], CT[TB::SC + TB::GRAV + 2]);
+      } else {
+        const T J3[3] = {d3, T(0), T(0)}, J4[3] = {A4[0] * d4, A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
+        const T W4[3] = {J3[0] + J4[0], J3[1] + J4[1], J3[2] + J4[2]};
+        const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
+        T pJ3[3], pJ4[3], pJ5[3];
+        cross3(P, J3, pJ3);
+        cross3(P, J4, pJ4);
+        cross3(P, J5, pJ5);
+        const T pW4[3] = {pJ3[0] + pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
+        const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
+        const T V3[3] = {U[0] + pJ3[0], U[1] + pJ3[1], U[2] + pJ3[2]};
+        const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
+        const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
+        T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
+        cross3(J3, J4, a45);
+        cross3(W4, J5, a55);
+        cross3(J3, pJ3, t1);
+        cross3(V3, J3, t2);
+        l3[0] = t1[0] + t2[0]; l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
+        cross3(W4, pJ4, t1);
+        cross3(V4, J4, t2);
+        l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
+        cross3(W5, pJ5, t1);
+        cross3(V5, J5, t2);
+        l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          v5[k] = W5[k];
+          v5[3 + k] = V5[k];
+          a5[k] = a45[k] + a55[k];
+          a5[3 + k] = (l3[k] + l4[k] + l5[k]) - OCT_TOP(tc.grav[k], CT[TB::SC + TB::GRAV + k]);
+        }
       }
     }
 #undef OCT_TOP
@@ -1007,10 +1149,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_MARK("main_totals");
     // ---- E. composite inertia / bias force (CRBA, mass_matrix.hpp:39-56): the robot's totals = root + every leg link
     //         (8-lane sums of the rigid values: every lane the same bits); the hip's composite = hip + ankle
+    // (Ic[6 .. 8] = m cw are products: pinned.  The others are sums — Ic[0 .. 5], fc — or a table value, Ic[9])
+    static_for<0, 10>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      It[k] += oct_sum<!(TDS_OCT_TOTALS_NOPIN != 0) || (k >= 6 && k <= 8)>(Ic[k]);
+    });
 #pragma unroll
-    for (int k = 0; k < 10; ++k) It[k] += oct_sum(Ic[k]);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) ft[k] += oct_sum(fc[k]);
+    for (int k = 0; k < 6; ++k) ft[k] += oct_sum<!(TDS_OCT_TOTALS_NOPIN != 0)>(fc[k]);
     {
       const T recv = pos == 0 ? T(1) : T(0);
 #pragma unroll
@@ -1029,8 +1174,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     Cr[0] = ft[3];  // bias forces of the root dofs
     Cr[1] = ft[4];
     Cr[2] = ft[5];
-    Cr[3] = dot6(ax3, ft);
-    Cr[4] = dot6(ax4, ft);
+    if constexpr (ROOT_ZEROS) {  // (ax3 = (1, 0, 0 | 0, pA3[1], pA3[2]), ax4 = (0, A4[1], A4[2] | pA4))
+      Cr[3] = ft[0] + oct_dot3_0(pA3, ft + 3);
+      Cr[4] = oct_dot3_0(A4, ft) + dot3(pA4, ft + 3);
+    } else {
+      Cr[3] = dot6(ax3, ft);
+      Cr[4] = dot6(ax4, ft);
+    }
     Cr[5] = dot6(ax5, ft);
     // ---- G. M in leaves-first order.  My row of my leg's 2 x 2 block (M[i][j] = F_i . s_j for j an ancestor of i or i,
     //         mass_matrix.hpp:87-109) and my coupling to the root dofs
@@ -1044,8 +1194,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       Cc[0] = Fc[3];
       Cc[1] = Fc[4];
       Cc[2] = Fc[5];
-      Cc[3] = dot6(Fc, ax3);
-      Cc[4] = dot6(Fc, ax4);
+      if constexpr (ROOT_ZEROS) {
+        Cc[3] = Fc[0] + oct_dot3_0(Fc + 3, pA3);
+        Cc[4] = oct_dot3_0(Fc, A4) + dot3(Fc + 3, pA4);
+      } else {
+        Cc[3] = dot6(Fc, ax3);
+        Cc[4] = dot6(Fc, ax4);
+      }
       Cc[5] = dot6(Fc, ax5);
     }
     OCT_MARK("main_legldl");
@@ -1132,20 +1287,35 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     T F3[6], F4[6];
     auto root_block_a1 = [&]() {
       const T m = It[9];
-      times_inertia(It, ax3, F3);
+      // (ROOT_ZEROS: F3[3] = m * 0 - 0 is a structural zero of its own, in the three dot products below as well)
+      if constexpr (ROOT_ZEROS) oct_times_inertia_ex(It, pA3, F3);
+      else times_inertia(It, ax3, F3);
       Sm[0] = m;
       Sm[1] = T(0); Sm[2] = m;
       Sm[3] = T(0); Sm[4] = T(0); Sm[5] = m;
-      Sm[6] = F3[3]; Sm[7] = F3[4]; Sm[8] = F3[5]; Sm[9] = dot6(ax3, F3);
+      Sm[6] = F3[3]; Sm[7] = F3[4]; Sm[8] = F3[5];
+      if constexpr (ROOT_ZEROS) Sm[9] = F3[0] + oct_dot3_0(pA3, F3 + 3);
+      else Sm[9] = dot6(ax3, F3);
     };
     auto root_block_a2 = [&]() {
-      times_inertia(It, ax4, F4);
-      Sm[10] = F4[3]; Sm[11] = F4[4]; Sm[12] = F4[5]; Sm[13] = dot6(ax4, F3); Sm[14] = dot6(ax4, F4);
+      if constexpr (ROOT_ZEROS) oct_times_inertia_0(It, ax4, F4);
+      else times_inertia(It, ax4, F4);
+      Sm[10] = F4[3]; Sm[11] = F4[4]; Sm[12] = F4[5];
+      if constexpr (ROOT_ZEROS) {
+        Sm[13] = oct_dot3_0(A4, F3) + oct_dot3_0(pA4, F3 + 3);
+        Sm[14] = oct_dot3_0(A4, F4) + dot3(pA4, F4 + 3);
+      } else {
+        Sm[13] = dot6(ax4, F3);
+        Sm[14] = dot6(ax4, F4);
+      }
     };
     auto root_block_b = [&]() {
       T F5[6];
       times_inertia(It, ax5, F5);
-      Sm[15] = F5[3]; Sm[16] = F5[4]; Sm[17] = F5[5]; Sm[18] = dot6(ax5, F3); Sm[19] = dot6(ax5, F4); Sm[20] = dot6(ax5, F5);
+      Sm[15] = F5[3]; Sm[16] = F5[4]; Sm[17] = F5[5];
+      if constexpr (ROOT_ZEROS) Sm[18] = dot3(A5, F3) + oct_dot3_0(pA5, F3 + 3);
+      else Sm[18] = dot6(ax5, F3);
+      Sm[19] = dot6(ax5, F4); Sm[20] = dot6(ax5, F5);
     };
     // the sums sum_lanes L_c[r] W[r'] of the Schur complement, entry e = r (r + 1) / 2 + r' on lane e mod 8 (three passes)
     if constexpr (HELP_SCHUR) {

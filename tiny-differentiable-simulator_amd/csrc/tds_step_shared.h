@@ -80,6 +80,73 @@ static __device__ __forceinline__ void tds_sincos(double x, double *sn, double *
 }
 static __device__ __forceinline__ void tds_sincos(float x, float *sn, float *cs) { sincosf(x, sn, cs); }
 
+// tds_sincos of TWO arguments in one evaluation: per argument the operations of tds_sincos in its order — the same bits —
+// the two chains interleaved statement by statement, so that each of the 17 constants is named once in one block (a VOP3 f64
+// operand cannot be a 64-bit literal: a constant is two moves into a register pair wherever a copy of the routine stands;
+// tds_oct.hip: the joint's angle and the root's, both known at the top of the step).  The fallback keeps its rule per
+// argument: a lane beyond 1e5 (or NaN) takes the library routine for THAT argument only.
+static __device__ __forceinline__ void tds_sincos2(double xa, double xb, double *sa, double *ca, double *sb, double *cb) {
+  const bool biga = !(__builtin_fabs(xa) < 1.0e5), bigb = !(__builtin_fabs(xb) < 1.0e5);
+  const double ka = __builtin_rint(xa * 6.36619772367581382433e-01), kb = __builtin_rint(xb * 6.36619772367581382433e-01);
+  double ra = __builtin_fma(-ka, 1.57079632679489655800e+00, xa), rb = __builtin_fma(-kb, 1.57079632679489655800e+00, xb);
+  ra = __builtin_fma(-ka, 6.12323399573676603587e-17, ra);
+  rb = __builtin_fma(-kb, 6.12323399573676603587e-17, rb);
+  const int qa = (int)ka, qb = (int)kb;
+  const double za = ra * ra, zb = rb * rb;
+  double psa = __builtin_fma(za, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+  double psb = __builtin_fma(zb, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+  psa = __builtin_fma(za, psa, 2.75573137070700676789e-06);
+  psb = __builtin_fma(zb, psb, 2.75573137070700676789e-06);
+  psa = __builtin_fma(za, psa, -1.98412698298579493134e-04);
+  psb = __builtin_fma(zb, psb, -1.98412698298579493134e-04);
+  psa = __builtin_fma(za, psa, 8.33333333332248946124e-03);
+  psb = __builtin_fma(zb, psb, 8.33333333332248946124e-03);
+  psa = __builtin_fma(za, psa, -1.66666666666666324348e-01);
+  psb = __builtin_fma(zb, psb, -1.66666666666666324348e-01);
+  const double s0a = __builtin_fma(za * ra, psa, ra), s0b = __builtin_fma(zb * rb, psb, rb);
+  double pca = __builtin_fma(za, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+  double pcb = __builtin_fma(zb, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+  pca = __builtin_fma(za, pca, -2.75573143513906633035e-07);
+  pcb = __builtin_fma(zb, pcb, -2.75573143513906633035e-07);
+  pca = __builtin_fma(za, pca, 2.48015872894767294178e-05);
+  pcb = __builtin_fma(zb, pcb, 2.48015872894767294178e-05);
+  pca = __builtin_fma(za, pca, -1.38888888888741095749e-03);
+  pcb = __builtin_fma(zb, pcb, -1.38888888888741095749e-03);
+  pca = __builtin_fma(za, pca, 4.16666666666666019037e-02);
+  pcb = __builtin_fma(zb, pcb, 4.16666666666666019037e-02);
+  const double c0a = __builtin_fma(za * za, pca, __builtin_fma(za, -0.5, 1.0));
+  const double c0b = __builtin_fma(zb * zb, pcb, __builtin_fma(zb, -0.5, 1.0));
+  const bool swapa = (qa & 1) != 0, swapb = (qb & 1) != 0;
+  const double ssa = swapa ? c0a : s0a, cca = swapa ? s0a : c0a;
+  const double ssb = swapb ? c0b : s0b, ccb = swapb ? s0b : c0b;
+  double sa_ = (qa & 2) ? -ssa : ssa, ca_ = ((qa + 1) & 2) ? -cca : cca;
+  double sb_ = (qb & 2) ? -ssb : ssb, cb_ = ((qb + 1) & 2) ? -ccb : ccb;
+  // (ONE branch behind both chains, the two arguments' own tests inside it: with a branch per argument the back end sinks the
+  //  second chain behind the first branch — two blocks, and the constants are moved into registers once per block again)
+  if (__builtin_expect(__any(biga || bigb), 0)) {
+    if (__any(biga)) {
+      double s2, c2;
+      sincos(xa, &s2, &c2);
+      sa_ = biga ? s2 : sa_;
+      ca_ = biga ? c2 : ca_;
+    }
+    if (__any(bigb)) {
+      double s2, c2;
+      sincos(xb, &s2, &c2);
+      sb_ = bigb ? s2 : sb_;
+      cb_ = bigb ? c2 : cb_;
+    }
+  }
+  *sa = sa_;
+  *ca = ca_;
+  *sb = sb_;
+  *cb = cb_;
+}
+static __device__ __forceinline__ void tds_sincos2(float xa, float xb, float *sa, float *ca, float *sb, float *cb) {
+  sincosf(xa, sa, ca);
+  sincosf(xb, sb, cb);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // A step's records are out: the wavefront that stored them counts its workgroup in.
 //
