@@ -1,5 +1,5 @@
 """The 8-lane kernel's first Gauss-Seidel sweep specialised for the wavefront's contact count (csrc/tds_oct.hip: main_sweep with
-NA as a template constant; step-loop build for one wavefront per SIMD; switch TDS_OCT_SWEEP_NA, run-time option oct_sweep_na).
+NA as a template constant; step-loop build for one wavefront per SIMD; run-time option oct_sweep_na).
 
 With NA = 1 .. 4 contacts at most among a wavefront's environments the first sweep of a step runs straight-line: every row's
 kind static, the normal rows' impulses handed to their friction rows in registers, the long window's second barrier where the

@@ -1,5 +1,5 @@
 """The 8-lane kernel's main wavefront without the instructions its result does not need (csrc/tds_oct.hip, every build of the
-unit; switches TDS_OCT_SINCOS2, TDS_OCT_ROOT_ZEROS, TDS_OCT_TOTALS_NOPIN).
+unit: main_kin's one sincos evaluation, the root chain's oct_*_0 helpers, main_dyn's totals).
 
 What these tests guard, part by part:
   * tds_sincos2 (csrc/tds_step_shared.h): the joint's and the root angles' sines and cosines in one interleaved evaluation —

@@ -1,5 +1,5 @@
 """The 8-lane kernel's helper wavefront without its exposed waits (csrc/tds_oct.hip, step-loop build for one wavefront per
-SIMD; switches TDS_OCT_HELP_ARGS, TDS_OCT_GEOM_BATCH).
+SIMD — the unit's SOLO trait: the helper's control-block copy and rows_geom's batched reads).
 
 What these tests guard, part by part:
   * the helper's copy of the control block (`hc`, read through OCT_HC): which rings a launch has, where they are, their strides

@@ -30,12 +30,22 @@
 //
 // Two forms (template parameter LOOP) as in tds_quad.hip: one step per launch, and K steps per launch with the state in
 // LDS, a fresh action block per step, per-step record rings, reset-pool entries taken inside the loop and the exchange of
-// the multi-GPU layer (tds_shard.hip: progress counters, peer stores).  Two builds of each (template parameter W2): one
-// wavefront per workgroup of eight environments, and TWO — a main wavefront on the step's dependent chain and a helper /
-// recorder beside it (narrowphase, visual poses, constraint rows, every record store), the form the host grants while
-// every workgroup is resident with at most two wavefronts per SIMD (Ant x 4096: one wavefront per SIMD; x 8192: two).
+// the multi-GPU layer (tds_shard.hip: progress counters, peer stores).  Four builds of each (template parameter BUILD, see
+// oct_body): one wavefront per workgroup of eight environments, and three with TWO — a main wavefront on the step's
+// dependent chain and a helper / recorder beside it (narrowphase, visual poses, constraint rows, every record store), the
+// form the host grants while every workgroup is resident with at most two wavefronts per SIMD (Ant x 4096: one wavefront
+// per SIMD; x 8192: two).  Who does what between which barriers: the comment at "the step" at the end of oct_body.
 // In-kernel reset + settle, substeps with one action through a policy and on-device rollouts stay with the general
 // kernel.  Reference files as in tds_kernels.hip.
+//
+// One instantiation is tuned beyond the others: the step-loop form of the build for one wavefront per SIMD (oct_body:
+// SOLO) — the benchmark's, Ant x 4096.  There each wavefront has a loop of its own, the main wavefront carries its state and
+// the constants of the step's top across the step boundary in registers, the helper sums the Schur complement, stores the
+// visual poses in its idle tail, reads the launch's control block once and its rows' operands in batches, and the first
+// sweep is specialised for 1 .. 4 contacts.  Where it differs, an `if constexpr (SOLO)` says so and why at the place; the
+// other seven instantiations compile the other arm and keep their statement order: reordered statements move the
+// register allocation of builds that gain nothing from them (tools/experiments/lds_batching_not_kept.txt).  What was
+// measured and lost, so that nobody tries it again: tools/experiments/oct_*_not_kept.txt.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
@@ -101,72 +111,6 @@ __device__ int tds_oct_prof_iter = 500;
 #define OCT_MARK(name) do { } while (0)
 #endif
 
-// The step boundary of the two-wavefront step-loop builds, three parts, each behind a switch of its own (an experiment build
-// turns one off with -DTDS_OCT_...=0; builds that do not take a part keep their statement order — see oct_body):
-//   TDS_OCT_SD_LATE    a friction row's first use of its normal row's impulse behind the row's 8-lane sum
-//   TDS_OCT_CARRY      the main wavefront's state across barrier (0) in registers
-//   TDS_OCT_TOP_EARLY  the constants of the PD block and jcalc requested in front of barrier (0)
-#ifndef TDS_OCT_SD_LATE
-#define TDS_OCT_SD_LATE 1
-#endif
-#ifndef TDS_OCT_CARRY
-#define TDS_OCT_CARRY 1
-#endif
-#ifndef TDS_OCT_TOP_EARLY
-#define TDS_OCT_TOP_EARLY 1
-#endif
-#ifndef TDS_OCT_SPLIT_LOOP  // (1: a loop per wavefront even where nothing is carried — what the split is worth on its own)
-#define TDS_OCT_SPLIT_LOOP 0
-#endif
-// Who computes what between barriers (1b) and (2) of the step-loop build for one wavefront per SIMD, two parts, a switch each
-// (the same convention: -DTDS_OCT_...=0 compiles a part out, and every statement then stands where it stood):
-//   TDS_OCT_POSES_LATE     the visual poses behind the helper's last row window, in its idle tail in front of barrier (0)
-//   TDS_OCT_HELP_SCHUR     the 21 sums of the Schur complement on the helper, handed over at a barrier of its own, (1c)
-// (The head of the forward dynamics in front of (1c) as well was measured and lost: tools/experiments/oct_helper_schur_not_kept.txt.)
-#ifndef TDS_OCT_POSES_LATE
-#define TDS_OCT_POSES_LATE 1
-#endif
-#ifndef TDS_OCT_HELP_SCHUR
-#define TDS_OCT_HELP_SCHUR 1
-#endif
-// The first Gauss-Seidel sweep of the same build, specialised for NA = 1 .. 4 (main_sweep; run-time option oct_sweep_na, default 1):
-//   TDS_OCT_SWEEP_NA       0 compiles the four instantiations out; every statement then stands where it stood
-#ifndef TDS_OCT_SWEEP_NA
-#define TDS_OCT_SWEEP_NA 1
-#endif
-// The helper's exposed waits, the same build, two parts, a switch each (-DTDS_OCT_...=0 compiles a part out, and every
-// statement then stands where it stood):
-//   TDS_OCT_HELP_ARGS       the helper reads the fields of the launch's control block that every step needs once, in front of its loop
-//   TDS_OCT_GEOM_BATCH      rows_geom's operands in two batches, one per dependent round trip
-// (Measured with them and not kept — tools/experiments/oct_root_helper_not_kept.txt: the root body's visual pose in the helper's
-//  wait at barrier (2), the root body's rigid inertia on the helper.)
-#ifndef TDS_OCT_HELP_ARGS
-#define TDS_OCT_HELP_ARGS 1
-#endif
-#ifndef TDS_OCT_GEOM_BATCH
-#define TDS_OCT_GEOM_BATCH 1
-#endif
-// Instructions of the main wavefront's chain that compute nothing, every build of the unit, three parts, a switch each
-// (-DTDS_OCT_...=0 compiles a part out, and every statement then stands where it stood; each part alone and in pairs:
-//  profiles/oct_main_diet_bench.txt, tools/experiments/oct_main_diet_not_kept.txt):
-//   TDS_OCT_SINCOS2         the joint's and the root's sines / cosines in one interleaved evaluation (tds_sincos2): the 17
-//                           constants of the routine in registers once per step instead of once per inlined copy — same bits
-//   TDS_OCT_ROOT_ZEROS      the root chain written without its structural zeros (A3 = e_x, A4 = (0, cx, sx), P x A3 = (0, Pz, -Py),
-//                           J3 = (d3, 0, 0)): without fast-math the back end keeps every x * 0 and 0 + x.  Only a product with a
-//                           literal-zero factor, or the addition of one, is left out; what remains is rounded as before — see
-//                           oct_dot3_0 for how the expressions are written — so results differ in the sign of an exact zero at most
-//   TDS_OCT_TOTALS_NOPIN    the robot's totals (main_dyn): the 8-lane sums of the summands that are not products without oct_sum's
-//                           pinning copy
-#ifndef TDS_OCT_SINCOS2
-#define TDS_OCT_SINCOS2 1
-#endif
-#ifndef TDS_OCT_ROOT_ZEROS
-#define TDS_OCT_ROOT_ZEROS 1
-#endif
-#ifndef TDS_OCT_TOTALS_NOPIN
-#define TDS_OCT_TOTALS_NOPIN 1
-#endif
-
 namespace {
 
 #define OCT_SYNC()                                             \
@@ -223,7 +167,11 @@ __device__ __forceinline__ float oct_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(t, b, 0x150 + 8 + K, 0xF, 0xC, false));
 }
 
-// ---- TDS_OCT_ROOT_ZEROS: dot3 / cross3 / sym3_mulv / I s where components of an operand are structural zeros ----
+// ---- dot3 / cross3 / sym3_mulv / I s where components of an operand are structural zeros ----
+// The root chain is written without the zeros of its axes (A3 = e_x, A4 = (0, cx, sx), P x A3 = (0, Pz, -Py), J3 = (d3, 0, 0)):
+// without fast-math the back end keeps every x * 0 and 0 + x.  Only a product with a literal-zero factor, or the addition of
+// one, is left out; what remains is rounded as the general form rounds it, so results differ from it in the sign of an exact
+// zero at most (profiles/oct_main_diet_bench.txt, tools/experiments/oct_main_diet_not_kept.txt).
 // -ffp-contract=on fuses as the source says: x * y + z * w is fma(x, y, rnd(z * w)) — the LEFT product is fused, the right one
 // rounded first — so dot3's a0 b0 + a1 b1 + a2 b2 is fma(a2, b2, fma(a0, b0, rnd(a1 b1))), and x * y - z * w is
 // fma(x, y, -rnd(z * w)).  With a product 0 what is left must name the SAME product as the rounded one: dot3 without its first
@@ -336,11 +284,7 @@ struct OctKernArgs {
 // the constants of the model as the kernel reads them: one table in LDS behind the environments' regions, copied from
 // DevModel::oct_tab (laid out by tds_build_oct_table on the host: tds_device_model.h, TDS_OCT_*) at the top of a launch
 using TB = TdsOctTab;
-// wavefront priorities of the two-wavefront builds: 1 = the main wavefront at priority 3, the helper at 0 (see the top of the step)
-constexpr int TDS_OCT_PRIO = 1;
 
-// record stores: plain stores (as non-temporal stores they changed nothing: tools/experiments/r06_not_kept.txt)
-#define OCT_ST(v, p) (*(p) = (v))
 // barrier between the two wavefronts of a workgroup (W2: LDS writes done, then s_barrier — neither wavefront waits for its
 // outstanding global stores); a compiler-level fence in the one-wave build, where the LDS executes a wavefront's
 // instructions in order
@@ -374,50 +318,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   }
 #endif
   constexpr bool W2 = BUILD >= 2;
-  // BATCH_SCHUR: the Schur sums' operands requested a pass at a time, the root block's arithmetic across them (main_dyn2).  The
-  // step-loop build for one wavefront per SIMD only — the benchmark's: build 2 pays for the operands' registers with scratch
-  // (16-32 B), the straight-line form of build 3 with two more registers, and the one-wavefront build plays both roles in one
-  // stream: nothing waits for its main part (profiles/oct_kernel_resources_lds.txt).  Same arithmetic either way, term by term.
-  constexpr bool BATCH_SCHUR = LOOP && BUILD == 3;
-  // The step boundary (step-loop forms of the two-wavefront builds only: where a switch is off every statement stands where it stood —
-  // reordered statements move the register allocation of builds that do not take them, tools/experiments/lds_batching_not_kept.txt):
-  // SD_LATE: main_sweep; CARRY, TOP_EARLY: main_fin -> main_kin of the next step
-  constexpr bool SD_LATE = LOOP && (BUILD == 2 || BUILD == 3) && TDS_OCT_SD_LATE != 0;
-  // (CARRY and TOP_EARLY in the build for one wavefront per SIMD only — the benchmark's: the 256-register build pays for the
-  //  carried state with 20 B of scratch and for the 33 constants with 64 - 84 B: profiles/oct_step_boundary_resources.txt)
-  constexpr bool CARRY = LOOP && BUILD == 3 && TDS_OCT_CARRY != 0;
-  constexpr bool TOP_EARLY = LOOP && BUILD == 3 && TDS_OCT_TOP_EARLY != 0;
-  constexpr bool SPLIT_LOOP = CARRY || TOP_EARLY || (LOOP && BUILD == 3 && TDS_OCT_SPLIT_LOOP != 0);
-  // Between barriers (1b) and (2) (the same build only: the others keep their statement order).  Without them the helper idles
-  // ~2 k cycles in front of barrier (0) and is yet the late one at barrier (2), behind the visual poses:
-  // POSES_LATE: help_poses' computation and stores move behind the helper's last row window (help_poses_tail) — the link and root
-  //   transforms stay in the helper's registers across the windows, whose rows overwrite the hand-over slots; the first window's
-  //   rows then pass from rows_leg to rows_root in registers (no rows_park / rows_fetch);
-  // HELP_SCHUR: the 21 Schur sums by the helper directly behind (1b) (help_schur), barrier (1c), and the main wavefront's root
-  //   block straight through in front of it.
-  // LDS between (1b) and (2) in this build: W (O.xs) is read by the helper only, in front of (1c) — the sweep's first impulse is
-  // written behind the first window barrier; O.fac is written by the helper in front of (1c), read by every main lane behind it,
-  // then overwritten by main lane 0 with the factors (behind an OCT_SYNC: every lane's reads are done) and read by the helper
-  // behind (2); the helper's next write to it is behind (1b) of the next step.
-  constexpr bool POSES_LATE = LOOP && BUILD == 3 && TDS_OCT_POSES_LATE != 0;
-  constexpr bool HELP_SCHUR = LOOP && BUILD == 3 && TDS_OCT_HELP_SCHUR != 0;
-  // SWEEP_NA: main_sweep's instantiations with NA as a template constant (the same build only)
-  constexpr bool SWEEP_NA = LOOP && BUILD == 3 && TDS_OCT_SWEEP_NA != 0;
-  // The helper's exposed waits (the same build only):
-  // HELP_ARGS: the helper's phases read the control block's every-step fields from a copy made in front of its loop (SPLIT_LOOP:
-  //   the loop is its own; `hc`, OCT_HC) — through the laundered segment pointer every field is a scalar load of its own in every
-  //   step, and where one field decides whether the next is read (help_np, help_poses_head, help_rec) a round trip of its own
-  //   that nothing covers.  What changes from step to step (ring positions, `last`) was never read from there: it follows `it`.
-  // GEOM_BATCH: rows_geom asks for everything that needs no other read first (contact point, distance, owner, direction, the
-  //   root's velocities, the two constants), then for what the owner decides (the leg's axes and velocities), a scheduling fence
-  //   behind each batch: left to itself the back end spreads the reads over the arithmetic with a wait in front of every use.
-  constexpr bool HELP_ARGS = SPLIT_LOOP && TDS_OCT_HELP_ARGS != 0;
-  constexpr bool GEOM_BATCH = LOOP && BUILD == 3 && TDS_OCT_GEOM_BATCH != 0;
-  // What the result does not need (every build): SINCOS2: main_kin's two sincos in one evaluation; ROOT_ZEROS: root_frame, the
-  // root's velocities and bias accelerations (main_kin), the root dofs' bias forces, couplings and block (main_dyn, main_dyn2)
-  // without the products and sums of the root axes' structural zeros
-  constexpr bool SINCOS2 = TDS_OCT_SINCOS2 != 0;
-  constexpr bool ROOT_ZEROS = TDS_OCT_ROOT_ZEROS != 0;
+  // SOLO: the step-loop form compiled for one wavefront per SIMD — the benchmark's instantiation, and the one with registers
+  // to spare.  What is confined to it costs registers: the 256-register build would pay with scratch, and the others gain
+  // nothing from it (each site says what; profiles/oct_step_boundary_resources.txt, profiles/oct_kernel_resources_lds.txt).
+  constexpr bool SOLO = LOOP && BUILD == 3;
+  // SD_LATE (main_sweep): a friction row's first use of its normal row's impulse stands behind the row's 8-lane sum — the
+  // step-loop forms of builds 2 and 3
+  constexpr bool SD_LATE = LOOP && (BUILD == 2 || BUILD == 3);
   constexpr int nq = 14, nd = 14, adim = 8, in_dim = nq + nd + adim + 3, w_obs = nq + nd + 2;
   constexpr int NT = W2 ? 128 : 64;
   T *const CT = sm + 8 * O.stride;  // the constant table
@@ -472,17 +379,19 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // (where my lane's action sits in the record: one register across the steps, against a table read in front of the PD block's
   //  read of the action — two LDS round trips in a row at the top of the main wavefront's step)
   const int act_slot = (int)(CT + (threadIdx.x & 7) * TB::LSTR)[TB::ACT];
-  // CARRY: what the main wavefront's integration (main_fin) hands to its next kinematics (main_kin) in registers — its dof's q
+  // SOLO: what the main wavefront's integration (main_fin) hands to its next kinematics (main_kin) in registers — its dof's q
   // and qd, the root's six coordinates and six velocities, the very values it stores into the LDS record — so that the top of a
   // step does not read back across barrier (0) what the wavefront wrote itself a phase earlier.  The record is read for the
   // first step of a launch (here: behind the prologue's barrier) and where the reset pool replaced the state of one of the
   // wavefront's environments (main_pool); lanes of an environment past n_envs carry what they stored, as they read it before.
+  // (The 256-register build pays for the carried state with 20 B of scratch: profiles/oct_step_boundary_resources.txt.)
   struct Carried { T q, qd, rq[6], rqd[6]; };
-  // TOP_EARLY: the constants of the PD block, jcalc, the root's frame and velocities — nothing writes them inside a launch: the
+  // SOLO: the constants of the PD block, jcalc, the root's frame and velocities — nothing writes them inside a launch: the
   // lane table and the scalar table (written by the prologue, in front of its barrier), kp / kd / max_force of the x record
   // (the reset pool rewrites q | qd only, the helper the action slots only) — requested by the main wavefront in main_fin and
   // held across barrier (0), whose own wait for the LDS takes them in: behind it nothing covers their round trips.  (xt: the
-  // translation of X_T; its rotation, read where X_T is not the identity only, stays where it is.)
+  // translation of X_T; its rotation, read where X_T is not the identity only, stays where it is.  The 256-register build pays
+  // for the 33 constants with 64 - 84 B of scratch: the same table.)
   struct TopConsts { T S[6], rotf, nax[3], nn[6], xt[3], ipose, stiff, damp, act_lim, xt_ident, base_t[3], grav[3], kp, kd, max_force; };
   auto carry_load = [&](const T *xr_, int lane_, Carried &c) {
     c.q = xr_[6 + lane_];
@@ -519,10 +428,13 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   Carried car = {};
   TopConsts tc = {};
-  // HELP_ARGS: the fields of the launch's control block that the helper reads in every step, whatever the launch's form — which
+  // SOLO: the fields of the launch's control block that the helper reads in every step, whatever the launch's form — which
   // rings there are, where they are, whether the step is counted in — read from the kernel-argument segment once per launch and
-  // scalars from here on (no other build refers to it).  What only an exchange launch reads (the peer table, offsets, flags,
-  // epoch) stays a read per step.  The kernel has no SGPRs to spare: the back end parks these sixteen in the lanes of a VGPR in
+  // scalars from here on (`hc`, OCT_HC; the helper's loop is its own there, and no other build refers to the copy): through the
+  // laundered segment pointer every field is a scalar load of its own in every step, and where one field decides whether the next
+  // is read (help_np, help_poses_head, help_rec) a round trip of its own that nothing covers.  What changes from step to step
+  // (ring positions, `last`) was never read from there: it follows `it`.  What only an exchange launch reads (the peer table,
+  // offsets, flags, epoch) stays a read per step.  The kernel has no SGPRs to spare: the back end parks these sixteen in the lanes of a VGPR in
   // the prologue and fetches a field with one v_readlane where a step uses it — no wait (the whole block held across the loop
   // was 40 parked SGPRs and 69 v_readlane per step; profiles/oct_root_helper_resources.txt).
   struct HelpArgs {
@@ -534,19 +446,19 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   const HelpArgs hc = {ctl_arg.act_pool, ctl_arg.obs_ring, ctl_arg.y_ring, ctl_arg.peer_arrive, ctl_arg.progress, ctl_arg.act_envs,
                        ctl_arg.obs_slots, ctl_arg.ring_envs, ctl_arg.y_stride, ctl_arg.obs_envs, ctl_arg.ring_flags};
-  if constexpr (CARRY || TOP_EARLY) {
+  if constexpr (SOLO) {
     const int lane_ = threadIdx.x & 7;
     const T *const xr_ = sm + ((threadIdx.x & 63) >> 3) * O.stride;
-    if constexpr (CARRY) carry_load(xr_, lane_, car);
-    if constexpr (TOP_EARLY) top_request(xr_, CT + lane_ * TB::LSTR, tc);
+    carry_load(xr_, lane_, car);
+    top_request(xr_, CT + lane_ * TB::LSTR, tc);
   }
   // ================================ a step: the body of the step loop ================================
-  // ROLE 2: one loop for the whole workgroup, the wavefronts part ways inside the step (`wv`).  ROLE 0 / 1 (SPLIT_LOOP): the
+  // ROLE 2: one loop for the whole workgroup, the wavefronts part ways inside the step (`wv`).  ROLE 0 / 1 (SOLO): the
   // main wavefront's / the helper's step, each in a loop of its own — see the loops behind the body.
   auto step_body = [&](auto rolec, const int it) {
   constexpr int ROLE = decltype(rolec)::value;
-  // (nothing but `it`, next_act and act_slot lives across an iteration — and, on the main wavefront of the builds that take
-  //  them, `car` and `tc` from main_fin to main_kin: lane and kernel-argument segment are laundered)
+  // (nothing but `it`, next_act and act_slot lives across an iteration — and, on the main wavefront of the SOLO build,
+  //  `car` and `tc` from main_fin to main_kin: lane and kernel-argument segment are laundered)
   const __attribute__((address_space(4))) char *ka_seg = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
   int tid = threadIdx.x;
   if constexpr (LOOP) asm volatile("" : "+s"(ka_seg), "+v"(tid));
@@ -555,7 +467,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // Two wavefronts per SIMD (BUILD 2): where a main wavefront shares its SIMD with a helper, the main one — the step's
   // instruction stream — issues first (Ant x 8192, same box: 7.93 / 8.09e8 -> 8.42 / 8.37e8 env-steps/s; no effect at one
   // wavefront per SIMD)
-  if constexpr (W2 && TDS_OCT_PRIO != 0) {
+  if constexpr (W2) {
     if (BUILD != 4 && wv == 0) __builtin_amdgcn_s_setprio(3);
     else __builtin_amdgcn_s_setprio(0);  // (a helper one step in front of a refill pass's wavefronts on its SIMD: measured, nothing)
   }
@@ -586,9 +498,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   const int dq = 6 + lane;  // my dof in the q / qd records
   const T *const CL = CT + lane * TB::LSTR;  // my lane's constants
   typename TdsCtlRef<LOOP>::type ctl = TdsCtlRef<LOOP>::get(ctl_arg, ka_seg + __builtin_offsetof(OctKernArgs, ctl));
-  // (a field of the control block as the helper's phases read it: HELP_ARGS, in the helper's own loop — the copy made in front of
+  // (a field of the control block as the helper's phases read it: SOLO, in the helper's own loop — the copy made in front of
   //  that loop; everywhere else the field itself.  The condition is a compile-time constant: one arm only is compiled)
-#define OCT_HC(f) ((HELP_ARGS && ROLE == 1) ? hc.f : ctl.f)
+#define OCT_HC(f) ((SOLO && ROLE == 1) ? hc.f : ctl.f)
   const T dt = CT[TB::SC + TB::DT];
   const int pgs_iters = (int)CT[TB::SC + TB::PGS_ITERATIONS];
   const bool last = it == nsteps - 1;
@@ -608,7 +520,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 
   // the root body's frame and the root's revolute axes from the six sines / cosines (kinematics.hpp:64-97; tds_kernels.hip
   // phase C: same formulas): R5, P, A4, A5 and the linear parts P x A of the three revolute axes (A3 = e_x)
-  // (rq, bt: the root's position and the base offset — the record and the table, or the main wavefront's registers: CARRY, TOP_EARLY)
+  // (rq, bt: the root's position and the base offset — the record and the table, or the main wavefront's registers: SOLO)
   auto root_frame = [&](const T *rq, const T *bt, T sx, T cx, T sy, T cy, T sz, T cz) {
     R5[0] = cy * cz;                 R5[1] = -cy * sz;                R5[2] = sy;
     R5[3] = sx * sy * cz + cx * sz;  R5[4] = cx * cz - sx * sy * sz;  R5[5] = -sx * cy;
@@ -619,8 +531,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     A4[0] = T(0); A4[1] = cx; A4[2] = sx;
     A5[0] = sy; A5[1] = -sx * cy; A5[2] = cx * cy;
     pA3[0] = T(0); pA3[1] = P[2]; pA3[2] = -P[1];  // P x e_x
-    if constexpr (ROOT_ZEROS) oct_cross3_b0(P, A4, pA4);
-    else cross3(P, A4, pA4);
+    oct_cross3_b0(P, A4, pA4);
     cross3(P, A5, pA5);
   };
   auto times_inertia = [&](const T *I, const T *s, T *F) {  // (I w + h x v, m v - h x w)
@@ -640,10 +551,10 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   auto main_kin = [&]() {
     // ================================ main: PD, jcalc, kinematics ================================
     OCT_MARK("main_top");
-    // (a constant of the top of the step: the register requested in front of barrier (0), TOP_EARLY, or the read at its place
+    // (a constant of the top of the step: the register requested in front of barrier (0), SOLO, or the read at its place
     //  of use — the condition is a compile-time constant: one arm only is compiled)
-#define OCT_TOP(early, read) (TOP_EARLY ? (early) : (read))
-    if constexpr (CARRY) {
+#define OCT_TOP(early, read) (SOLO ? (early) : (read))
+    if constexpr (SOLO) {
       q = car.q;
       qd = car.qd;
     } else {
@@ -676,7 +587,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     // (my root angle: lanes 0, 1, 2 the three angles, the others the first)
     auto root_angle = [&]() -> T {
-      if constexpr (CARRY) {
+      if constexpr (SOLO) {
         // (by value first: a conditional between array elements is a conditional between addresses, and `car` a record in scratch)
         const T a3 = car.rq[3], a4 = car.rq[4], a5 = car.rq[5];
         return lane == 1 ? a4 : (lane == 2 ? a5 : a3);
@@ -684,7 +595,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         return xr[3 + (lane < 3 ? lane : 0)];
       }
     };
-    T root_s = T(0), root_c = T(0);  // (SINCOS2: the root angle's sine and cosine, evaluated beside the joint's)
+    // (the root angle's sine and cosine, evaluated beside the joint's in one interleaved routine, tds_sincos2: its 17 constants in
+    //  registers once per step instead of once per inlined copy — the same bits as two tds_sincos)
+    T root_s = T(0), root_c = T(0);
     OCT_MARK("main_jcalc");
     // ---- B. jcalc (link.hpp:229-287)
 #pragma unroll
@@ -695,8 +608,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // joint's angle is multiplied by 0), t_J = S_linear q (zero for a revolute joint) — every joint type of link.hpp:229-287
       // without a branch; X_parent = X_T X_J, and where every X_T rotation is the identity (the Ant) no product at all
       T sn, cs;
-      if constexpr (SINCOS2) tds_sincos2(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), root_angle(), &sn, &cs, &root_s, &root_c);
-      else tds_sincos(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), &sn, &cs);
+      tds_sincos2(q * OCT_TOP(tc.rotf, CL[TB::ROTF]), root_angle(), &sn, &cs, &root_s, &root_c);
       const T c1 = T(1) - cs;
       const T nx = OCT_TOP(tc.nax[0], CL[TB::NAX]), ny = OCT_TOP(tc.nax[1], CL[TB::NAX + 1]), nz = OCT_TOP(tc.nax[2], CL[TB::NAX + 2]);
       T RJ[9];
@@ -729,13 +641,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     // ---- C. the root chain in closed form, on every lane.  The three root angles' sines and cosines: lanes 0, 1, 2 of the
     //         environment, broadcast (and, two-wavefront build, handed to the helper behind the links' world transforms)
     {
-      T rs, rc;
-      if constexpr (SINCOS2) {
-        rs = root_s;
-        rc = root_c;
-      } else {
-        tds_sincos(root_angle(), &rs, &rc);
-      }
+      const T rs = root_s, rc = root_c;
       const T sx = oct_bcast<0>(rs), cx = oct_bcast<0>(rc);
       const T sy = oct_bcast<1>(rs), cy = oct_bcast<1>(rc);
       const T sz = oct_bcast<2>(rs), cz = oct_bcast<2>(rc);
@@ -746,83 +652,51 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           sc[2 * lane + 1] = rc;
         }
       }
-      root_frame(CARRY ? car.rq : xr, TOP_EARLY ? tc.base_t : CT + TB::SC + TB::BASE_T, sx, cx, sy, cy, sz, cz);
+      root_frame(SOLO ? car.rq : xr, SOLO ? tc.base_t : CT + TB::SC + TB::BASE_T, sx, cx, sy, cy, sz, cz);
     }
     OCT_MARK("main_rootvel");
     {
-      const T *const rqd = CARRY ? car.rqd : xr + nq;
+      const T *const rqd = SOLO ? car.rqd : xr + nq;
       const T d0 = rqd[0], d1 = rqd[1], d2 = rqd[2], d3 = rqd[3], d4 = rqd[4], d5 = rqd[5];
       const T U[3] = {d0, d1, d2};
-      if constexpr (ROOT_ZEROS) {
-        // J3 = (d3, 0, 0), J4 = (0, cx d4, sx d4): the statements of the general form below, each without its 0 * x and 0 + x
-        const T J4[3] = {T(0), A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
-        const T W4[3] = {d3, J4[1], J4[2]};
-        const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
-        T pJ3[3], pJ4[3], pJ5[3];
-        oct_cross3_bx(P, d3, pJ3);
-        oct_cross3_b0(P, J4, pJ4);
-        cross3(P, J5, pJ5);
-        const T pW4[3] = {pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
-        const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
-        const T V3[3] = {U[0], U[1] + pJ3[1], U[2] + pJ3[2]};
-        const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
-        const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
-        T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
-        oct_cross3_ax_b0(d3, J4, a45);
-        cross3(W4, J5, a55);
-        oct_cross3_ax_b0(d3, pJ3, t1);
-        oct_cross3_bx(V3, d3, t2);
-        l3[0] = T(0); l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
-        cross3(W4, pJ4, t1);
-        oct_cross3_b0(V4, J4, t2);
-        l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
-        cross3(W5, pJ5, t1);
-        cross3(V5, J5, t2);
-        l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
+      // J3 = (d3, 0, 0), J4 = (0, cx d4, sx d4).  The general form (tds_kernels.hip phase C) — W4 = J3 + J4, pW4 = P x J3 + P x J4,
+      // V3 = U + P x J3, a45 = J3 x J4, l_k = W_k x pJ_k + V_k x J_k, a5 = (a45 + a55 | l3 + l4 + l5 - g) — statement by statement,
+      // each without its 0 * x and 0 + x
+      const T J4[3] = {T(0), A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
+      const T W4[3] = {d3, J4[1], J4[2]};
+      const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
+      T pJ3[3], pJ4[3], pJ5[3];
+      oct_cross3_bx(P, d3, pJ3);
+      oct_cross3_b0(P, J4, pJ4);
+      cross3(P, J5, pJ5);
+      const T pW4[3] = {pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
+      const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
+      const T V3[3] = {U[0], U[1] + pJ3[1], U[2] + pJ3[2]};
+      const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
+      const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
+      T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
+      oct_cross3_ax_b0(d3, J4, a45);
+      cross3(W4, J5, a55);
+      oct_cross3_ax_b0(d3, pJ3, t1);
+      oct_cross3_bx(V3, d3, t2);
+      l3[0] = T(0); l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
+      cross3(W4, pJ4, t1);
+      oct_cross3_b0(V4, J4, t2);
+      l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
+      cross3(W5, pJ5, t1);
+      cross3(V5, J5, t2);
+      l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          v5[k] = W5[k];
-          v5[3 + k] = V5[k];
-        }
-        a5[0] = a55[0];
-        a5[1] = a45[1] + a55[1];
-        a5[2] = a45[2] + a55[2];
-        a5[3] = (l4[0] + l5[0]) - OCT_TOP(tc.grav[0], CT[TB::SC + TB::GRAV + 0]);
-        a5[4] = (l3[1] + l4[1] + l5[1]) - OCT_TOP(tc.grav[1], CT[TB::SC + TB::GRAV + 1]);
-        a5[5] = (l3[2] + l4[2] + l5[2]) - OCT_TOP(tc.grav[2], CT[TB::SC + TB::GRAV + 2]);
-      } else {
-        const T J3[3] = {d3, T(0), T(0)}, J4[3] = {A4[0] * d4, A4[1] * d4, A4[2] * d4}, J5[3] = {A5[0] * d5, A5[1] * d5, A5[2] * d5};
-        const T W4[3] = {J3[0] + J4[0], J3[1] + J4[1], J3[2] + J4[2]};
-        const T W5[3] = {W4[0] + J5[0], W4[1] + J5[1], W4[2] + J5[2]};
-        T pJ3[3], pJ4[3], pJ5[3];
-        cross3(P, J3, pJ3);
-        cross3(P, J4, pJ4);
-        cross3(P, J5, pJ5);
-        const T pW4[3] = {pJ3[0] + pJ4[0], pJ3[1] + pJ4[1], pJ3[2] + pJ4[2]};
-        const T pW5[3] = {pW4[0] + pJ5[0], pW4[1] + pJ5[1], pW4[2] + pJ5[2]};
-        const T V3[3] = {U[0] + pJ3[0], U[1] + pJ3[1], U[2] + pJ3[2]};
-        const T V4[3] = {U[0] + pW4[0], U[1] + pW4[1], U[2] + pW4[2]};
-        const T V5[3] = {U[0] + pW5[0], U[1] + pW5[1], U[2] + pW5[2]};
-        T a45[3], a55[3], t1[3], t2[3], l3[3], l4[3], l5[3];
-        cross3(J3, J4, a45);
-        cross3(W4, J5, a55);
-        cross3(J3, pJ3, t1);
-        cross3(V3, J3, t2);
-        l3[0] = t1[0] + t2[0]; l3[1] = t1[1] + t2[1]; l3[2] = t1[2] + t2[2];
-        cross3(W4, pJ4, t1);
-        cross3(V4, J4, t2);
-        l4[0] = t1[0] + t2[0]; l4[1] = t1[1] + t2[1]; l4[2] = t1[2] + t2[2];
-        cross3(W5, pJ5, t1);
-        cross3(V5, J5, t2);
-        l5[0] = t1[0] + t2[0]; l5[1] = t1[1] + t2[1]; l5[2] = t1[2] + t2[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          v5[k] = W5[k];
-          v5[3 + k] = V5[k];
-          a5[k] = a45[k] + a55[k];
-          a5[3 + k] = (l3[k] + l4[k] + l5[k]) - OCT_TOP(tc.grav[k], CT[TB::SC + TB::GRAV + k]);
-        }
+      for (int k = 0; k < 3; ++k) {
+        v5[k] = W5[k];
+        v5[3 + k] = V5[k];
       }
+      a5[0] = a55[0];
+      a5[1] = a45[1] + a55[1];
+      a5[2] = a45[2] + a55[2];
+      a5[3] = (l4[0] + l5[0]) - OCT_TOP(tc.grav[0], CT[TB::SC + TB::GRAV + 0]);
+      a5[4] = (l3[1] + l4[1] + l5[1]) - OCT_TOP(tc.grav[1], CT[TB::SC + TB::GRAV + 1]);
+      a5[5] = (l3[2] + l4[2] + l5[2]) - OCT_TOP(tc.grav[2], CT[TB::SC + TB::GRAV + 2]);
     }
 #undef OCT_TOP
     OCT_MARK("main_legs");
@@ -1017,8 +891,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     OCT_STAMP(8, na);
   };
-  // (two halves: POSES_LATE takes them apart — the head stays between barriers (1b) and (2), the tail goes behind the helper's
-  //  last row window; everywhere else help_poses runs them back to back)
+  // (two halves: SOLO takes them apart — the head stays between barriers (1b) and (2), the tail goes behind the helper's last
+  //  row window, into its idle tail in front of barrier (0): in one piece the helper idled ~2 k cycles there and was yet the late
+  //  one at barrier (2), behind the visual poses; everywhere else help_poses runs them back to back)
   auto help_poses_head = [&]() {
     OCT_MARK("help_signal_poses");
     if constexpr (LOOP) {
@@ -1029,17 +904,17 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       // nothing here, in front of this step's first stores — are counted in
       if (it > 0 && OCT_HC(obs_ring) != nullptr) {  // (wave-uniform)
         if (OCT_HC(peer_arrive) != nullptr) tds_peer_finish(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1, sig_tok);
-        // (HELP_ARGS: this guard MIRRORS tds_signal_slot's own check — tds_step_shared.h: without the peer form it acts where there
+        // (SOLO: this guard MIRRORS tds_signal_slot's own check — tds_step_shared.h: without the peer form it acts where there
         //  is a progress counter only — so that a launch without one does not read the two fields per step.  Keep the two in
         //  step: a form added to tds_signal_slot must be added here, or this guard skips it)
-        else if (!(HELP_ARGS && ROLE == 1) || hc.progress != nullptr) tds_signal_slot(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1);
+        else if (!(SOLO && ROLE == 1) || hc.progress != nullptr) tds_signal_slot(ctl, (o_slot == 0 ? OCT_HC(obs_slots) : o_slot) - 1);
       }
     }
   };
   auto help_poses_tail = [&]() {
-    // (POSES_LATE: R, p, R5, P are the helper's registers since help_np — the hand-over slots they came from are row slots of
+    // (SOLO: R, p, R5, P are the helper's registers since help_np — the hand-over slots they came from are row slots of
     //  the later windows by now; the pose slots of the y record are nobody else's: main_pool and help_rec store the state part)
-    if constexpr (POSES_LATE) OCT_MARK("help_poses_late");
+    if constexpr (SOLO) OCT_MARK("help_poses_late");
     // ---- M1. visual poses of y, from the PRE-step X_world (locomotion_contact_simulation.h:281-299): visual 1 + lane is
     //          my link's (DevModel::oct checks the order); visual 0 — the root body's — goes out on lane 7
     TR *yo, *yo2;
@@ -1054,22 +929,22 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         mat3_mulv(Rl, vx + 9, po);
         matrix_to_quat(Ro, qo);
         TR *o = yo + (nq + nd) + 7 * k;
-        OCT_ST((TR)(pl[0] + po[0]), &o[0]);
-        OCT_ST((TR)(pl[1] + po[1]), &o[1]);
-        OCT_ST((TR)(pl[2] + po[2]), &o[2]);
-        OCT_ST((TR)qo[0], &o[3]);
-        OCT_ST((TR)qo[1], &o[4]);
-        OCT_ST((TR)qo[2], &o[5]);
-        OCT_ST((TR)qo[3], &o[6]);
+        o[0] = (TR)(pl[0] + po[0]);
+        o[1] = (TR)(pl[1] + po[1]);
+        o[2] = (TR)(pl[2] + po[2]);
+        o[3] = (TR)qo[0];
+        o[4] = (TR)qo[1];
+        o[5] = (TR)qo[2];
+        o[6] = (TR)qo[3];
         if (yo2 != nullptr) {
           TR *o2 = yo2 + (nq + nd) + 7 * k;
-          OCT_ST((TR)(pl[0] + po[0]), &o2[0]);
-          OCT_ST((TR)(pl[1] + po[1]), &o2[1]);
-          OCT_ST((TR)(pl[2] + po[2]), &o2[2]);
-          OCT_ST((TR)qo[0], &o2[3]);
-          OCT_ST((TR)qo[1], &o2[4]);
-          OCT_ST((TR)qo[2], &o2[5]);
-          OCT_ST((TR)qo[3], &o2[6]);
+          o2[0] = (TR)(pl[0] + po[0]);
+          o2[1] = (TR)(pl[1] + po[1]);
+          o2[2] = (TR)(pl[2] + po[2]);
+          o2[3] = (TR)qo[0];
+          o2[4] = (TR)qo[1];
+          o2[5] = (TR)qo[2];
+          o2[6] = (TR)qo[3];
         }
       };
       pose_out(R, p, CL + TB::VIS, 1 + lane);
@@ -1143,19 +1018,22 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_MARK("main_rigid");
     T Ic[10], fc[6];
     rigid(R, p, CL[TB::MASS], CL + TB::COM, CL + TB::INER, v, a0, Ic, fc);
-    T ft[6];  // (It, ft) the root body's; below: + the legs' = the whole robot's
+    // (It, ft) the root body's; below: + the legs' = the whole robot's.  (On the helper, handed over at (1b), it was measured
+    //  and not kept — as was the root body's visual pose in the helper's wait at (2): tools/experiments/oct_root_helper_not_kept.txt)
+    T ft[6];
     rigid(R5, P, CT[TB::ROOT + TB::R_MASS], CT + TB::ROOT + TB::R_COM, CT + TB::ROOT + TB::R_INER, v5, a5, It, ft);
     OCT_STAMP(2, ft[5]);
     OCT_MARK("main_totals");
     // ---- E. composite inertia / bias force (CRBA, mass_matrix.hpp:39-56): the robot's totals = root + every leg link
     //         (8-lane sums of the rigid values: every lane the same bits); the hip's composite = hip + ankle
-    // (Ic[6 .. 8] = m cw are products: pinned.  The others are sums — Ic[0 .. 5], fc — or a table value, Ic[9])
+    // (Ic[6 .. 8] = m cw are products: pinned.  The others are sums — Ic[0 .. 5], fc — or a table value, Ic[9]: summed without
+    //  oct_sum's pinning copy)
     static_for<0, 10>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
-      It[k] += oct_sum<!(TDS_OCT_TOTALS_NOPIN != 0) || (k >= 6 && k <= 8)>(Ic[k]);
+      It[k] += oct_sum<(k >= 6 && k <= 8)>(Ic[k]);
     });
 #pragma unroll
-    for (int k = 0; k < 6; ++k) ft[k] += oct_sum<!(TDS_OCT_TOTALS_NOPIN != 0)>(fc[k]);
+    for (int k = 0; k < 6; ++k) ft[k] += oct_sum<false>(fc[k]);
     {
       const T recv = pos == 0 ? T(1) : T(0);
 #pragma unroll
@@ -1168,19 +1046,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     T Fc[6];
     times_inertia(Ic, sw, Fc);
     Cb = dot6(sw, fc);
-    // the root's revolute axes as (angular | linear); the prismatic ones are (0 | e_k)
-    const T ax3[6] = {T(1), T(0), T(0), pA3[0], pA3[1], pA3[2]}, ax4[6] = {A4[0], A4[1], A4[2], pA4[0], pA4[1], pA4[2]},
-            ax5[6] = {A5[0], A5[1], A5[2], pA5[0], pA5[1], pA5[2]};
+    // the root's revolute axes as (angular | linear): ax3 = (1, 0, 0 | 0, pA3[1], pA3[2]) and ax4 = (0, A4[1], A4[2] | pA4) are
+    // written out term by term, without their zeros; the prismatic ones are (0 | e_k)
+    const T ax5[6] = {A5[0], A5[1], A5[2], pA5[0], pA5[1], pA5[2]};
     Cr[0] = ft[3];  // bias forces of the root dofs
     Cr[1] = ft[4];
     Cr[2] = ft[5];
-    if constexpr (ROOT_ZEROS) {  // (ax3 = (1, 0, 0 | 0, pA3[1], pA3[2]), ax4 = (0, A4[1], A4[2] | pA4))
-      Cr[3] = ft[0] + oct_dot3_0(pA3, ft + 3);
-      Cr[4] = oct_dot3_0(A4, ft) + dot3(pA4, ft + 3);
-    } else {
-      Cr[3] = dot6(ax3, ft);
-      Cr[4] = dot6(ax4, ft);
-    }
+    Cr[3] = ft[0] + oct_dot3_0(pA3, ft + 3);
+    Cr[4] = oct_dot3_0(A4, ft) + dot3(pA4, ft + 3);
     Cr[5] = dot6(ax5, ft);
     // ---- G. M in leaves-first order.  My row of my leg's 2 x 2 block (M[i][j] = F_i . s_j for j an ancestor of i or i,
     //         mass_matrix.hpp:87-109) and my coupling to the root dofs
@@ -1194,13 +1067,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       Cc[0] = Fc[3];
       Cc[1] = Fc[4];
       Cc[2] = Fc[5];
-      if constexpr (ROOT_ZEROS) {
-        Cc[3] = Fc[0] + oct_dot3_0(Fc + 3, pA3);
-        Cc[4] = oct_dot3_0(Fc, A4) + dot3(Fc + 3, pA4);
-      } else {
-        Cc[3] = dot6(Fc, ax3);
-        Cc[4] = dot6(Fc, ax4);
-      }
+      Cc[3] = Fc[0] + oct_dot3_0(Fc + 3, pA3);
+      Cc[4] = oct_dot3_0(Fc, A4) + dot3(Fc + 3, pA4);
       Cc[5] = dot6(Fc, ax5);
     }
     OCT_MARK("main_legldl");
@@ -1243,10 +1111,14 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     }
     OCT_STAMP(3, Lc[5]);
   };
-  // HELP_SCHUR: the Schur sums by the helper, directly behind barrier (1b): L_c (O.lcw) and W (O.xs) are in LDS there, and the
+  // SOLO: the Schur sums by the helper, directly behind barrier (1b): L_c (O.lcw) and W (O.xs) are in LDS there, and the
   // sums pass through LDS (O.fac) on their way to the 6 x 6 LDL^T anyway.  main_dyn2's table, passes and FMA chains, term by
   // term; the helper has nothing to put across a pass's round trip, so the 48 operands of the three passes are requested in one
-  // batch (pass by pass the listing showed 13 exposed round trips; the helper has the registers: see the resource table).
+  // batch (pass by pass the listing showed 13 exposed round trips).  The other builds sum on the main wavefront, in main_dyn2:
+  // batched operands cost build 2 scratch (16-32 B) and the straight-line form of build 3 two more registers, and the
+  // one-wavefront build plays both roles in one stream — nothing waits for its main part (profiles/oct_kernel_resources_lds.txt).
+  // (The head of the forward dynamics in front of (1c) as well was measured and lost:
+  //  tools/experiments/oct_helper_schur_not_kept.txt.)
   auto help_schur = [&]() {
     OCT_MARK("help_schur");
     const T *const lcw = E + O.lcw;
@@ -1279,132 +1151,67 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
   auto main_dyn2 = [&]() {
     OCT_MARK("main_schur");
-    const T ax3[6] = {T(1), T(0), T(0), pA3[0], pA3[1], pA3[2]}, ax4[6] = {A4[0], A4[1], A4[2], pA4[0], pA4[1], pA4[2]},
-            ax5[6] = {A5[0], A5[1], A5[2], pA5[0], pA5[1], pA5[2]};
+    // (ax3 = (1, 0, 0 | 0, pA3[1], pA3[2]) is written out term by term, without its zeros; of ax4 = (0, A4[1], A4[2] | pA4) the
+    //  zero is never read)
+    const T ax4[6] = {A4[0], A4[1], A4[2], pA4[0], pA4[1], pA4[2]}, ax5[6] = {A5[0], A5[1], A5[2], pA5[0], pA5[1], pA5[2]};
     T Sm[21];
     // the root block R[r][r'] = s_r . (It s_r') in registers (packed lower triangle, r (r + 1) / 2 + r'): the prismatic
-    // axes are unit vectors, It e_k = (h x e_k | m e_k).  In three parts, one per revolute axis (the first with the prismatic rows)
-    T F3[6], F4[6];
-    auto root_block_a1 = [&]() {
+    // axes are unit vectors, It e_k = (h x e_k | m e_k); then the rows of the three revolute axes
+    auto root_block = [&]() {
+      T F3[6], F4[6], F5[6];
       const T m = It[9];
-      // (ROOT_ZEROS: F3[3] = m * 0 - 0 is a structural zero of its own, in the three dot products below as well)
-      if constexpr (ROOT_ZEROS) oct_times_inertia_ex(It, pA3, F3);
-      else times_inertia(It, ax3, F3);
+      oct_times_inertia_ex(It, pA3, F3);  // (F3[3] = m * 0 - 0 is a structural zero of its own, in the dot products below as well)
       Sm[0] = m;
       Sm[1] = T(0); Sm[2] = m;
       Sm[3] = T(0); Sm[4] = T(0); Sm[5] = m;
       Sm[6] = F3[3]; Sm[7] = F3[4]; Sm[8] = F3[5];
-      if constexpr (ROOT_ZEROS) Sm[9] = F3[0] + oct_dot3_0(pA3, F3 + 3);
-      else Sm[9] = dot6(ax3, F3);
-    };
-    auto root_block_a2 = [&]() {
-      if constexpr (ROOT_ZEROS) oct_times_inertia_0(It, ax4, F4);
-      else times_inertia(It, ax4, F4);
+      Sm[9] = F3[0] + oct_dot3_0(pA3, F3 + 3);
+      oct_times_inertia_0(It, ax4, F4);
       Sm[10] = F4[3]; Sm[11] = F4[4]; Sm[12] = F4[5];
-      if constexpr (ROOT_ZEROS) {
-        Sm[13] = oct_dot3_0(A4, F3) + oct_dot3_0(pA4, F3 + 3);
-        Sm[14] = oct_dot3_0(A4, F4) + dot3(pA4, F4 + 3);
-      } else {
-        Sm[13] = dot6(ax4, F3);
-        Sm[14] = dot6(ax4, F4);
-      }
-    };
-    auto root_block_b = [&]() {
-      T F5[6];
+      Sm[13] = oct_dot3_0(A4, F3) + oct_dot3_0(pA4, F3 + 3);
+      Sm[14] = oct_dot3_0(A4, F4) + dot3(pA4, F4 + 3);
       times_inertia(It, ax5, F5);
       Sm[15] = F5[3]; Sm[16] = F5[4]; Sm[17] = F5[5];
-      if constexpr (ROOT_ZEROS) Sm[18] = dot3(A5, F3) + oct_dot3_0(pA5, F3 + 3);
-      else Sm[18] = dot6(ax5, F3);
+      Sm[18] = dot3(A5, F3) + oct_dot3_0(pA5, F3 + 3);
       Sm[19] = dot6(ax5, F4); Sm[20] = dot6(ax5, F5);
     };
     // the sums sum_lanes L_c[r] W[r'] of the Schur complement, entry e = r (r + 1) / 2 + r' on lane e mod 8 (three passes)
-    if constexpr (HELP_SCHUR) {
+    if constexpr (SOLO) {
       // The helper sums (help_schur) while this wavefront does what needs no sum: the root block straight through; barrier (1c):
       // the 21 sums are in O.fac.  Both wavefronts take it once per step, unconditionally.
       // (fences: left to itself the back end moves the root block — arithmetic on registers — up in front of barrier (1b), where
       //  the helper, early there, would wait for it instead of summing beside it; and nothing is to slide behind (1c))
       __builtin_amdgcn_sched_barrier(0);
-      root_block_a1();
-      root_block_a2();
-      root_block_b();
+      root_block();
       __builtin_amdgcn_sched_barrier(0);
       OCT_MARK("main_wait_schur");
       OCT_BAR_T(36);  // (1c)
     } else {
+      // (the other builds: this wavefront sums, then computes the root block — why: at help_schur)
       const T *const lcw = E + O.lcw;
       const T *const wl = E + O.xs;  // (W = L_c D in the impulses' slots: every read of it stands here, behind barrier (1b) and in
                                      //  front of barrier (2), in either order of the reads; the sweep's impulses come behind (2))
       T *const Ssum = E + O.fac;
       const int code = (int)CL[TB::SCHUR];  // (which entries this lane sums: table)
-      if constexpr (BATCH_SCHUR) {
-        // A pass's 16 operands are requested in one batch and a third of the root block — f64 arithmetic that depends on no
-        // LDS value: the rows of one revolute axis — runs while they arrive.  In the loop below a pass's reads were three
-        // exposed round trips, and the root block sat behind the last pass, where it covered nothing.  (Two passes' operands
-        // at once, or all three, cost the one-wavefront-per-SIMD build 28 / 72 accumulation registers' worth of copies and
-        // the other build scratch.)  The three FMA chains are those of the loop below, term by term.
-        T la[3][8], wa[3][8];
-        int ee[3];
-        auto ask = [&](auto pc) {
-          constexpr int pass = decltype(pc)::value;
-          const int rc = (code >> (6 * pass)) & 63;
-          const int r = rc >> 3, rp = rc & 7;
-          ee[pass] = (r * (r + 1)) / 2 + rp;
 #pragma unroll
-          for (int l = 0; l < 8; ++l) {
-            la[pass][l] = lcw[l * OctLds::LCW + r];
-            wa[pass][l] = wl[l * 6 + rp];
-          }
-        };
-        auto sum = [&](auto pc) {
-          constexpr int pass = decltype(pc)::value;
-          T acc = T(0);
+      for (int pass = 0; pass < 3; ++pass) {
+        const int rc = (code >> (6 * pass)) & 63;
+        const int r = rc >> 3, rp = rc & 7;
+        const int e = (r * (r + 1)) / 2 + rp;
+        T acc = T(0);
 #pragma unroll
-          for (int l = 0; l < 8; ++l) acc += la[pass][l] * wa[pass][l];
-          Ssum[ee[pass]] = acc;
-        };
-        // (fences stand where arithmetic must not slide in front of a request or behind its sums.  None separates sum(p)
-        //  from ask(p + 1): both sit between two fences, the back end issues the eight reads first because they have no
-        //  operand to wait for — tools/oct_isa_phases.py's exposed-wait column shows it if that ever changes)
-        ask(std::integral_constant<int, 0>{});
-        __builtin_amdgcn_sched_barrier(0);
-        root_block_a1();
-        __builtin_amdgcn_sched_barrier(0);
-        sum(std::integral_constant<int, 0>{});
-        ask(std::integral_constant<int, 1>{});
-        __builtin_amdgcn_sched_barrier(0);
-        root_block_a2();
-        __builtin_amdgcn_sched_barrier(0);
-        sum(std::integral_constant<int, 1>{});
-        ask(std::integral_constant<int, 2>{});
-        __builtin_amdgcn_sched_barrier(0);
-        root_block_b();
-        __builtin_amdgcn_sched_barrier(0);
-        sum(std::integral_constant<int, 2>{});
-      } else {
-#pragma unroll
-        for (int pass = 0; pass < 3; ++pass) {
-          const int rc = (code >> (6 * pass)) & 63;
-          const int r = rc >> 3, rp = rc & 7;
-          const int e = (r * (r + 1)) / 2 + rp;
-          T acc = T(0);
-#pragma unroll
-          for (int l = 0; l < 8; ++l) acc += lcw[l * OctLds::LCW + r] * wl[l * 6 + rp];
-          Ssum[e] = acc;
-        }
+        for (int l = 0; l < 8; ++l) acc += lcw[l * OctLds::LCW + r] * wl[l * 6 + rp];
+        Ssum[e] = acc;
       }
     }
     OCT_MARK("main_Rblock");
-    if constexpr (!BATCH_SCHUR) {
-      root_block_a1();
-      root_block_a2();
-      root_block_b();
-    }
+    if constexpr (!SOLO) root_block();
     OCT_SYNC();  // (the sums of every lane are in LDS, in front of any lane's read of them: a wavefront's LDS operations execute in order)
     OCT_MARK("main_ldl6");
     // ... the Schur complement, factorised redundantly on every lane: Ls (strictly lower, row-major packed), 1 / D
     {
       const T *const Ssum = E + O.fac;
-      if constexpr (BATCH_SCHUR) {
+      if constexpr (SOLO) {
         // (the 21 sums requested in one batch: one round trip, not one per pair of them)
         T ss[21];
 #pragma unroll
@@ -1519,7 +1326,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   // The row's entries of z~ pass from stage to stage in registers (RowRegs), and a slot of the row in LDS is written once, with
   // its final value.  The first window's rows wait for the root block's factors across the visual poses: parked in their own
   // slots of the row (rows_park) and read back in FRONT of barrier (2) (rows_fetch) — behind it the helper reads nothing
-  // but the factors.  (POSES_LATE builds: the poses stand behind the last window, and the first window's rows stay in registers.)
+  // but the factors.  (SOLO: the poses stand behind the last window, and the first window's rows stay in registers.)
   struct RowRegs {
     T z0, z1, zr[6];
     int hl;
@@ -1543,15 +1350,18 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       const T owner = cpx[4 * OctLds::NCP + ac];
       const T *const dir = CT + TB::SC + TB::NB + 3 * tk;
       const T e[3] = {dir[0], dir[1], dir[2]};
-      T rv[6] = {}, c_rest = T(0), c_erp = T(0);  // (GEOM_BATCH: the root's velocities and the two constants, with the first batch)
-      if constexpr (GEOM_BATCH) {
+      // (SOLO: two batches, one per dependent round trip, a scheduling fence behind each — everything that needs no other read
+      //  first: the above, the root's velocities, the two constants; then what the owner decides: the leg's axes and velocities.
+      //  Left to itself the back end spreads the reads over the arithmetic with a wait in front of every use)
+      T rv[6] = {}, c_rest = T(0), c_erp = T(0);
+      if constexpr (SOLO) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) rv[k] = xr[nq + k];
         c_rest = CT[TB::SC + TB::RESTITUTION];
         c_erp = CT[TB::SC + TB::ERP_OVER_DT];
         __builtin_amdgcn_sched_barrier(0);
       }
-#define OCT_GEOM(early, read) (GEOM_BATCH ? (early) : (read))
+#define OCT_GEOM(early, read) (SOLO ? (early) : (read))
       const int ol = real ? (int)owner : 8;    // owner lane; 8: the root body
       const bool on_leg = ol < 8;
       const int hl = on_leg ? (ol & ~1) : 0;   // the hip lane of the contact's leg
@@ -1563,7 +1373,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         sa[c] = swl[(hl + 1) * 6 + c];
       }
       const T qh = xr[nq + 6 + hl], qa = xr[nq + 6 + hl + 1];  // velocities before the step
-      if constexpr (GEOM_BATCH) __builtin_amdgcn_sched_barrier(0);
+      if constexpr (SOLO) __builtin_amdgcn_sched_barrier(0);
       // column of the point Jacobian along e: e . s_lin + P . (e x s_ang) = e . s_lin + (P x e) . s_ang  (jacobian.hpp:56-72)
       T mo[3];
       cross3(Pc, e, mo);
@@ -1676,8 +1486,8 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   //      the first: the same immediate offsets off the same bases — instead of returning to the window loop for a window of
   //      one to four rows.  They are second-tangent rows (8 >= 2 NA): the friction arm with xs2 only.  The second window's
   //      barrier is taken in position 7, in front of the request for position 8's operands.
-  //      SWEEP_NA (NAC = 1 .. 4; the first iteration's sweep from position 0 where it covers all 3 NA rows — one window, or the
-  //      long window): NA is a template constant, the rows are straight-line — every row's kind static, no compare, no branch —,
+  //      SOLO, NAC = 1 .. 4 (run-time option oct_sweep_na, default 1; the first iteration's sweep from position 0 where it
+  //      covers all 3 NA rows — one window, or the long window): NA is a template constant, the rows are straight-line — every row's kind static, no compare, no branch —,
   //      and the normal rows' clamped impulses stay in registers for their friction rows (the stores xw[k] stay: later
   //      iterations read them): no address select, no read, no canonicalising maximum, no wait for the LDS behind the sum.
   //      The long window's second barrier stands where it stands in the generic chain: position 7, in front of position 8's
@@ -1861,10 +1671,10 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       qn0 = qn_root[0];
       qn2 = qn_root[2];
       qo0 = q_old0;
-      // (TOP_EARLY: the next step's constants, behind the integration's own reads — nothing waits for them in front of barrier
+      // (SOLO: the next step's constants, behind the integration's own reads — nothing waits for them in front of barrier
       //  (0), whose wait for the LDS completes them; the prologue's barrier ordered the tables' and the record's writes, and
       //  nothing writes these slots inside a launch)
-      if constexpr (TOP_EARLY) top_request(xr, CL, tc);
+      if constexpr (SOLO) top_request(xr, CL, tc);
       OCT_SYNC();
       if (lane == 0) {
 #pragma unroll
@@ -1876,7 +1686,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       const T q_new = q + qd_new * dt;
       xr[dq] = q_new;
       xr[nq + dq] = qd_new;
-      if constexpr (CARRY) {  // (the stores above stay: the helper's records, the rows and the next launch read the record)
+      if constexpr (SOLO) {  // (the stores above stay: the helper's records, the rows and the next launch read the record)
         car.q = q_new;
         car.qd = qd_new;
 #pragma unroll
@@ -1927,6 +1737,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
     OCT_SYNC();
   };
   // the state part of a y record — q | qd | (visual poses: M1) | up.z | zero padding — from the LDS record
+  // (record stores are plain stores: as non-temporal stores they changed nothing, tools/experiments/r06_not_kept.txt)
   auto y_state = [&](TR *y, int end) {
     {  // (the reads in one batch in front of the stores: as a loop of read -> store every value was an LDS round trip of its own)
       constexpr int NB = (nq + nd + 7) / 8;
@@ -1935,15 +1746,15 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       for (int k = 0; k < NB; ++k) sv[k] = xr[lane + 8 * k < nq + nd ? lane + 8 * k : 0];
 #pragma unroll
       for (int k = 0; k < NB; ++k)
-        if (lane + 8 * k < nq + nd) OCT_ST((TR)sv[k], &y[lane + 8 * k]);
+        if (lane + 8 * k < nq + nd) y[lane + 8 * k] = (TR)sv[k];
     }
     int tail = nq + nd;
     if ((int)CT[TB::SC + TB::PACK_VISUALS]) {
       tail += 7 * nv;
-      if (lane == 0) OCT_ST((TR)(CT[TB::SC + TB::BASE_R8]), &y[tail]);  // up_dot_world_z (fixed base)
+      if (lane == 0) y[tail] = (TR)(CT[TB::SC + TB::BASE_R8]);  // up_dot_world_z (fixed base)
       tail += 1;
     }
-    for (int i = tail + lane; i < end; i += 8) OCT_ST(TR(0), &y[i]);
+    for (int i = tail + lane; i < end; i += 8) y[i] = TR(0);
   };
   auto main_pool = [&]() {
     OCT_MARK("main_pool");
@@ -1973,7 +1784,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         xr[in_dim + 3] = T(1);
       }
     }
-    if constexpr (CARRY) {
+    if constexpr (SOLO) {
       // (the carried state of a replaced environment is the terminal step's: where any environment of the wavefront was replaced —
       //  wave-uniform, rare — every lane takes its state from the record again; the others read back what they stored)
       if (ctl.pool != nullptr && __any(replaced)) {
@@ -2080,11 +1891,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
             if (rf & TDS_RING_OBS_F32) {
               float *const pp = tds_global((float *)OCT_HC(obs_ring)) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (float)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              else OCT_ST((float)vv, pp);
+              else *pp = (float)vv;
             } else {
               TR *const pp = tds_global((TR *)OCT_HC(obs_ring)) + at + i;
               if (rf & TDS_RING_NOFENCE) __hip_atomic_store(pp, (TR)vv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              else OCT_ST((TR)vv, pp);
+              else *pp = (TR)vv;
             }
             if (np > 0 && (i >= nq + nd || !rd_only)) {
               for (int pr = 0; pr < np; ++pr) {
@@ -2116,12 +1927,26 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
   };
 
   // ================================ the step ================================
-  // barriers of a two-wavefront workgroup: (1) the kinematics are in LDS; (1b) the leg blocks' factors and couplings; (1c,
-  // HELP_SCHUR builds only) the helper's 21 Schur sums; (2) the
-  // root block's factors (main wavefront), the contact list and counts (helper); one per row window (window wi is in LDS: the
-  // helper stays a window ahead of the sweep); (0) the
-  // step's state, reward and done are in the LDS record — the helper stores the step's records while the main wavefront
-  // starts the next step (it does not write the record before its own integration, two barriers on)
+  // Barriers of a two-wavefront workgroup, and who does what between them (main | helper):
+  //   (0)  the step's state, reward and done are in the LDS record.
+  //        PD, jcalc, kinematics (main_kin) | the records of the step before (help_rec: the main wavefront does not write the
+  //        record before its own integration)
+  //   (1)  the kinematics are in LDS.
+  //        inertias, leg LDL^T, couplings (main_dyn) | narrowphase, the first window's geometry (help_np, rows_geom)
+  //   (1b) the leg blocks' factors and couplings are in LDS.
+  //        SOLO:   the root block in registers | the 21 Schur sums (help_schur)
+  //          (1c)  the sums are in O.fac.
+  //                the 6 x 6 LDL^T | the first window's leg stage; the next action, the exchange's count (help_poses_head)
+  //        others: the Schur sums, the root block, the 6 x 6 LDL^T (main_dyn2) | the first window's leg stage, its rows parked
+  //                in LDS across help_poses_head and the visual poses (help_poses)
+  //   (2)  the root block's factors (main wavefront), the contact list and counts (helper) are in LDS.
+  //        forward dynamics, then the sweep | the row windows, a window ahead of the sweep — a barrier per window (window wi is
+  //        in LDS)
+  //        integration, reward, reset pool (main_fin, main_pool) | SOLO: the visual poses (help_poses_tail); others: idle
+  // LDS between (1b) and (2), SOLO: W (O.xs) is read by the helper only, in front of (1c) — the sweep's first impulse is written
+  // behind the first window barrier; O.fac is written by the helper in front of (1c), read by every main lane behind it, then
+  // overwritten by main lane 0 with the factors (behind an OCT_SYNC: every lane's reads are done) and read by the helper behind
+  // (2); the helper's next write to it is behind (1b) of the next step.
   if constexpr (W2) {
     if (wv == 0) {
       main_kin();
@@ -2147,13 +1972,16 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
           OCT_BAR_W(30, (pit | w0) == 0);
           if ((pit | w0) == 0) OCT_STAMP(12, tid);
           if (pit == 0) {
-            // (SWEEP_NA: wave-uniform; tds_oct_sweep_na: the sweep that starts here covers every row of the iteration and takes
-            //  the barriers the generic chain takes — none inside for one window, the long window's one in position 7)
-            if (SWEEP_NA && tds_oct_sweep_na(NA, w0, nw, ctl.flags & TDS_CTL_OCT_SWEEP_NA)) {
-              if (NA == 1) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 1 : 0>{}, 0, 0, false);
-              else if (NA == 2) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 2 : 0>{}, 0, 0, false);
-              else if (NA == 3) main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 3 : 0>{}, 0, 0, true);
-              else main_sweep(std::true_type{}, std::integral_constant<int, SWEEP_NA ? 4 : 0>{}, 0, 0, true);
+            // (SOLO: the sweep specialised for NA = 1 .. 4 — wave-uniform; tds_oct_sweep_na: the sweep that starts here covers every
+            //  row of the iteration and takes the barriers the generic chain takes — none inside for one window, the long window's
+            //  one in position 7.  The other builds do not instantiate the four)
+            if (SOLO && tds_oct_sweep_na(NA, w0, nw, ctl.flags & TDS_CTL_OCT_SWEEP_NA)) {
+              if constexpr (SOLO) {
+                if (NA == 1) main_sweep(std::true_type{}, std::integral_constant<int, 1>{}, 0, 0, false);
+                else if (NA == 2) main_sweep(std::true_type{}, std::integral_constant<int, 2>{}, 0, 0, false);
+                else if (NA == 3) main_sweep(std::true_type{}, std::integral_constant<int, 3>{}, 0, 0, true);
+                else main_sweep(std::true_type{}, std::integral_constant<int, 4>{}, 0, 0, true);
+              }
             } else {
               main_sweep(std::true_type{}, std::integral_constant<int, 0>{}, w0, bo, nw == 2);
             }
@@ -2175,11 +2003,9 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
       RowRegs rw = {};
       if (NA > 0) rows_geom(0, 0, rw);
       OCT_BAR_T(42);  // (1b)
-      if constexpr (HELP_SCHUR) {
+      if constexpr (SOLO) {
         help_schur();
         OCT_BAR_T(52);  // (1c): once per step, whatever NA, pgs_iters, valid and last are — as the main wavefront's in main_dyn2
-      }
-      if constexpr (POSES_LATE) {
         // (nothing stands between the first window's leg stage and its root stage but the barrier: the rows stay in registers)
         if (NA > 0) rows_leg(0, rw);
         help_poses_head();
@@ -2212,7 +2038,7 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
         }
       }
       // (behind the last row window, or right behind (2) where a step has none: the helper's idle tail)
-      if constexpr (POSES_LATE) help_poses_tail();
+      if constexpr (SOLO) help_poses_tail();
       OCT_BAR_T(50);  // (0)
       help_rec();
     }
@@ -2276,11 +2102,11 @@ __device__ __forceinline__ void oct_body(const DevModel<T> *__restrict__ mdl_arg
 #undef OCT_HC
   };  // ================================ end of a step ================================
   // ================================ step loop ================================
-  // SPLIT_LOOP: each wavefront of the workgroup in a loop of its own.  What the main wavefront carries from one step into the
+  // SOLO: each wavefront of the workgroup in a loop of its own.  What the main wavefront carries from one step into the
   // next (`car`, `tc`) is a loop-carried value of ITS loop alone: in the one loop both wavefronts pass through the loop's
   // header, the helper's path had to define the values as well, and the register allocation joined the two paths' registers
   // with up to 140 moves per step at the bottom of the loop (profiles/oct_step_boundary_resources.txt).
-  if constexpr (SPLIT_LOOP) {
+  if constexpr (SOLO) {
     if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0) {
       for (int it = 0; it < nsteps; ++it) step_body(std::integral_constant<int, 0>{}, it);
     } else {

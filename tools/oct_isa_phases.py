@@ -12,7 +12,7 @@ LDS latency it has nothing to cover with (~70 cycles per dependent read).  Two c
 
 usage: tools/oct_isa_phases.py [kernel substring, default IddLb1ELi3 = f64 step-loop two-wavefront build]
                                [--phases profiles/oct_lds_before.txt] [--src other/tds_oct.hip]
-                               [--define TDS_OCT_CARRY=0 ...] [--asm marks.s: an assembly compiled before, not compiled here]"""
+                               [--define NAME=VALUE ...: further -D flags of an experiment build] [--asm marks.s: an assembly compiled before, not compiled here]"""
 import argparse
 import collections
 import os
