@@ -1026,6 +1026,56 @@ int tds_hip_feedback_rollout_host(const tds_model_t *model, int rows, int T, int
                                   const double *s_nom, const double *u_nom, const double *k, const double *K,
                                   const double *alpha, const int32_t *problem_of_row, double *s_out, double *u_out);
 
+/* Batched iLQR under control limits (box-DDP: Tassa, Mansard, Todorov, ICRA 2014), part 1: the backward pass of
+   tds_hip_lqr_backward with bounds dlo <= dhi [n][T][nu] on the step k_t (lo - u_nom, hi - u_nom of the nominal controls;
+   +-inf where a control has no limit).  Products, Q_x .. Q_uu, the V update, dv and the symmetrisation are the plain
+   pass's; in place of the unconstrained solve, step t solves
+       min_x  f(x) = x^T H x / 2 + q^T x   over dlo <= x <= dhi,     H = Q_uu + mu I,  q = Q_u
+   by projected Newton from x = clamp(k_{t+1}, dlo, dhi) (clamp(0) at t = T-1).  For i = 1 .. 100:
+     1. g = q + H x; control a is CLAMPED if (x_a == dlo_a and g_a > 0) or (x_a == dhi_a and g_a < 0), otherwise FREE
+     2. no control free: stop
+     3. first iteration, or the clamped set changed: H_ff = L L^T, as the Cholesky of H with the clamped rows and columns
+        replaced by the identity's (a pivot that is not positive: status t + 1, as in the plain pass)
+     4. |g_f|_2 < 1e-8: stop
+     5. y_c = x_c, y_f = -H_ff^-1 (q_f + H_fc x_c); sd = (y - x)^T g; sd >= 0: stop
+     6. line search: the candidate at step 1 is clamp(y) itself, at step < 1 clamp(x + step (y - x)); the first with
+        (f(cand) - f(x)) / (step sd) >= 0.1 is taken, else step *= 0.6; step < 1e-22: stop and keep x
+     7. x = cand
+   then k_t = x, and K_t = -H_ff^-1 Q_ux,f on the free rows of the last factorisation's set, zero on its clamped rows,
+   zero everywhere if the loop stopped with nothing free.  V and dv use the unregularised Q_uu, as in the plain pass.
+   The constants (100, 1e-8, 0.1, 0.6, 1e-22) are the paper's.  With dlo = -inf, dhi = +inf, k, K, dv and status are
+   tds_hip_lqr_backward's bit for bit (the first Newton point is the plain k by the same sums; the second iteration's
+   test 4 ends the loop).  Further outputs: clamped [n][T] (int32; bit a set: control a clamped in the final set),
+   qp_iterations [n][T] (int32; iterations begun, at most 100); both zero over the horizon of a problem whose status is
+   not 0.  dlo <= dhi without NaN is the caller's promise on the device (the host checker returns TDS_ERR_INVALID_ARG).
+   Bounds, refusals and messages otherwise as tds_hip_lqr_backward; ONE launch on the handle's stream, no host wait. */
+int tds_hip_lqr_backward_box(tds_hip_sim_t *sim, int n, int T, int nx, int nu, const void *A_dev, const void *B_dev,
+                             const void *lx_dev, const void *lu_dev, const void *lxx_dev, const void *luu_dev,
+                             const void *lux_dev, const void *mu_dev, const void *dlo_dev, const void *dhi_dev,
+                             void *k_dev, void *K_dev, void *dv_dev, void *status_dev, void *clamped_dev,
+                             void *qp_iterations_dev);
+/* The same statement with plain loops on the CPU: the checker.  dlo > dhi anywhere, or a NaN bound:
+   TDS_ERR_INVALID_ARG. */
+int tds_hip_lqr_backward_box_host(int n, int T, int nx, int nu, const double *A, const double *B, const double *lx,
+                                  const double *lu, const double *lxx, const double *luu, const double *lux,
+                                  const double *mu, const double *dlo, const double *dhi, double *k, double *K,
+                                  double *dv, int32_t *status, int32_t *clamped, int32_t *qp_iterations);
+
+/* Batched iLQR under control limits, part 2: tds_hip_feedback_rollout with
+       u_t = min(max((u_nom[p,t] + alpha k[p,t]) + K[p,t] (s_t - s_nom[p,t]), u_lo[p,t]), u_hi[p,t])
+   u_lo, u_hi [P][T][n_act] absolute bounds, indexed by the row's problem and the step; u_out and the record that enters
+   the step both hold the clamped value.  u_lo = u_hi = NULL is tds_hip_feedback_rollout itself; one of them NULL is
+   TDS_ERR_INVALID_ARG.  u_lo <= u_hi without NaN is the caller's promise on the device (the host checker returns
+   TDS_ERR_INVALID_ARG).  Everything else as tds_hip_feedback_rollout. */
+int tds_hip_feedback_rollout_box(tds_hip_sim_t *sim, int rows, int T, const void *x0_dev, const void *s_nom_dev,
+                                 const void *u_nom_dev, const void *k_dev, const void *K_dev, const void *alpha_dev,
+                                 const void *problem_of_row_dev, const void *u_lo_dev, const void *u_hi_dev,
+                                 void *s_out_dev, void *u_out_dev);
+int tds_hip_feedback_rollout_box_host(const tds_model_t *model, int rows, int T, int num_problems, const double *x0,
+                                      const double *s_nom, const double *u_nom, const double *k, const double *K,
+                                      const double *alpha, const int32_t *problem_of_row, const double *u_lo,
+                                      const double *u_hi, double *s_out, double *u_out);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

@@ -191,6 +191,10 @@ def lib():
         L.tds_hip_lqr_backward_host.argtypes = [C.c_int] * 4 + [C.c_void_p] * 12
         L.tds_hip_feedback_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
         L.tds_hip_feedback_rollout_host.argtypes = [P, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9
+        L.tds_hip_lqr_backward_box.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 16
+        L.tds_hip_lqr_backward_box_host.argtypes = [C.c_int] * 4 + [C.c_void_p] * 16
+        L.tds_hip_feedback_rollout_box.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
+        L.tds_hip_feedback_rollout_box_host.argtypes = [P, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11
         _lib = L
     return _lib
 
@@ -429,6 +433,8 @@ EXPORTED_SYMBOLS = [
     "tds_hip_dynamics_host", "tds_hip_inverse_dynamics_host", "tds_hip_point_jacobian_host",
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
     "tds_hip_lqr_backward", "tds_hip_lqr_backward_host", "tds_hip_feedback_rollout", "tds_hip_feedback_rollout_host",
+    "tds_hip_lqr_backward_box", "tds_hip_lqr_backward_box_host", "tds_hip_feedback_rollout_box",
+    "tds_hip_feedback_rollout_box_host",
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_hip_contacts_jvp", "tds_hip_contacts_jvp_host", "tds_hip_contacts_jvp_tangents",
     "tds_hip_dynamics_jvp", "tds_hip_inverse_dynamics_jvp", "tds_hip_dynamics_jvp_host",
@@ -980,6 +986,41 @@ def lqr_backward_host(A, B, lx, lu, lxx, luu, lux, mu):
     return k, K, dv, status
 
 
+def _bounds_ordered(lo, hi, names):
+    """ValueError unless lo <= hi in every entry (a NaN fails the comparison); numpy arrays or torch tensors"""
+    if not bool((lo <= hi).all()):
+        raise ValueError(f"{names[0]} > {names[1]} somewhere, or a NaN bound")
+
+
+def lqr_backward_box_host(A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi):
+    """The backward pass under control limits on the CPU (tds_hip_lqr_backward_box_host; the checker of
+    HipSim.lqr_backward_box, needs no GPU).  Arguments as lqr_backward_host, and dlo <= dhi [n, T, nu]: the bounds on
+    the step k_t (lo - u_nom, hi - u_nom; +-inf: none).  Per step a box-constrained QP by projected Newton in place of
+    the unconstrained solve, feedback gains on the controls it left free (include/tds_hip.h states it).  Returns
+    (k, K, dv, status, clamped [n, T] int32 -- bit a set: control a clamped in the QP's final set --, qp_iterations
+    [n, T] int32).  Infinite bounds give lqr_backward_host's k, K, dv, status bit for bit."""
+    import numpy as np
+
+    A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
+    (n, T, nx, nu), shapes = _lqr_shapes(A, B)
+    shapes.update({"dlo": (n, T, nu), "dhi": (n, T, nu)})
+    arg = {"lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux,
+           "mu": np.broadcast_to(np.asarray(mu, dtype=np.float64), (n,)), "dlo": dlo, "dhi": dhi}
+    for key, shape in shapes.items():
+        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
+        if arg[key].shape != shape:
+            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
+    _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
+    k, K = np.zeros((n, T, nu)), np.zeros((n, T, nu, nx))
+    dv, status = np.zeros((n, 2)), np.zeros(n, dtype=np.int32)
+    clamped, its = np.zeros((n, T), dtype=np.int32), np.zeros((n, T), dtype=np.int32)
+    _check(lib().tds_hip_lqr_backward_box_host(
+        n, T, nx, nu, A.ctypes.data, B.ctypes.data,
+        *(arg[key].ctypes.data for key in ("lx", "lu", "lxx", "luu", "lux", "mu", "dlo", "dhi")),
+        k.ctypes.data, K.ctypes.data, dv.ctypes.data, status.ctypes.data, clamped.ctypes.data, its.ctypes.data))
+    return k, K, dv, status, clamped, its
+
+
 def _feedback_shapes(m, x0, s_nom):
     """(rows, P, T) and the shapes of a feedback rollout's inputs by name"""
     nsd, n_act, _ = trajectory_dims(m, 1)
@@ -992,12 +1033,15 @@ def _feedback_shapes(m, x0, s_nom):
                                       "alpha": (rows,)}
 
 
-def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, problem_of_row=None):
+def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, problem_of_row=None, u_lo=None,
+                          u_hi=None):
     """The closed-loop rollout on the CPU over step_host (tds_hip_feedback_rollout_host; the checker of
     HipSim.feedback_rollout, needs no GPU).  x0 [rows, input_dim], s_nom [P, T + 1, nsd], u_nom and k [P, T, n_act],
     K [P, T, n_act, nsd], alpha [rows] (or a scalar), problem_of_row [rows] ints in [0, P) or None (row r follows
     problem r: rows == P).  u_t = (u_nom + alpha k) + K (s_t - s_nom), s_{t+1} = the step of [s_t | u_t | the rest of
-    x0's record].  Returns (s [rows, T + 1, nsd], u [rows, T, n_act])."""
+    x0's record].  u_lo, u_hi [P, T, n_act] (both or neither): u_t is clamped to [u_lo, u_hi] of its problem and step
+    (tds_hip_feedback_rollout_box_host); None is the call without limits.  Returns (s [rows, T + 1, nsd],
+    u [rows, T, n_act])."""
     import numpy as np
 
     x0, s_nom = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(s_nom, dtype=np.float64)
@@ -1015,6 +1059,19 @@ def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, pr
     elif rows != P:
         raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
     s, u = np.zeros((rows, T + 1, nsd)), np.zeros((rows, T, n_act))
+    if (u_lo is None) != (u_hi is None):
+        raise ValueError("u_lo and u_hi are given together or not at all")
+    if u_lo is not None:
+        lim = {"u_lo": np.ascontiguousarray(u_lo, dtype=np.float64), "u_hi": np.ascontiguousarray(u_hi, dtype=np.float64)}
+        for key, a in lim.items():
+            if a.shape != (P, T, n_act):
+                raise ValueError(f"{key}: expected {[P, T, n_act]}, got {list(a.shape)}")
+        _bounds_ordered(lim["u_lo"], lim["u_hi"], ("u_lo", "u_hi"))
+        _check(lib().tds_hip_feedback_rollout_box_host(
+            C.byref(m), rows, T, P, x0.ctypes.data, s_nom.ctypes.data,
+            *(arg[key].ctypes.data for key in ("u_nom", "k", "K", "alpha")), None if por is None else por.ctypes.data,
+            lim["u_lo"].ctypes.data, lim["u_hi"].ctypes.data, s.ctypes.data, u.ctypes.data))
+        return s, u
     _check(lib().tds_hip_feedback_rollout_host(C.byref(m), rows, T, P, x0.ctypes.data, s_nom.ctypes.data,
                                                *(arg[key].ctypes.data for key in ("u_nom", "k", "K", "alpha")),
                                                None if por is None else por.ctypes.data, s.ctypes.data, u.ctypes.data))
@@ -2152,17 +2209,56 @@ class HipSim:
                                           C.c_void_p(status.data_ptr())))
         return k, K, dv, status
 
-    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, problem_of_row=None, check: bool = True):
+    def lqr_backward_box(self, A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi, check: bool = True):
+        """The backward pass under control limits as one launch (tds_hip_lqr_backward_box; arguments and results as
+        hip_backend.lqr_backward_box_host, CUDA tensors).  check: dlo <= dhi without NaN is verified before the launch
+        (the one host wait of the call); a caller that built the bounds itself passes False and the call is
+        asynchronous.  The handle's model is not read."""
+        import torch
+
+        (n, T, nx, nu), shapes = _lqr_shapes(A, B)
+        arg = {"A": A, "B": B, "lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux, "mu": mu, "dlo": dlo, "dhi": dhi}
+        shapes.update({"A": (n, T, nx, nx), "B": (n, T, nx, nu), "dlo": (n, T, nu), "dhi": (n, T, nu)})
+        for key, shape in shapes.items():
+            t = arg[key]
+            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
+                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
+            arg[key] = t.contiguous()
+        if check:
+            _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
+        dev = A.device
+        k = torch.empty((n, T, nu), dtype=torch.float64, device=dev)
+        K = torch.empty((n, T, nu, nx), dtype=torch.float64, device=dev)
+        dv = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        clamped = torch.empty((n, T), dtype=torch.int32, device=dev)
+        its = torch.empty((n, T), dtype=torch.int32, device=dev)
+        _check(lib().tds_hip_lqr_backward_box(
+            self.h, n, T, nx, nu,
+            *(C.c_void_p(arg[key].data_ptr())
+              for key in ("A", "B", "lx", "lu", "lxx", "luu", "lux", "mu", "dlo", "dhi")),
+            *(C.c_void_p(t.data_ptr()) for t in (k, K, dv, status, clamped, its))))
+        return k, K, dv, status, clamped, its
+
+    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, problem_of_row=None, check: bool = True, u_lo=None,
+                         u_hi=None):
         """The closed-loop rollout under u_t = (u_nom + alpha k) + K (s_t - s_nom) (tds_hip_feedback_rollout; arguments
         and results as hip_backend.feedback_rollout_host, CUDA float64 tensors; alpha [rows]; problem_of_row a CUDA
         int32 tensor [rows] with entries in [0, P), or None).  Any number of rows.  check: the entries of problem_of_row
         are verified before the launch (the one host wait of the call); a caller that built the map itself passes
-        False and the call is asynchronous."""
+        False and the call is asynchronous.  u_lo, u_hi [P, T, n_act] (both or neither): u_t is clamped to them
+        (tds_hip_feedback_rollout_box; u_lo <= u_hi without NaN is verified under check); None is the call without
+        limits."""
         import torch
 
         (rows, P, T, nsd, n_act), shapes = _feedback_shapes(self.model, x0, s_nom)
         arg = {"x0": x0, "s_nom": s_nom, "u_nom": u_nom, "k": k, "K": K, "alpha": alpha}
         shapes.update({"x0": (rows, self.input_dim), "s_nom": (P, T + 1, nsd)})
+        if (u_lo is None) != (u_hi is None):
+            raise ValueError("u_lo and u_hi are given together or not at all")
+        if u_lo is not None:
+            arg.update({"u_lo": u_lo, "u_hi": u_hi})
+            shapes.update({"u_lo": (P, T, n_act), "u_hi": (P, T, n_act)})
         for key, shape in shapes.items():
             t = arg[key]
             if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
@@ -2179,6 +2275,15 @@ class HipSim:
             raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
         s = torch.empty((rows, T + 1, nsd), dtype=torch.float64, device=x0.device)
         u = torch.empty((rows, T, n_act), dtype=torch.float64, device=x0.device)
+        if u_lo is not None:
+            if check:
+                _bounds_ordered(arg["u_lo"], arg["u_hi"], ("u_lo", "u_hi"))
+            _check(lib().tds_hip_feedback_rollout_box(
+                self.h, rows, T, *(C.c_void_p(arg[key].data_ptr()) for key in ("x0", "s_nom", "u_nom", "k", "K", "alpha")),
+                C.c_void_p(problem_of_row.data_ptr()) if problem_of_row is not None else None,
+                C.c_void_p(arg["u_lo"].data_ptr()), C.c_void_p(arg["u_hi"].data_ptr()), C.c_void_p(s.data_ptr()),
+                C.c_void_p(u.data_ptr())))
+            return s, u
         _check(lib().tds_hip_feedback_rollout(self.h, rows, T,
                                               *(C.c_void_p(arg[key].data_ptr())
                                                 for key in ("x0", "s_nom", "u_nom", "k", "K", "alpha")),

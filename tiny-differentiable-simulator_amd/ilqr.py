@@ -6,7 +6,11 @@ every line-search candidate of every problem (``feedback_rollout``), and a per-p
 ``HipSim`` the loop runs on the device; given a ``Model`` the same driver runs over the ``_host`` checkers on CPU
 tensors, so it can be tested without a GPU.  Every decision is a ``torch.where`` per problem.
 
-Out of scope: second-order dynamics terms (DDP), control limits inside the backward pass (box-DDP)."""
+With ``u_limits`` the iteration is control-limited (Tassa, Mansard, Todorov, ICRA 2014): the backward pass solves a
+box-constrained QP per step and keeps feedback only on the controls it left free (``lqr_backward_box``), and every
+rollout clamps its actions, so each nominal trajectory is feasible and the cost is charged for the actions executed.
+
+Out of scope: second-order dynamics terms (DDP), state constraints."""
 from . import hip_backend
 from . import model as _model
 
@@ -79,8 +83,12 @@ class _DeviceOps:
     def lqr_backward(self, *a):
         return self.sim.lqr_backward(*a)
 
-    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, por):
-        return self.sim.feedback_rollout(x0, s_nom, u_nom, k, K, alpha, por, check=False)  # (por: built below)
+    def lqr_backward_box(self, *a):
+        return self.sim.lqr_backward_box(*a, check=False)  # (the bounds: lo - u <= 0 <= hi - u of a feasible u)
+
+    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, por, u_lo=None, u_hi=None):
+        return self.sim.feedback_rollout(x0, s_nom, u_nom, k, K, alpha, por, check=False,  # (por: built below)
+                                         u_lo=u_lo, u_hi=u_hi)
 
 
 class _HostOps:
@@ -99,11 +107,17 @@ class _HostOps:
 
         return tuple(torch.from_numpy(r) for r in hip_backend.lqr_backward_host(*(t.numpy() for t in a)))
 
-    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, por):
+    def lqr_backward_box(self, *a):
         import torch
 
+        return tuple(torch.from_numpy(r) for r in hip_backend.lqr_backward_box_host(*(t.numpy() for t in a)))
+
+    def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, por, u_lo=None, u_hi=None):
+        import torch
+
+        lim = {} if u_lo is None else {"u_lo": u_lo.numpy(), "u_hi": u_hi.numpy()}
         s, u = hip_backend.feedback_rollout_host(self.model, x0.numpy(), s_nom.numpy(), u_nom.numpy(), k.numpy(),
-                                                 K.numpy(), alpha.numpy(), None if por is None else por.numpy())
+                                                 K.numpy(), alpha.numpy(), None if por is None else por.numpy(), **lim)
         return torch.from_numpy(s), torch.from_numpy(u)
 
 
@@ -111,7 +125,7 @@ DEFAULT_ALPHAS = tuple(2.0 ** -i for i in range(8))
 
 
 def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS, armijo: float = 1e-4,
-         mu0=1e-6, mu_min: float = 1e-9, mu_max: float = 1e9, mu_factor: float = 10.0):
+         mu0=1e-6, mu_min: float = 1e-9, mu_max: float = 1e9, mu_factor: float = 10.0, u_limits=None):
     """iLQR for N problems of horizon T from x0 [N, input_dim] (the first record of each problem: its state, and the
     gains every later record keeps) and the action sequences u0 [N, T, n_act].
 
@@ -126,7 +140,14 @@ def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS
     pass's gains), cost [iterations + 1, N], alpha [iterations, N] (0: rejected), mu [N], status [N] (of the last
     backward pass); and per iteration mu_trace [iterations + 1, N] (the mu each backward pass ran with, then the
     final one), status_trace [iterations, N], dv_trace [iterations, N, 2].  mu0 may be a [N] tensor (a mu per problem).
-    Tensors on the handle's device (a HipSim) or the CPU (a Model)."""
+    Tensors on the handle's device (a HipSim) or the CPU (a Model).
+
+    u_limits: None (no limits: the calls above), a pair (lo, hi) that broadcasts to [N, T, n_act] (+-inf: no limit on
+    that side), or "model": -+action_limit of a locomotion model, which clamps its actions inside the step (a torque
+    model has no limit of its own: ValueError).  With limits the first open-loop rollout and every candidate's rollout
+    clamp their actions to [lo, hi], the backward pass is ``lqr_backward_box`` with the bounds lo - u, hi - u on the
+    step, and the result gains clamped [N, T] (int32, bit a: control a clamped in the last pass's QP) and
+    qp_iterations [N, T].  The line search, the mu schedule and the traces are the same."""
     import torch
 
     ops = _HostOps(sim_or_model) if isinstance(sim_or_model, _model.Model) else _DeviceOps(sim_or_model)
@@ -143,6 +164,22 @@ def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS
     C = int(al.shape[0])
     if C < 1 or iterations < 0:
         raise ValueError("ilqr: needs at least one alpha and iterations >= 0")
+    lo = hi = None
+    if u_limits is not None:
+        if isinstance(u_limits, str):
+            if u_limits != "model":
+                raise ValueError(f'ilqr: u_limits is None, (lo, hi) or "model", got {u_limits!r}')
+            if m.step_mode != _model.TDS_STEP_LOCOMOTION:
+                raise ValueError('ilqr: u_limits="model" needs a locomotion model (a torque model has no action limit)')
+            u_limits = (-float(m.action_limit), float(m.action_limit))
+        if len(u_limits) != 2:
+            raise ValueError(f'ilqr: u_limits is None, (lo, hi) or "model", got {u_limits!r}')
+        try:
+            lo, hi = (torch.as_tensor(b, dtype=torch.float64).to(dev).expand(N, T, n_act).contiguous() for b in u_limits)
+        except RuntimeError:
+            raise ValueError(f"ilqr: u_limits do not broadcast to [N, T, {n_act}] = {[N, T, n_act]}") from None
+        if not bool((lo <= hi).all()):
+            raise ValueError("ilqr: u_limits: lo > hi somewhere, or a NaN bound")
     rows_sel, cols_sel = list(range(nsd)), list(range(nsd + n_act))
     value_of = getattr(cost, "value", None)
     # the candidates' rows: row p C + c is problem p under alpha[c]
@@ -152,11 +189,13 @@ def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS
     # the nominal trajectory of u0: the open-loop rollout
     zk = torch.zeros((N, T, n_act), dtype=torch.float64, device=dev)
     zK = torch.zeros((N, T, n_act, nsd), dtype=torch.float64, device=dev)
+    lim = {} if lo is None else {"u_lo": lo, "u_hi": hi}
     s, u = ops.feedback_rollout(x0, torch.zeros((N, T + 1, nsd), dtype=torch.float64, device=dev), u, zk, zK,
-                                torch.zeros(N, dtype=torch.float64, device=dev), None)
+                                torch.zeros(N, dtype=torch.float64, device=dev), None, **lim)
     mu = torch.as_tensor(mu0, dtype=torch.float64).to(dev).expand(N).contiguous()
     costs, taken, mus, stats, dvs = [], [], [mu], [], []
     k, K, status = zk, zK, torch.zeros(N, dtype=torch.int32, device=dev)
+    clamped = qp_its = torch.zeros((N, T), dtype=torch.int32, device=dev)
     J = cost.expand(s, u)[0]
     costs.append(J)
     for _ in range(int(iterations)):
@@ -164,9 +203,12 @@ def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS
         jac = jac.reshape(N, T, nsd, nsd + n_act)
         A, B = jac[..., :nsd].contiguous(), jac[..., nsd:].contiguous()
         J, lx, lu, lxx, luu, lux = cost.expand(s, u)
-        k, K, dv, status = ops.lqr_backward(A, B, lx.contiguous(), lu.contiguous(), lxx.contiguous(), luu.contiguous(),
-                                            lux.contiguous(), mu)
-        sc, uc = ops.feedback_rollout(x0_rows, s, u, k, K, alpha_rows, por)
+        ex = (A, B, lx.contiguous(), lu.contiguous(), lxx.contiguous(), luu.contiguous(), lux.contiguous(), mu)
+        if lo is None:
+            k, K, dv, status = ops.lqr_backward(*ex)
+        else:
+            k, K, dv, status, clamped, qp_its = ops.lqr_backward_box(*ex, lo - u, hi - u)
+        sc, uc = ops.feedback_rollout(x0_rows, s, u, k, K, alpha_rows, por, **lim)
         sc, uc = sc.reshape(N, C, T + 1, nsd), uc.reshape(N, C, T, n_act)
         if value_of is not None:
             Jc = value_of(sc, uc)
@@ -191,7 +233,10 @@ def ilqr(sim_or_model, x0, u0, cost, iterations: int = 10, alphas=DEFAULT_ALPHAS
         stats.append(status)
         dvs.append(dv)
     hist = lambda a, shape, dt: torch.stack(a) if a else torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-    return {"s": s, "u": u, "k": k, "K": K, "cost": torch.stack(costs),
-            "alpha": hist(taken, (0, N), torch.float64), "mu": mu, "status": status,
-            "mu_trace": torch.stack(mus), "status_trace": hist(stats, (0, N), torch.int32),
-            "dv_trace": hist(dvs, (0, N, 2), torch.float64)}
+    res = {"s": s, "u": u, "k": k, "K": K, "cost": torch.stack(costs),
+           "alpha": hist(taken, (0, N), torch.float64), "mu": mu, "status": status,
+           "mu_trace": torch.stack(mus), "status_trace": hist(stats, (0, N), torch.int32),
+           "dv_trace": hist(dvs, (0, N, 2), torch.float64)}
+    if lo is not None:
+        res.update({"clamped": clamped, "qp_iterations": qp_its})
+    return res

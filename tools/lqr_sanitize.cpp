@@ -1,7 +1,9 @@
 // lqr_sanitize.cpp — the host side of batched iLQR as a program of its own, for the host sanitizers:
 // tds_hip_lqr_backward_host and tds_hip_feedback_rollout_host (csrc/tds_lqr.hip, host code only) at the edge shapes:
 // nx = 1 and 40, nu = 1 and 16, T = 1, a problem that is not positive definite between two that are; the rollout with
-// and without problem_of_row over a stand-in step.  Every array is allocated at its exact size, so that an index past
+// and without problem_of_row over a stand-in step; and their control-limited twins tds_hip_lqr_backward_box_host and
+// tds_hip_feedback_rollout_box_host at the same shapes with finite, infinite and pinned (dlo == dhi) bounds, a step
+// that is not positive definite, and the argument errors.  Every array is allocated at its exact size, so that an index past
 // what is due is an address the sanitizer knows.  No GPU, no Python.  Build and run:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //     -Xarch_host -fno-sanitize-recover=undefined -Iinclude -Itiny-differentiable-simulator_amd/csrc \
@@ -95,6 +97,61 @@ static int backward(int n, int T, int nx, int nu, int bad_problem, int bad_step)
   return 0;
 }
 
+// the box pass: kind 0 bounds -U(0, 1) .. U(0, 1), 1 infinite (the outputs are the plain pass's), 2 every control pinned
+static int backward_box(int n, int T, int nx, int nu, int kind, int bad_problem, int bad_step) {
+  std::vector<double> A = draw((size_t)n * T * nx * nx, -0.5 / nx, 0.5 / nx), B = draw((size_t)n * T * nx * nu, -1, 1);
+  std::vector<double> lx = draw((size_t)n * (T + 1) * nx, -1, 1), lu = draw((size_t)n * T * nu, -1, 1);
+  std::vector<double> lxx = spd((size_t)n * (T + 1), nx, 1.5), luu = spd((size_t)n * T, nu, 1.5);
+  std::vector<double> lux = draw((size_t)n * T * nu * nx, -0.1, 0.1), mu((size_t)n, 0.25);
+  std::vector<double> dlo = draw((size_t)n * T * nu, -1, 0), dhi = draw((size_t)n * T * nu, 0, 1);
+  if (kind == 1)
+    for (size_t e = 0; e < dlo.size(); ++e) dlo[e] = -INFINITY, dhi[e] = INFINITY;
+  if (kind == 2) dlo = dhi;
+  if (bad_problem >= 0)
+    for (int a = 0; a < nu; ++a) {
+      const size_t e = ((size_t)bad_problem * T + bad_step) * nu + a;
+      luu[e * nu + a] = -1e3, dlo[e] = -INFINITY, dhi[e] = INFINITY;  // (left free: the pivot is met)
+    }
+  std::vector<double> k((size_t)n * T * nu), K((size_t)n * T * nu * nx), dv((size_t)n * 2);
+  std::vector<int32_t> status((size_t)n), clamped((size_t)n * T), its((size_t)n * T);
+  EXPECT(tds_hip_lqr_backward_box_host(n, T, nx, nu, A.data(), B.data(), lx.data(), lu.data(), lxx.data(), luu.data(),
+                                       lux.data(), mu.data(), dlo.data(), dhi.data(), k.data(), K.data(), dv.data(),
+                                       status.data(), clamped.data(), its.data()) == TDS_OK);
+  for (int p = 0; p < n; ++p) {
+    EXPECT(status[p] == (p == bad_problem ? bad_step + 1 : 0));
+    for (size_t e = 0; e < (size_t)T * nu * nx; ++e) EXPECT(isfinite(K[(size_t)p * T * nu * nx + e]));
+    for (size_t e = (size_t)p * T * nu; e < (size_t)(p + 1) * T * nu; ++e)
+      EXPECT(p == bad_problem ? k[e] == 0.0 : k[e] >= dlo[e] && k[e] <= dhi[e]);
+    for (size_t e = (size_t)p * T; e < (size_t)(p + 1) * T; ++e) {
+      EXPECT(p == bad_problem ? its[e] == 0 && clamped[e] == 0 : its[e] >= 1 && its[e] <= 100);
+      EXPECT(clamped[e] >= 0 && clamped[e] < (1 << nu));
+      if (kind == 1 && p != bad_problem) EXPECT(clamped[e] == 0 && its[e] == 2);
+      if (kind == 2 && p != bad_problem && bad_problem < 0) EXPECT(its[e] <= 2);
+    }
+  }
+  if (kind == 1) {  // infinite bounds: the plain pass, bit for bit
+    std::vector<double> k0(k.size()), K0(K.size()), dv0(dv.size());
+    std::vector<int32_t> status0((size_t)n);
+    EXPECT(tds_hip_lqr_backward_host(n, T, nx, nu, A.data(), B.data(), lx.data(), lu.data(), lxx.data(), luu.data(),
+                                     lux.data(), mu.data(), k0.data(), K0.data(), dv0.data(), status0.data()) == TDS_OK);
+    EXPECT(k == k0 && K == K0 && dv == dv0 && status == status0);
+  }
+  // the argument errors: bounds out of order, a NaN bound
+  if (kind == 0) {
+    const double keep = dhi.back();
+    dhi.back() = dlo.back() - 1.0;
+    EXPECT(tds_hip_lqr_backward_box_host(n, T, nx, nu, A.data(), B.data(), lx.data(), lu.data(), lxx.data(), luu.data(),
+                                         lux.data(), mu.data(), dlo.data(), dhi.data(), k.data(), K.data(), dv.data(),
+                                         status.data(), clamped.data(), its.data()) == TDS_ERR_INVALID_ARG);
+    dhi.back() = keep, dlo[0] = NAN;
+    EXPECT(tds_hip_lqr_backward_box_host(n, T, nx, nu, A.data(), B.data(), lx.data(), lu.data(), lxx.data(), luu.data(),
+                                         lux.data(), mu.data(), dlo.data(), dhi.data(), k.data(), K.data(), dv.data(),
+                                         status.data(), clamped.data(), its.data()) == TDS_ERR_INVALID_ARG);
+    EXPECT(strstr(tds_internal::g_err, "dlo > dhi or a NaN bound") != nullptr);
+  }
+  return 0;
+}
+
 static int rollout(int rows, int T, int P, bool mapped) {
   tds_model_t m;
   memset(&m, 0, sizeof(m));
@@ -111,6 +168,38 @@ static int rollout(int rows, int T, int P, bool mapped) {
                                        alpha.data(), mapped ? por.data() : nullptr, s.data(), u.data()) == TDS_OK);
   for (double v : s) EXPECT(isfinite(v));
   for (double v : u) EXPECT(isfinite(v));
+  // the clamped twin: every action inside its bounds; infinite bounds give the call above; the argument errors
+  std::vector<double> lo = draw((size_t)P * T * nact, -0.5, 0), hi = draw((size_t)P * T * nact, 0, 0.5);
+  std::vector<double> sb(s.size()), ub(u.size());
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, lo.data(), hi.data(), sb.data(),
+                                           ub.data()) == TDS_OK);
+  for (int r = 0; r < rows; ++r)
+    for (int e = 0; e < T * nact; ++e) {
+      const size_t b = (size_t)(mapped ? por[r] : r) * T * nact + e;
+      EXPECT(ub[(size_t)r * T * nact + e] >= lo[b] && ub[(size_t)r * T * nact + e] <= hi[b]);
+    }
+  for (double v : sb) EXPECT(isfinite(v));
+  std::vector<double> ninf(lo.size(), -INFINITY), pinf(lo.size(), INFINITY);
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, ninf.data(), pinf.data(),
+                                           sb.data(), ub.data()) == TDS_OK);
+  EXPECT(sb == s && ub == u);
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, nullptr, nullptr, sb.data(),
+                                           ub.data()) == TDS_OK);
+  EXPECT(sb == s && ub == u);
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, lo.data(), nullptr, sb.data(),
+                                           ub.data()) == TDS_ERR_INVALID_ARG);
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, hi.data(), lo.data(), sb.data(),
+                                           ub.data()) == TDS_ERR_INVALID_ARG);
+  lo.back() = NAN;
+  EXPECT(tds_hip_feedback_rollout_box_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
+                                           alpha.data(), mapped ? por.data() : nullptr, lo.data(), hi.data(), sb.data(),
+                                           ub.data()) == TDS_ERR_INVALID_ARG);
+  EXPECT(strstr(tds_internal::g_err, "u_lo > u_hi or a NaN bound") != nullptr);
   if (mapped) {
     por[rows / 2] = P;
     EXPECT(tds_hip_feedback_rollout_host(&m, rows, T, P, x0.data(), s_nom.data(), u_nom.data(), k.data(), K.data(),
@@ -125,6 +214,11 @@ int main() {
     if (backward(sh[0], sh[1], sh[2], sh[3], -1, 0)) return 1;
   if (backward(3, 4, 40, 16, 1, 2)) return 1;  // not positive definite at step 2 of the middle problem
   if (backward(3, 1, 5, 3, 1, 0)) return 1;
+  for (const auto &sh : shapes)
+    for (int kind = 0; kind < 3; ++kind)
+      if (backward_box(sh[0], sh[1], sh[2], sh[3], kind, -1, 0)) return 1;
+  if (backward_box(3, 4, 40, 16, 0, 1, 2) || backward_box(3, 1, 5, 3, 0, 1, 0) || backward_box(3, 4, 28, 8, 1, 1, 0))
+    return 1;
   std::vector<double> none(1);
   std::vector<int32_t> st(1);
   EXPECT(tds_hip_lqr_backward_host(1, 1, 41, 1, none.data(), none.data(), none.data(), none.data(), none.data(),
@@ -135,6 +229,17 @@ int main() {
                                    none.data(), none.data(), none.data(), none.data(), none.data(), none.data(),
                                    st.data()) == TDS_ERR_UNSUPPORTED);
   EXPECT(strstr(tds_internal::g_err, "16 controls") != nullptr);
+  EXPECT(tds_hip_lqr_backward_box_host(1, 1, 41, 1, none.data(), none.data(), none.data(), none.data(), none.data(),
+                                       none.data(), none.data(), none.data(), none.data(), none.data(), none.data(),
+                                       none.data(), none.data(), st.data(), st.data(), st.data()) == TDS_ERR_UNSUPPORTED);
+  EXPECT(strstr(tds_internal::g_err, "40 state entries") != nullptr);
+  EXPECT(tds_hip_lqr_backward_box_host(1, 1, 1, 17, none.data(), none.data(), none.data(), none.data(), none.data(),
+                                       none.data(), none.data(), none.data(), none.data(), none.data(), none.data(),
+                                       none.data(), none.data(), st.data(), st.data(), st.data()) == TDS_ERR_UNSUPPORTED);
+  EXPECT(strstr(tds_internal::g_err, "16 controls") != nullptr);
+  EXPECT(tds_hip_lqr_backward_box_host(1, 1, 1, 1, none.data(), none.data(), none.data(), none.data(), none.data(),
+                                       none.data(), none.data(), none.data(), nullptr, none.data(), none.data(),
+                                       none.data(), none.data(), st.data(), st.data(), st.data()) == TDS_ERR_INVALID_ARG);
   if (rollout(1, 1, 1, false) || rollout(5, 4, 5, false) || rollout(7, 3, 2, true)) return 1;
   printf("lqr_sanitize: ok\n");
   return 0;

@@ -6,6 +6,10 @@ them, and the split of one iLQR iteration.
                      n 64 / 1024 / 4096
   feedback_rollout   against T rounds of forward_zero with the feedback law in torch ops (Ant, T 64, rows 64 / 1024 / 4096)
   one ilqr iteration Ant, 64 problems, T 64, 8 alphas: linearisation (jacobian), backward pass, line-search rollout
+  lqr_backward_box   (--sections box) against lqr_backward on the same problem sets, once with infinite bounds and once
+                     with bounds at half the unconstrained k on a random half of the controls: `ratio` = slowest box /
+                     fastest plain, the mean QP iterations and the share of clamped controls; then one
+                     ilqr(u_limits="model") iteration on the Ant beside the unlimited one
 
 Per case a warm-up call, then `--reps` calls timed one by one (a synchronise around each): the line gives the slowest
 and fastest of each side and `ratio` = slowest native / fastest yardstick (the requirement is ratio <= 1).  Run it
@@ -26,6 +30,7 @@ def main():
     ap.add_argument("--T", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="64,1024,4096")
+    ap.add_argument("--sections", default="plain", help="comma-separated: plain (the yardstick comparisons), box")
     args = ap.parse_args()
 
     import numpy as np
@@ -89,12 +94,23 @@ def main():
             k[:, t], K[:, t] = kk[:, :, 0], KK
         return k, K, torch.stack([dv1, dv2], dim=1), bad
 
+    sections = [w for w in args.sections.split(",") if w]
+
+    def problems(n, nx, nu):
+        A = rnd(n, T, nx, nx) / nx ** 0.5
+        B = rnd(n, T, nx, nu) / nx ** 0.5
+        return (A, B, rnd(n, T + 1, nx), rnd(n, T, nu), spd(n, T + 1, nx), spd(n, T, nu), 0.1 * rnd(n, T, nu, nx),
+                torch.full((n,), 1e-6, dtype=torch.float64, device=dev))
+
+    if "box" in sections:
+        box_section(args, sim, m, sizes, problems, times, rnd)
+    if "plain" not in sections:
+        return
+
     for nx, nu in ((nsd, n_act), (hb.LQR_MAX_NX, hb.LQR_MAX_NU)):
         for n in sizes:
-            A = rnd(n, T, nx, nx) / nx ** 0.5
-            B = rnd(n, T, nx, nu) / nx ** 0.5
-            P = (A, B, rnd(n, T + 1, nx), rnd(n, T, nu), spd(n, T + 1, nx), spd(n, T, nu), 0.1 * rnd(n, T, nu, nx),
-                 torch.full((n,), 1e-6, dtype=torch.float64, device=dev))
+            P = problems(n, nx, nu)
+            A, B = P[:2]
             got, want = sim.lqr_backward(*P), composed_backward(*P)
             diff = max(float((g - w).abs().max() / w.abs().max().clamp(min=1.0)) for g, w in zip(got[:3], want[:3]))
             report(f"lqr_backward nx={nx} nu={nu} T={T} n={n}", times(lambda: sim.lqr_backward(*P)),
@@ -153,6 +169,56 @@ def main():
                       "backward_pass_ms": rng_ms(back), "line_search_rollout_ms": rng_ms(line),
                       "ilqr_iterations_1_ms (with the first open-loop rollout)": rng_ms(whole),
                       "status_nonzero": int((status != 0).sum())}), flush=True)
+
+
+def box_section(args, sim, m, sizes, problems, times, rnd):
+    import numpy as np
+    import torch
+
+    import tds_amd
+    from tds_amd import hip_backend as hb
+
+    T, dev = args.T, "cuda"
+    nsd, n_act, _ = hb.trajectory_dims(m, 1)
+    rng_ms = lambda t: [round(min(t), 3), round(max(t), 3)]  # noqa: E731
+    for nx, nu in ((nsd, n_act), (hb.LQR_MAX_NX, hb.LQR_MAX_NU)):
+        for n in sizes:
+            P = problems(n, nx, nu)
+            k = sim.lqr_backward(*P)[0]
+            inf = torch.full((n, T, nu), float("inf"), dtype=torch.float64, device=dev)
+            # half the controls, chosen at random, may move half as far as the unconstrained pass would move them
+            cut = torch.rand((n, T, nu), device=dev, generator=torch.Generator(device=dev).manual_seed(n + nu)) < 0.5
+            dlo = torch.where(cut & (k < 0), 0.5 * k, -inf)
+            dhi = torch.where(cut & (k > 0), 0.5 * k, inf)
+            plain = times(lambda: sim.lqr_backward(*P))
+            for what, lo, hi in (("infinite bounds", -inf, inf), ("half cut", dlo, dhi)):
+                box = times(lambda: sim.lqr_backward_box(*P, lo, hi, check=False))
+                res = sim.lqr_backward_box(*P, lo, hi, check=False)
+                share = float(sum(((res[4] >> a) & 1).double().mean() for a in range(nu)) / nu)
+                print(json.dumps({"case": f"lqr_backward_box nx={nx} nu={nu} T={T} n={n}, {what}",
+                                  "box_ms": rng_ms(box), "plain_ms": rng_ms(plain),
+                                  "ratio": round(max(box) / min(plain), 4),
+                                  "mean_qp_iterations": round(float(res[5].double().mean()), 3),
+                                  "clamped_share": round(share, 3), "status_nonzero": int((res[3] != 0).sum())}),
+                      flush=True)
+            del P, k, inf, cut, dlo, dhi
+    # one iLQR iteration on the Ant with and without the model's limits
+    N, C = 64, 8
+    g = np.load(os.path.join(ROOT, "tests", "golden", "ant.npz"))["x"]
+    sim64 = hb.HipSim(m, N * C, device=0, dtype="f64")
+    x0 = torch.from_numpy(g[np.random.default_rng(0).integers(0, g.shape[0], N)]).to(dev)
+    u0 = 0.3 * rnd(N, T, n_act)
+    cost = tds_amd.QuadraticCost(torch.eye(nsd), 0.1 * torch.eye(n_act), torch.eye(nsd))
+    free = times(lambda: tds_amd.ilqr(sim64, x0, u0, cost, iterations=1))
+    lim = times(lambda: tds_amd.ilqr(sim64, x0, u0, cost, iterations=1, u_limits="model"))
+    r = tds_amd.ilqr(sim64, x0, u0, cost, iterations=1, u_limits="model")
+    print(json.dumps({"case": f"one ilqr iteration, ant x {N}, T={T}, {C} alphas (with the first open-loop rollout)",
+                      "unlimited_ms": rng_ms(free), "model_limits_ms": rng_ms(lim),
+                      "ratio": round(max(lim) / min(free), 4),
+                      "mean_qp_iterations": round(float(r["qp_iterations"].double().mean()), 3),
+                      "steps_with_a_clamped_control": int((r["clamped"] != 0).sum()), "steps": N * T,
+                      "accepted": int((r["alpha"] > 0).sum())}), flush=True)
+    sim64.close()
 
 
 if __name__ == "__main__":
