@@ -282,6 +282,20 @@ def test_invalid_arguments(built):
         hb.inverse_kinematics_host(m, q, [0], t, method="newton")
     with pytest.raises(ValueError, match="unknown inverse-kinematics option"):
         hb.inverse_kinematics_host(m, q, [0], t, beta=1.0)
+    # malformed arrays are refused in Python, before the library is called: N = 2, K = 2
+    q2, t2 = np.repeat(q, 2, axis=0), np.zeros((2, 2, 3))
+    with pytest.raises(ValueError, match=r"body_points must be \[2, 3\]"):
+        hb.inverse_kinematics_host(m, q2, [0, 1], t2, body_points=np.zeros((1, 3)))
+    with pytest.raises(ValueError, match="cannot reshape"):
+        hb.inverse_kinematics_host(m, q2, [0, 1], np.zeros((2, 2, 2)))
+    with pytest.raises(ValueError, match="broadcast"):
+        hb.inverse_kinematics_host(m, q2, [0, 1], np.zeros((3, 2, 3)))
+    with pytest.raises(ValueError, match="cannot reshape"):
+        hb.inverse_kinematics_host(m, q2[:, :-1], [0, 1], t2)
+    with pytest.raises(ValueError, match="broadcast"):
+        hb.inverse_kinematics_host(m, q2, [0, 1], t2, q_reference=np.zeros((3, m.dof_q)))
+    with pytest.raises(ValueError, match="cannot reshape"):
+        hb.inverse_kinematics_host(m, q2, [0, 1], t2, q_reference=np.zeros((2, m.dof_q - 1)))
     L = hb.lib()
     links = (C.c_int32 * 1)(0)
     out = np.zeros((1, m.dof_q))

@@ -257,3 +257,25 @@ def test_refusals_on_the_device(built):
         sim.inverse_kinematics(cu(q0), links, cu(tgt), method="damped_lm", lam=0.0)
     with pytest.raises(hb.TdsHipError, match="error 1: inverse kinematics: negative max_iterations"):
         sim.inverse_kinematics(cu(q0), links, cu(tgt), max_iterations=-2)
+    # malformed tensors are refused in Python, before the library is called: N = 2, K = 2
+    import torch
+
+    q, t, l2 = cu(q0[:2]), cu(np.zeros((2, 2, 3))), [0, 1]
+    for bad in (q[:, :-1], q.float(), q.cpu(), q[0]):
+        with pytest.raises(AssertionError, match="q_init"):
+            sim.inverse_kinematics(bad, l2, t)
+    for bad in (t[:, :1], t[:1], t[..., :2], t.float(), t.cpu()):
+        with pytest.raises(AssertionError, match="targets"):
+            sim.inverse_kinematics(q, l2, bad)
+    for bad in (q[:1], q[:, :-1], q.float(), q.cpu()):
+        with pytest.raises(AssertionError, match="q_reference"):
+            sim.inverse_kinematics(q, l2, t, q_reference=bad)
+    with pytest.raises(ValueError, match=r"body_points must be \[2, 3\]"):
+        sim.inverse_kinematics(q, l2, t, body_points=np.zeros((1, 3)))
+    with pytest.raises(AssertionError, match="out must hold q"):
+        sim.inverse_kinematics(q, l2, t, out={"status": torch.zeros(2, dtype=torch.int32, device="cuda")})
+    for key, bad in (("q", torch.zeros_like(q)[:, :-1]), ("q", torch.zeros_like(q).float()), ("q", torch.zeros_like(q).cpu()),
+                     ("q", torch.zeros_like(q).t().contiguous().t()), ("status", torch.zeros(2, dtype=torch.int64, device="cuda")),
+                     ("residual", torch.zeros(3, dtype=torch.float64, device="cuda"))):
+        with pytest.raises(AssertionError, match=key):
+            sim.inverse_kinematics(q, l2, t, out={"q": torch.zeros_like(q), key: bad})

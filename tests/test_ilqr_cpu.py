@@ -399,6 +399,20 @@ def test_argument_errors(built):
         hb.feedback_rollout_host(m, x0, s_nom[:, :1], u_nom[:, :0], k[:, :0], K[:, :0], alpha)
     with pytest.raises(ValueError, match="ilqr: expected"):
         tds_amd.ilqr(m, x0, u_nom[:2], quadratic_cost(m))
+    # the refusals no case above reaches: n = 2, T = 2, nx = 4, nu = 1
+    P = lq_problem(3, 2, 2, 4, 1)
+    with pytest.raises(ValueError, match=r"A: expected \[n, T, nx, nx\] and B \[n, T, nx, nu\], got \(2, 2, 4, 4\) and \(2, 1, 4, 1\)"):
+        hb.lqr_backward_host(P[0], P[1][:, :1], *P[2:])
+    with pytest.raises(ValueError, match="broadcast"):
+        hb.lqr_backward_host(*P[:7], np.zeros(3))
+    with pytest.raises(ValueError, match=rf"x0: expected \[rows, {m.input_dim}\], got \[3, {m.input_dim - 1}\]"):
+        hb.feedback_rollout_host(m, x0[:, :-1], s_nom, u_nom, k, K, alpha)
+    with pytest.raises(ValueError, match=r"s_nom: expected \[P, T \+ 1, 4\] with T >= 1, got \[3, 6, 3\]"):
+        hb.feedback_rollout_host(m, x0, s_nom[..., :3], u_nom, k, K, alpha)
+    with pytest.raises(ValueError, match=r"problem_of_row: expected \[3\], got \[2\]"):
+        hb.feedback_rollout_host(m, x0, s_nom, u_nom, k, K, alpha, problem_of_row=[0, 1])
+    with pytest.raises(ValueError, match="broadcast"):
+        hb.feedback_rollout_host(m, x0, s_nom, u_nom, k, K, alpha[:2])
 
 
 @pytest.mark.parametrize("name", REFUSED)

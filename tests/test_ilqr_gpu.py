@@ -239,6 +239,39 @@ def test_refusals_on_the_device(cartpole_sim):
         cartpole_sim.feedback_rollout(*dev, problem_of_row=cu(np.array([0, 3, 1], dtype=np.int32)))
     with pytest.raises(ValueError, match="K: expected"):
         cartpole_sim.feedback_rollout(*dev[:4], dev[4][..., :3], dev[5])
+    # the refusals no case above reaches: n = 2, T = 2, nx = 4, nu = 1; a feedback rollout of 3 rows
+    L = [cu(a) for a in lq_problem(3, 2, 2, 4, 1)]
+    one = torch.ones((2, 2, 1), dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError, match=r"A: expected \[n, T, nx, nx\] and B \[n, T, nx, nu\], got \(2, 2, 4, 4\) and \(2, 1, 4, 1\)"):
+        cartpole_sim.lqr_backward(L[0], L[1][:, :1], *L[2:])
+    with pytest.raises(ValueError, match=r"A: expected \[n, T, nx, nx\] and B"):
+        cartpole_sim.lqr_backward_box(L[0][:, :, :3], *L[1:], -one, one)
+    for bad in (L[6][..., :3], L[6].float(), L[6].cpu()):
+        with pytest.raises(ValueError, match=r"lux: expected a CUDA float64 tensor \[2, 2, 1, 4\], got "):
+            cartpole_sim.lqr_backward(*L[:6], bad, L[7])
+        with pytest.raises(ValueError, match=r"lux: expected a CUDA float64 tensor \[2, 2, 1, 4\], got "):
+            cartpole_sim.lqr_backward_box(*L[:6], bad, L[7], -one, one)
+    for bad in (one[:, :1], one.float(), one.cpu()):
+        with pytest.raises(ValueError, match=r"dhi: expected a CUDA float64 tensor \[2, 2, 1\], got "):
+            cartpole_sim.lqr_backward_box(*L, -one, bad)
+    with pytest.raises(ValueError, match=rf"x0: expected \[rows, {m.input_dim}\], got \[3, {m.input_dim - 1}\]"):
+        cartpole_sim.feedback_rollout(dev[0][:, :-1], *dev[1:])
+    with pytest.raises(ValueError, match=r"s_nom: expected \[P, T \+ 1, 4\] with T >= 1, got \[3, 6, 3\]"):
+        cartpole_sim.feedback_rollout(dev[0], dev[1][..., :3], *dev[2:])
+    with pytest.raises(ValueError, match=r"x0: expected a CUDA float64 tensor \[3, "):
+        cartpole_sim.feedback_rollout(dev[0].float(), *dev[1:])
+    with pytest.raises(ValueError, match=r"alpha: expected a CUDA float64 tensor \[3\], got \[2\]"):
+        cartpole_sim.feedback_rollout(*dev[:5], dev[5][:2])
+    with pytest.raises(ValueError, match=r"one row per problem \(3\), got 2"):
+        cartpole_sim.feedback_rollout(dev[0][:2], *dev[1:5], dev[5][:2])
+    por = cu(np.array([0, 2, 1], dtype=np.int32))
+    for bad in (por[:2], por.long(), por.cpu()):
+        with pytest.raises(ValueError, match=r"problem_of_row: expected a CUDA int32 tensor \[3\]"):
+            cartpole_sim.feedback_rollout(*dev, problem_of_row=bad)
+    lo, hi = -torch.ones_like(dev[2]), torch.ones_like(dev[2])
+    for bad in (hi[:, :3], hi.float(), hi.cpu()):
+        with pytest.raises(ValueError, match=rf"u_hi: expected a CUDA float64 tensor \[3, 5, {lo.shape[2]}\], got "):
+            cartpole_sim.feedback_rollout(*dev, u_lo=lo, u_hi=bad)
     refused = 0
     for dt in ("f32", "mixed"):  # float arithmetic; double arithmetic over float records
         s32 = hb.HipSim(m, 4, device=0, dtype=dt)

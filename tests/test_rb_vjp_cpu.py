@@ -221,6 +221,26 @@ def test_refusals(built):
         with pytest.raises(hb.TdsHipError, match="tds_rb error 1:") as e:
             hb.rb_vjp_host(m, s0, 1, gs, bad)
         assert str(e.value) == str(e_jvp.value)
+    # malformed arrays are refused in Python, before the library is called: N = 2, K = 2, steps = 2
+    sel = [("mass", 1), ("friction",)]
+    z = np.zeros
+    for bad_gs in (z((2, 2, ns)), z((2, ns - 1)), z((1, 1, ns))):
+        with pytest.raises(ValueError, match=rf"gs: expected \[2, 1, {ns}\], got "):
+            hb.rb_vjp_host(m, s0, 2, bad_gs)
+    with pytest.raises(ValueError, match=rf"gs: expected \[2, 2, {ns}\], got "):
+        hb.rb_vjp_host(m, s0, 2, gs, every=1)
+    for bad_theta, got in ((z((2, 1)), r"\(2, 1\)"), (z((1, 2)), r"\(1, 2\)"), (z(3), r"\(3,\)")):
+        with pytest.raises(ValueError, match=r"theta: expected \[2\] or \[2, 2\], got " + got):
+            hb.rb_vjp_host(m, s0, 2, gs, sel, bad_theta)
+        with pytest.raises(ValueError, match=r"theta: expected \[2\] or \[2, 2\], got " + got):
+            hb.rb_jvp_host(m, s0, 2, None, sel, bad_theta)
+    for v in (z((2, 2, ns + 3)), z((3, 2, ns + 2)), z((2, ns + 3)), z((2, 2, 1, ns + 2))):
+        with pytest.raises(ValueError, match=rf"v: expected \[2, K, {ns + 2}\]"):
+            hb.rb_jvp_host(m, s0, 2, v, sel)
+    with pytest.raises(ValueError, match="cannot reshape"):
+        hb.rb_jvp_host(m, np.zeros((2, ns - 1)), 2)
+    with pytest.raises(ValueError, match="cannot reshape"):
+        hb.rb_vjp_host(m, np.zeros((2, ns - 1)), 2, gs)
     L = hb.lib()
     st, out = np.ascontiguousarray(s0), np.zeros_like(s0)
     nul = (hb.Param * 1)()

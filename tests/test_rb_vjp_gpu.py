@@ -109,6 +109,25 @@ def test_rb_vjp_primal_resident_state_and_refusals(built):
     # an overflowing capacity: NaN gradients, the states stand
     with pytest.raises(hb.TdsHipError, match="tape exceeds the capacity"):
         sim.vjp(_cuda(s0), torch.ones((64, 1, ns), dtype=torch.float64, device="cuda"), 6, tape_cap=100)
+    # malformed tensors are refused in Python, before the library is called: N = 2, K = 2, steps = 2
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")  # noqa: E731
+    s2, sel = _cuda(s0[:2]), [("mass", 1), ("friction",)]
+    bad_s = (s2.float(), s2.cpu())
+    bad_th = (z(2, 1), z(1, 2), z(2, 2).float(), z(2, 2).cpu())
+    bad_v = (z(2, 2, ns + 3), z(3, 2, ns + 2), z(2, ns + 3), z(2, 2, 1, ns + 2), z(2, 2, ns + 2).float(),
+             z(2, 2, ns + 2).cpu())
+    bad_gs = (z(2, 2, ns), z(2, ns - 1), z(1, 1, ns), z(2, 1, ns).float(), z(2, 1, ns).cpu())
+    refused = [lambda b=b: sim.jvp(b, None, 2) for b in bad_s]
+    refused += [lambda b=b: sim.vjp(b, z(2, 1, ns), 2) for b in bad_s]
+    refused += [lambda b=b: sim.jvp(s2, None, 2, sel, b) for b in bad_th]
+    refused += [lambda b=b: sim.vjp(s2, z(2, 1, ns), 2, sel, b) for b in bad_th]
+    refused += [lambda b=b: sim.jvp(s2, b, 2, sel) for b in bad_v]
+    refused += [lambda b=b: sim.vjp(s2, b, 2) for b in bad_gs]
+    refused.append(lambda: sim.vjp(s2, z(2, 1, ns), 2, every=1))
+    for i, call in enumerate(refused):
+        with pytest.raises(AssertionError):
+            call()
+            pytest.fail(f"refused[{i}] was accepted")
 
 
 def test_rb_rollout_fn_reverse_gradcheck(built):

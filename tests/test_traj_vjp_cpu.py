@@ -230,6 +230,46 @@ def test_invalid_steps_every_and_selection(built):
         with pytest.raises(hb.TdsHipError, match="tds_hip error 1:") as e:
             hb.trajectory_vjp_host(m, x, np.zeros((1, 2, gs.shape[2])), 2, params=bad, theta=np.ones(len(bad)))
         assert str(e.value) == str(e_jvp.value)
+    # malformed arrays are refused in Python, before the library is called: N = 2, K = 2, steps = 2
+    x, th = x0[:2], th[:2]
+    nin, nout, p, nsd = m.input_dim, m.output_dim, len(sel), gs.shape[2]
+    n_act = hb.trajectory_dims(m, 2)[1]
+    P = hb.policy_network_spec(m)[4]
+    z = np.zeros
+    for bad_theta, got in ((th[:, :-1], f"({2}, {p - 1})"), (th[:1], f"(1, {p})"), (th[0, :-1], f"({p - 1},)")):
+        for call in (lambda t: hb.jvp_params_host(m, x, t, sel),
+                     lambda t: hb.vjp_params_host(m, x, t, sel, z((2, nout))),
+                     lambda t: hb.trajectory_jvp_host(m, x, steps=2, params=sel, theta=t),
+                     lambda t: hb.trajectory_vjp_host(m, x, z((2, 2, nsd)), 2, params=sel, theta=t),
+                     lambda t: hb.policy_trajectory_vjp_host(m, x, z(P), z((2, 2, nsd)), 2, params=sel, theta=t)):
+            with pytest.raises(ValueError, match=rf"theta: expected \[{p}\] or \[2, {p}\], got " + got.replace("(", r"\(").replace(")", r"\)")):
+                call(bad_theta)
+    for v in (z((2, 2, nin + p + 1)), z((3, 2, nin + p)), z((2, nin + p + 1)), z((2, 2, 1, nin + p))):
+        with pytest.raises(ValueError, match=rf"v: expected \[2, K, {nin + p}\]"):
+            hb.jvp_params_host(m, x, th, sel, v)
+        with pytest.raises(ValueError, match=rf"v: expected \[2, K, {nin + p}\]"):
+            hb.trajectory_jvp_host(m, x, v, 2, params=sel, theta=th)
+    for w in (z((2, 2, nout + 1)), z((3, 2, nout)), z((2, nout + 1)), z((2, 2, 1, nout))):
+        with pytest.raises(ValueError, match=rf"w: expected \[2, K, {nout}\] or \[2, {nout}\], got "):
+            hb.vjp_params_host(m, x, th, sel, w)
+        with pytest.raises(ValueError, match=rf"w: expected \[2, K, {nout}\] or \[2, {nout}\], got "):
+            hb.vjp_host(m, x, w)
+    for bad_u in (z((2, 2, n_act)), z((2, 1, n_act + 1)), z((1, 1, n_act))):
+        with pytest.raises(ValueError, match=rf"u: expected \[2, 1, {n_act}\], got "):
+            hb.trajectory_jvp_host(m, x, steps=2, u=bad_u)
+        with pytest.raises(ValueError, match=rf"u: expected \[2, 1, {n_act}\], got "):
+            hb.trajectory_vjp_host(m, x, z((2, 2, nsd)), 2, u=bad_u)
+    for bad_gs in (z((2, 1, nsd)), z((2, 2, nsd + 1)), z((1, 2, nsd))):
+        with pytest.raises(ValueError, match=rf"gs: expected \[2, 2, {nsd}\], got "):
+            hb.trajectory_vjp_host(m, x, bad_gs, 2)
+        with pytest.raises(ValueError, match=rf"gs: expected \[2, 2, {nsd}\], got "):
+            hb.policy_trajectory_vjp_host(m, x, z(P), bad_gs, 2)
+    for bad_ga in (z((2, 1, n_act)), z((2, 2, n_act + 1)), z((1, 2, n_act))):
+        with pytest.raises(ValueError, match=rf"ga: expected \[2, 2, {n_act}\], got "):
+            hb.policy_trajectory_vjp_host(m, x, z(P), None, 2, ga=bad_ga)
+    for bad_pol, got in ((z(P + 1), rf"\({P + 1},\)"), (z((1, P)), rf"\(1, {P}\)"), (z((2, P - 1)), rf"\(2, {P - 1}\)")):
+        with pytest.raises(ValueError, match=rf"policy: expected \[{P}\] or \[2, {P}\], got " + got):
+            hb.policy_trajectory_vjp_host(m, x, bad_pol, z((2, 2, nsd)), 2)
 
 
 @pytest.mark.parametrize("name", REFUSED)

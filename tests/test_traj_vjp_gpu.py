@@ -259,6 +259,52 @@ def test_refusals_and_the_tape_bound(built):
         s2 = hb.HipSim(ms, 2, device=0, dtype="f64")
         s2.trajectory_vjp(torch.from_numpy(records("pendulum5_spherical", 2)).cuda(),
                           torch.zeros((2, 3, ms.dof_q + ms.dof_qd), dtype=torch.float64, device="cuda"), 3)
+    # malformed tensors are refused in Python, before the library is called: N = 2, K = 2, steps = 2
+    mp, selp, xp, thp, up, gp = inputs("pendulum5", 2, 2)
+    sp = hb.HipSim(mp, 2, device=0, dtype="f64")
+    nin, nout, p, nsd = mp.input_dim, mp.output_dim, len(selp), gp.shape[2]
+    n_act, P = up.shape[2], hb.policy_network_spec(mp)[4]
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")  # noqa: E731
+    xg, tg, pol = cuda(xp), cuda(thp), z(P)
+    bad_x = (z(2, nin + 1), z(2, 1, nin), xg.float(), xg.cpu())
+    bad_th = (z(2, p + 1), z(1, p), tg.float(), tg.cpu())
+    bad_v = (z(2, 2, nin + p + 1), z(3, 2, nin + p), z(2, nin + p + 1), z(2, 2, nin + p).float(), z(2, 2, nin + p).cpu())
+    bad_w = (z(2, 2, nout + 1), z(3, 2, nout), z(2, nout + 1), z(2, 2, nout).float(), z(2, 2, nout).cpu())
+    bad_u = (z(2, 2, n_act), z(2, 1, n_act + 1), z(1, 1, n_act), z(2, 1, n_act).float(), z(2, 1, n_act).cpu())
+    bad_gs = (z(2, 1, nsd), z(2, 2, nsd + 1), z(1, 2, nsd), z(2, 2, nsd).float(), z(2, 2, nsd).cpu())
+    bad_ga = (z(2, 1, n_act), z(2, 2, n_act + 1), z(1, 2, n_act), z(2, 2, n_act).float(), z(2, 2, n_act).cpu())
+    bad_pol = (z(P + 1), z(1, P), z(2, P - 1), pol.float(), pol.cpu())
+    bad_y = (z(2, nout + 1), z(1, nout), z(2, nout).float(), z(2, nout).cpu(), z(nout, 2).t())
+    refused = [lambda b=b: sp.jvp(b, z(2, 2, nin)) for b in bad_x]
+    refused += [lambda b=b: sp.jacobian(b) for b in bad_x]
+    refused += [lambda b=b: sp.vjp(b, z(2, 2, nout)) for b in bad_x]
+    refused += [lambda b=b: sp.jvp_params(b, tg, selp) for b in bad_x]
+    refused += [lambda b=b: sp.vjp_params(b, tg, selp, z(2, 2, nout)) for b in bad_x]
+    refused += [lambda b=b: sp.trajectory_jvp(b, None, 2) for b in bad_x]
+    refused += [lambda b=b: sp.trajectory_vjp(b, z(2, 2, nsd), 2) for b in bad_x]
+    refused += [lambda b=b: sp.policy_trajectory_vjp(b, pol, z(2, 2, nsd), 2) for b in bad_x]
+    refused += [lambda b=b: sp.jacobian(xg, y=b) for b in bad_y]
+    refused += [lambda b=b: sp.vjp(xg, z(2, 2, nout), y=b) for b in bad_y]
+    refused += [lambda b=b: sp.jvp(xg, b) for b in (z(2, 2, nin + 1), z(3, 2, nin), z(2, nin + 1), z(2, 2, nin).float())]
+    refused += [lambda b=b: sp.jvp_params(xg, tg, selp, b) for b in bad_v]
+    refused += [lambda b=b: sp.trajectory_jvp(xg, b, 2, params=selp, theta=tg) for b in bad_v]
+    refused += [lambda b=b: sp.vjp(xg, b) for b in bad_w]
+    refused += [lambda b=b: sp.vjp_params(xg, tg, selp, b) for b in bad_w]
+    refused += [lambda b=b: sp.jvp_params(xg, b, selp) for b in bad_th]
+    refused += [lambda b=b: sp.vjp_params(xg, b, selp, z(2, 2, nout)) for b in bad_th]
+    refused += [lambda b=b: sp.trajectory_jvp(xg, None, 2, params=selp, theta=b) for b in bad_th]
+    refused += [lambda b=b: sp.trajectory_vjp(xg, z(2, 2, nsd), 2, params=selp, theta=b) for b in bad_th]
+    refused += [lambda b=b: sp.policy_trajectory_vjp(xg, pol, z(2, 2, nsd), 2, params=selp, theta=b) for b in bad_th]
+    refused += [lambda b=b: sp.trajectory_jvp(xg, None, 2, u=b) for b in bad_u]
+    refused += [lambda b=b: sp.trajectory_vjp(xg, z(2, 2, nsd), 2, u=b) for b in bad_u]
+    refused += [lambda b=b: sp.trajectory_vjp(xg, b, 2) for b in bad_gs]
+    refused += [lambda b=b: sp.policy_trajectory_vjp(xg, pol, b, 2) for b in bad_gs]
+    refused += [lambda b=b: sp.policy_trajectory_vjp(xg, pol, None, 2, ga=b) for b in bad_ga]
+    refused += [lambda b=b: sp.policy_trajectory_vjp(xg, b, z(2, 2, nsd), 2) for b in bad_pol]
+    for i, call in enumerate(refused):
+        with pytest.raises(AssertionError):
+            call()
+            pytest.fail(f"refused[{i}] was accepted")
     # one PGS iteration past class A's range, every parameter selected: some tapes of the contact sweep exceed the bound
     mo = m.copy()
     mo.pgs_iterations = ANT_PGS_OVERFLOW

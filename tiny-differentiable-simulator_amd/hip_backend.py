@@ -115,15 +115,17 @@ def lib():
         L.tds_hip_option_name.argtypes = [C.c_int]
         L.tds_hip_option_name.restype = C.c_char_p
         L.tds_hip_jvp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.tds_hip_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                       C.c_int, C.c_void_p, C.c_void_p]
-        L.tds_hip_jacobian_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                            C.c_void_p, C.c_void_p]
+        # a device call and its host twin share a tail: the handle or the model in front, the host's tape arguments
+        # (tape_cap, the tape_len pointer) behind
+        tape = [C.c_int, C.c_void_p]
+        jac_tail = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tds_hip_jacobian.argtypes = [C.c_void_p] + jac_tail
+        L.tds_hip_jacobian_host.argtypes = [P] + jac_tail
         L.tds_hip_jacobian_tangents.argtypes = [P]
-        L.tds_hip_vjp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.tds_hip_vjp_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.tds_hip_vjp_host_tape.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_int, C.c_void_p]
+        vjp_tail = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tds_hip_vjp.argtypes = [C.c_void_p] + vjp_tail
+        L.tds_hip_vjp_host.argtypes = [P] + vjp_tail
+        L.tds_hip_vjp_host_tape.argtypes = [P] + vjp_tail + tape
         PP = C.POINTER(Param)
         L.tds_hip_params_get.argtypes = [P, C.c_int, PP, C.c_void_p]
         L.tds_hip_params_apply.argtypes = [P, C.c_int, PP, C.c_void_p, P]
@@ -131,33 +133,27 @@ def lib():
         L.tds_hip_model_variants.argtypes = [C.c_void_p]
         L.tds_hip_model_variants_host.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, PP, C.c_void_p, C.c_void_p,
                                                   C.POINTER(C.c_int64)]
-        L.tds_hip_jvp_params.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PP] + [C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 3
-        L.tds_hip_vjp_params.argtypes = L.tds_hip_jvp_params.argtypes
-        L.tds_hip_jvp_params_host.argtypes = [P, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 3
-        L.tds_hip_vjp_params_host.argtypes = L.tds_hip_jvp_params_host.argtypes + [C.c_int, C.c_void_p]
-        L.tds_hip_trajectory_jvp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
-            [C.c_void_p, C.c_int] + [C.c_void_p] * 3
-        L.tds_hip_trajectory_jvp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
-            [C.c_void_p, C.c_int] + [C.c_void_p] * 3
-        L.tds_hip_trajectory_vjp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
-            [C.c_void_p] * 6
-        L.tds_hip_trajectory_vjp_host.argtypes = [P] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + \
-            [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
-        L.tds_hip_policy_trajectory_vjp.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + \
-            [C.c_void_p] * 3 + [C.c_int, PP] + [C.c_void_p] * 8
-        L.tds_hip_policy_trajectory_vjp_host.argtypes = [P] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + \
-            [C.c_void_p] * 3 + [C.c_int, PP] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
+        dp_tail = [C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.tds_hip_jvp_params.argtypes = L.tds_hip_vjp_params.argtypes = [C.c_void_p] + dp_tail
+        L.tds_hip_jvp_params_host.argtypes = [P] + dp_tail
+        L.tds_hip_vjp_params_host.argtypes = [P] + dp_tail + tape
+        tj_tail = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.tds_hip_trajectory_jvp.argtypes = [C.c_void_p] + tj_tail
+        L.tds_hip_trajectory_jvp_host.argtypes = [P] + tj_tail
+        tv_tail = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, PP] + [C.c_void_p] * 6
+        L.tds_hip_trajectory_vjp.argtypes = [C.c_void_p] + tv_tail
+        L.tds_hip_trajectory_vjp_host.argtypes = [P] + tv_tail + tape
+        pv_tail = [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, PP] + [C.c_void_p] * 8
+        L.tds_hip_policy_trajectory_vjp.argtypes = [C.c_void_p] + pv_tail
+        L.tds_hip_policy_trajectory_vjp_host.argtypes = [P] + pv_tail + tape
         RP = C.POINTER(_model.RbModel)
         L.tds_rb_params_get.argtypes = [RP, C.c_int, PP, C.c_void_p]
-        L.tds_rb_jvp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 3
-        L.tds_rb_jvp_host.argtypes = [RP, C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 3
-        L.tds_rb_vjp.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, PP] + [C.c_void_p] * 5 + \
-            [C.c_int, C.c_size_t]
-        L.tds_rb_vjp_host.argtypes = [RP] + [C.c_int] * 3 + [C.c_void_p, C.c_int, PP] + [C.c_void_p] * 5 + [C.c_int]
+        rj_tail = [C.c_int, C.c_int, C.c_void_p, C.c_int, PP, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.tds_rb_jvp.argtypes = [C.c_void_p] + rj_tail
+        L.tds_rb_jvp_host.argtypes = [RP] + rj_tail
+        rv_tail = [C.c_int] * 3 + [C.c_void_p, C.c_int, PP] + [C.c_void_p] * 5 + [C.c_int]   # (.., tape_cap)
+        L.tds_rb_vjp.argtypes = [C.c_void_p] + rv_tail + [C.c_size_t]                        # (.., work_bytes)
+        L.tds_rb_vjp_host.argtypes = [RP] + rv_tail
         L.tds_rb_vjp_plan.argtypes = [RP] + [C.c_int] * 4 + [C.c_size_t, C.POINTER(C.c_longlong)]
         DP = C.POINTER(DynOut)
         L.tds_hip_dynamics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [DP]
@@ -187,14 +183,14 @@ def lib():
             [C.c_void_p] * 4
         L.tds_hip_inverse_kinematics.argtypes = [C.c_void_p] + ik_tail
         L.tds_hip_inverse_kinematics_host.argtypes = [P] + ik_tail
-        L.tds_hip_lqr_backward.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 12
-        L.tds_hip_lqr_backward_host.argtypes = [C.c_int] * 4 + [C.c_void_p] * 12
-        L.tds_hip_feedback_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
-        L.tds_hip_feedback_rollout_host.argtypes = [P, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9
-        L.tds_hip_lqr_backward_box.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 16
-        L.tds_hip_lqr_backward_box_host.argtypes = [C.c_int] * 4 + [C.c_void_p] * 16
-        L.tds_hip_feedback_rollout_box.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
-        L.tds_hip_feedback_rollout_box_host.argtypes = [P, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11
+        # (the box forms: two bounds more among the inputs; the Riccati pass two outputs more as well.  The host's
+        # Riccati pass takes no model, its rollout the number of problems P)
+        for box, lq_tail, fb_tail in (("", [C.c_int] * 4 + [C.c_void_p] * 12, [C.c_void_p] * 9),
+                                      ("_box", [C.c_int] * 4 + [C.c_void_p] * 16, [C.c_void_p] * 11)):
+            getattr(L, f"tds_hip_lqr_backward{box}").argtypes = [C.c_void_p] + lq_tail
+            getattr(L, f"tds_hip_lqr_backward{box}_host").argtypes = lq_tail
+            getattr(L, f"tds_hip_feedback_rollout{box}").argtypes = [C.c_void_p, C.c_int, C.c_int] + fb_tail
+            getattr(L, f"tds_hip_feedback_rollout{box}_host").argtypes = [P, C.c_int, C.c_int, C.c_int] + fb_tail
         _lib = L
     return _lib
 
@@ -572,29 +568,9 @@ def jacobian_host(m: _model.Model, x, rows=None, cols=None, accumulate=None, wan
 
     x: [N, input_dim] float64.  Returns jac [N, n_rows, n_cols] (accumulate None) or [n_rows, n_cols] ("sum",
     "mean"); with want_y also forward_zero's y [N, output_dim] from the double instantiation of the same template."""
-    import numpy as np
-
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    n = x.shape[0]
-    ra, nr, rp = _index_array(rows)
-    ca, nc, cp = _index_array(cols)
-    nr = nr if rows is not None else m.output_dim
-    nc = nc if cols is not None else m.input_dim
-    acc = JAC_ACCUMULATE[accumulate]
-    jac = np.zeros((n, nr, nc) if acc == 0 else (nr, nc), dtype=np.float64)
-    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
-    _check(lib().tds_hip_jacobian_host(C.byref(m), n, x.ctypes.data, nr, rp, nc, cp, acc,
-                                       y.ctypes.data if want_y else None, jac.ctypes.data))
+    call = functools.partial(lib().tds_hip_jacobian_host, C.byref(m))
+    jac, y = _jacobian(_HostArrays, call, m, x, rows, cols, accumulate, want_y)
     return (jac, y) if want_y else jac
-
-
-def _host_rows(a, n, width):
-    import numpy as np
-
-    if a is None or width == 0:
-        return None, None
-    a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1, width), (n, width)))
-    return a, a.ctypes.data
 
 
 def _host_outputs(shapes, want, out=None, struct=None, dtypes={}):
@@ -610,15 +586,6 @@ def _host_outputs(shapes, want, out=None, struct=None, dtypes={}):
         assert a.dtype == dt and a.flags.c_contiguous and a.shape == shapes[k], k
         res[k] = a
     return res, struct and struct(**{k: a.ctypes.data for k, a in res.items()})
-
-
-def _dev_records(a, width, what, n=None):
-    """a checked as a CUDA float64 tensor [N, width] (N = n where given), contiguous"""
-    import torch
-
-    assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.shape[1] == width, what
-    assert n is None or a.shape[0] == n, what
-    return a.contiguous()
 
 
 def _dev_outputs(shapes, want, out, device, struct=None, dtypes={}):
@@ -638,25 +605,22 @@ def _dev_outputs(shapes, want, out, device, struct=None, dtypes={}):
     return res, struct and struct(**{k: (t if t.numel() else nothing).data_ptr() for k, t in res.items()})
 
 
-def _np_ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def _dev_theta_rows(theta, n, p):
-    import torch
-
-    assert theta.is_cuda and theta.dtype == torch.float64
-    if theta.dim() == 1:
-        theta = theta.unsqueeze(0).expand(n, p)
-    assert tuple(theta.shape) == (n, p), (tuple(theta.shape), n, p)
-    return theta.contiguous()
+def _entries(shape):
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
 
 
 class _HostArrays:
-    """How a query marshals its arguments and results over numpy arrays (the *_host functions); _DevArrays: the same
-    over CUDA tensors (HipSim's methods).  A query written on either is written once (_dynamics_jvp ...)."""
+    """How a call marshals its arguments and results over numpy arrays (the *_host functions); _DevArrays: the same
+    over CUDA tensors (HipSim's and RigidBodySim's methods).  A call written on either is written once (_vjp,
+    _dynamics_jvp ...).  The host side takes array-likes and refuses with ValueError; the device side demands CUDA
+    tensors of the dtype and refuses with AssertionError, or with `error` where a call names another."""
 
-    ptr = staticmethod(_np_ptr)
+    @staticmethod
+    def ptr(a, empty=None):
+        return None if a is None else a.ctypes.data
 
     @staticmethod
     def records(a, width, what):
@@ -666,7 +630,12 @@ class _HostArrays:
 
     @staticmethod
     def rows(a, n, width, what):
-        return _host_rows(a, n, width)
+        import numpy as np
+
+        if a is None or width == 0:
+            return None, None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1, width), (n, width)))
+        return a, a.ctypes.data
 
     @staticmethod
     def directions(v, n, width, width_text=None):
@@ -678,25 +647,75 @@ class _HostArrays:
         return v
 
     @staticmethod
-    def theta(theta, n, p):
-        th = None if theta is None else _theta_rows(theta, n, p)
-        return th, None if p == 0 else _np_ptr(th)
+    def tangents(v, n, width, name):
+        """v [n, width] (K = 1) or [n, K, width] as (the contiguous [n, K, width] array, whether to squeeze K out of
+        the result)"""
+        import numpy as np
+
+        v = np.asarray(v, dtype=np.float64)
+        squeeze = v.ndim == 2
+        v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
+        if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != width:
+            raise ValueError(f"{name}: expected [{n}, K, {width}] or [{n}, {width}], got {tuple(v.shape)}")
+        return v3, squeeze
 
     @staticmethod
-    def outputs(shapes, want, out, like, struct=None):
-        return _host_outputs(shapes, want, out, struct)
+    def exact(a, shape, name, dtype="float64", by_count=False, error=ValueError):
+        """a as a contiguous array of `shape` (None: any; by_count: anything of that many entries)"""
+        import numpy as np
+
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if shape is not None and (_entries(a.shape) != _entries(shape) if by_count else a.shape != tuple(shape)):
+            raise ValueError(f"{name}: expected {list(shape)}, got {list(a.shape)}")
+        return a
+
+    @staticmethod
+    def once(a, n, width, name):
+        """a [width] (every environment) or [n, width] as a contiguous [n, width] array"""
+        import numpy as np
+
+        t = np.asarray(a, dtype=np.float64)
+        if t.ndim == 1:
+            t = np.broadcast_to(t, (n, t.shape[0]))
+        if t.shape != (n, width):
+            raise ValueError(f"{name}: expected [{width}] or [{n}, {width}], got {tuple(np.shape(a))}")
+        return np.ascontiguousarray(t)
+
+    @staticmethod
+    def theta(theta, n, p):
+        th = None if theta is None else _HostArrays.once(theta, n, p, "theta")
+        return th, None if p == 0 else _HostArrays.ptr(th)
+
+    @staticmethod
+    def new(shape, like, dtype="float64", zero=False):
+        import numpy as np
+
+        return np.zeros(shape, dtype=dtype)
+
+    @staticmethod
+    def outputs(shapes, want, out, like, struct=None, dtypes={}):
+        return _host_outputs(shapes, want, out, struct, dtypes)
 
 
 class _DevArrays:
-    records = staticmethod(_dev_records)
-
     @staticmethod
-    def ptr(t):
+    def ptr(t, empty=None):
+        """the address of t; of a tensor without extent NULL, or that of `empty` where the library wants a buffer"""
+        if t is not None and t.numel() == 0:
+            t = empty
         return None if t is None else C.c_void_p(t.data_ptr())
 
     @staticmethod
+    def records(a, width, what, n=None):
+        import torch
+
+        assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.shape[1] == width, what
+        assert n is None or a.shape[0] == n, what
+        return a.contiguous()
+
+    @staticmethod
     def rows(a, n, width, what):
-        a = None if a is None or width == 0 else _dev_records(a, width, what, n)
+        a = None if a is None or width == 0 else _DevArrays.records(a, width, what, n)
         return a, _DevArrays.ptr(a)
 
     @staticmethod
@@ -708,13 +727,203 @@ class _DevArrays:
         return v.contiguous()
 
     @staticmethod
+    def tangents(v, n, width, name):
+        import torch
+
+        squeeze = v.dim() == 2
+        v3 = v.unsqueeze(1) if squeeze else v
+        assert v3.is_cuda and v3.dtype == torch.float64 and v3.dim() == 3 and tuple(v3.shape[::2]) == (n, width), \
+            f"{name}: expected a CUDA float64 tensor [{n}, K, {width}] or [{n}, {width}], got {tuple(v.shape)} {v.dtype}"
+        return v3.contiguous(), squeeze
+
+    @staticmethod
+    def exact(t, shape, name, dtype="float64", by_count=False, error=AssertionError):
+        import torch
+
+        ok = t.is_cuda and t.dtype == getattr(torch, dtype)
+        if ok and shape is not None:
+            ok = t.numel() == _entries(shape) if by_count else tuple(t.shape) == tuple(shape)
+        if not ok:
+            raise error(f"{name}: expected a CUDA {dtype} tensor {'of any shape' if shape is None else list(shape)}, "
+                        f"got {list(t.shape)} {t.dtype}")
+        return t.contiguous()
+
+    @staticmethod
+    def once(t, n, width, name):
+        import torch
+
+        assert t.is_cuda and t.dtype == torch.float64, name
+        if t.dim() == 1:
+            t = t.unsqueeze(0).expand(n, -1)
+        assert tuple(t.shape) == (n, width), (name, tuple(t.shape), n, width)
+        return t.contiguous()
+
+    @staticmethod
     def theta(theta, n, p):
-        th = None if theta is None or p == 0 else _dev_theta_rows(theta, n, p)
+        th = None if theta is None or p == 0 else _DevArrays.once(theta, n, p, "theta")
         return th, _DevArrays.ptr(th)
 
     @staticmethod
-    def outputs(shapes, want, out, like, struct=None):
-        return _dev_outputs(shapes, want, out, like.device, struct)
+    def new(shape, like, dtype="float64", zero=False):
+        import torch
+
+        return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, dtype), device=like.device)
+
+    @staticmethod
+    def outputs(shapes, want, out, like, struct=None, dtypes={}):
+        return _dev_outputs(shapes, want, out, like.device, struct, dtypes)
+
+
+def _tape(A, tape, shape, like):
+    """(lens, the two trailing arguments) of a host call that takes tape = (tape_cap, tape_len): lens int32 of `shape`
+    where tape_len asks for the recorded entries; tape None (the device calls): no such arguments"""
+    if tape is None:
+        return None, ()
+    lens = A.new(shape, like, "int32") if tape[1] else None
+    return lens, (int(tape[0]), A.ptr(lens))
+
+
+def _jacobian(A, call, m, x, rows, cols, accumulate, want_y, y=None, want_jac=True):
+    """(jac, y) of tds_hip_jacobian[_host]; y: a buffer to write forward_zero's output into (None with want_y: a new
+    one); want_jac False: the step alone"""
+    x = A.records(x, m.input_dim, "x")
+    n = x.shape[0]
+    ra, nr, rp = _index_array(rows)
+    ca, nc, cp = _index_array(cols)
+    nr = nr if rows is not None else m.output_dim
+    nc = nc if cols is not None else m.input_dim
+    acc = JAC_ACCUMULATE[accumulate]
+    jac = A.new((n, nr, nc) if acc == 0 else (nr, nc), x) if want_jac else None
+    y = A.outputs({"y": (n, m.output_dim)}, ("y",) if want_y else (), None if y is None else {"y": y}, x)[0].get("y")
+    _check(call(n, A.ptr(x), nr if want_jac else 0, rp, nc if want_jac else 0, cp, acc, A.ptr(y), A.ptr(jac)))
+    return jac, y
+
+
+def _vjp(A, call, m, x, w, want_y, y=None, params=None, theta=None, tape=None):
+    """(y, wj, lens) of the step VJPs: tds_hip_vjp[_host_tape], and with a selection `params` (theta [p] or [N, p])
+    tds_hip_vjp_params[_host], wj then over [x | theta]"""
+    x = A.records(x, m.input_dim, "x")
+    n, p = x.shape[0], 0 if params is None else len(params)
+    w3, squeeze = A.tangents(w, n, m.output_dim, "w")
+    k = w3.shape[1]
+    th = None if params is None else A.once(theta, n, p, "theta")
+    y = A.outputs({"y": (n, m.output_dim)}, ("y",) if want_y else (), None if y is None else {"y": y}, x)[0].get("y")
+    wj = A.new((n, k, m.input_dim + p), x)
+    lens, extra = _tape(A, tape, (n,), x)
+    selection = () if params is None else (p, param_spec(params), A.ptr(th))
+    _check(call(n, A.ptr(x), *selection, k, A.ptr(w3), A.ptr(y), A.ptr(wj), *extra))
+    return y, (wj[:, 0] if squeeze else wj), lens
+
+
+def _jvp_params(A, call, m, x, theta, params, v):
+    """(y, jv) of tds_hip_jvp_params[_host]; v None: jv None"""
+    x = A.records(x, m.input_dim, "x")
+    n, p = x.shape[0], len(params)
+    sel = param_spec(params)
+    th = A.once(theta, n, p, "theta")
+    y = A.new((n, m.output_dim), x)
+    k, v3, jv, squeeze = 0, None, None, False
+    if v is not None:
+        v3, squeeze = A.tangents(v, n, m.input_dim + p, "v")
+        k = v3.shape[1]
+        jv = A.new((n, k, m.output_dim), x)
+    _check(call(n, A.ptr(x), p, sel, A.ptr(th), k, A.ptr(v3), A.ptr(y), A.ptr(jv)))
+    return y, (jv[:, 0] if squeeze else jv)
+
+
+def _trajectory_inputs(A, m, x0, steps, every, u, params, theta):
+    """what the trajectory calls share in front: (x0, n, p, (nsd, n_act, n_rec), u, selection, theta, its pointer, s)"""
+    x0 = A.records(x0, m.input_dim, "x0")
+    n, p = x0.shape[0], len(params)
+    dims = trajectory_dims(m, steps, every)
+    sel = param_spec(params)
+    th, thp = A.theta(theta, n, p)
+    u = None if u is None else A.exact(u, (n, max(int(steps) - 1, 0), dims[1]), "u")
+    s = A.new((n, max(dims[2], 1), dims[0]), x0)
+    return x0, n, p, dims, u, sel, th, thp, s
+
+
+def _trajectory_jvp(A, call, m, x0, v, steps, every, u, params, theta):
+    """(s, js) of tds_hip_trajectory_jvp[_host]; v None: js None"""
+    x0, n, p, (nsd, n_act, n_rec), u, sel, th, thp, s = _trajectory_inputs(A, m, x0, steps, every, u, params, theta)
+    k, v3, js, squeeze = 0, None, None, False
+    if v is not None:
+        v3, squeeze = A.tangents(v, n, m.input_dim + p, "v")
+        k = v3.shape[1]
+        js = A.new((n, k, max(n_rec, 1), nsd), x0)
+    _check(call(n, int(steps), int(every), A.ptr(x0), A.ptr(u), p, sel, thp, k, A.ptr(v3), A.ptr(s), A.ptr(js)))
+    return s, (js[:, 0] if squeeze else js)
+
+
+def _trajectory_vjp(A, call, m, x0, gs, steps, every, u, params, theta, tape=None):
+    """(s, gx0, gu, gtheta, lens) of tds_hip_trajectory_vjp[_host]"""
+    x0, n, p, (nsd, n_act, n_rec), u, sel, th, thp, s = _trajectory_inputs(A, m, x0, steps, every, u, params, theta)
+    gs = A.exact(gs, (n, n_rec, nsd) if n_rec > 0 else None, "gs")  # (a bad steps / every is the library's to refuse)
+    gx0 = A.new((n, m.input_dim), x0)
+    gu = A.new((n, max(int(steps) - 1, 0), max(n_act, 0)), x0, zero=True)
+    gth = A.new((n, p), x0)
+    lens, extra = _tape(A, tape, (n, max(int(steps), 1)), x0)
+    # (the library wants a buffer behind every output: one without extent gets s's address)
+    _check(call(n, int(steps), int(every), A.ptr(x0), A.ptr(u), p, sel, thp, A.ptr(gs), A.ptr(s), A.ptr(gx0),
+                A.ptr(gu, s), A.ptr(gth, s), *extra))
+    return s, gx0, gu, gth, lens
+
+
+def _policy_trajectory_vjp(A, call, m, x0, policy, gs, steps, every, ga, network, params, theta, first_obs_raw, obs_raw,
+                           tape=None):
+    """(s, u, gpolicy, gx0, gtheta, lens) of tds_hip_policy_trajectory_vjp[_host]; network: (layer_sizes, activations,
+    use_bias); gs and ga both None: the primal alone, the gradients None"""
+    x0, n, p, (nsd, n_act, n_rec), _, sel, th, thp, s = _trajectory_inputs(A, m, x0, steps, every, None, params, theta)
+    nl, ls, act, ub, P = policy_network_spec(m, *network)
+    policy = A.once(policy, n, P, "policy")
+    T = max(int(steps), 0)
+    gs = None if gs is None else A.exact(gs, (n, n_rec, nsd) if n_rec > 0 else None, "gs")
+    ga = None if ga is None else A.exact(ga, (n, T, n_act) if T > 0 else None, "ga")
+    grad = gs is not None or ga is not None
+    # (a model without actions is refused by the library, not here: u and gtheta have an entry at least, and an
+    # argument without extent, the policy of such a model, gets s's address)
+    u = A.new((n, max(T, 1), max(n_act, 1)), x0)
+    gpol, gx0, gth = (A.new(shape, x0) for shape in ((n, P), (n, m.input_dim), (n, max(p, 1)))) if grad else (None,) * 3
+    lens, extra = _tape(A, tape, (n, max(T, 1)), x0)
+    flags = (1 if first_obs_raw else 0) | (2 if obs_raw else 0)
+    host = _HostArrays.ptr  # (the network's int32 arrays live on the host for either call)
+    ptrs = [A.ptr(t, s) for t in (gs, ga, s, u, gpol, gx0, gth)]
+    _check(call(n, int(steps), int(every), flags, A.ptr(x0, s), A.ptr(policy, s), nl, host(ls), host(act), host(ub), p,
+                sel, thp, *ptrs, *extra))
+    return s, u[:, :T, :max(n_act, 0)], gpol, gx0, (gth[:, :p] if grad else None), lens
+
+
+def _rb_jvp(A, call, m, s0, steps, v, params, theta):
+    """(s_T, jv) of tds_rb_jvp[_host]; v None: jv None"""
+    nb, nc = m.num_bodies, _model.TDS_RB_STATE
+    s0 = A.exact(s0, None, "s0").reshape(-1, nb, nc)
+    n, p = s0.shape[0], len(params)
+    sel = param_spec(params)
+    th, thp = A.theta(theta, n, p)
+    sT = A.new(tuple(s0.shape), s0)
+    k, v3, jv, squeeze = 0, None, None, False
+    if v is not None:
+        v3, squeeze = A.tangents(v, n, nb * nc + p, "v")
+        k = v3.shape[1]
+        jv = A.new((n, k, nb, nc), s0)
+    _rb_check(call(n, int(steps), A.ptr(s0), p, sel, thp, k, A.ptr(v3), A.ptr(sT), A.ptr(jv)))
+    return sT, (jv[:, 0] if squeeze else jv)
+
+
+def _rb_vjp(A, call, m, s0, steps, gs, params, theta, every, *budget):
+    """(s, gs0, gtheta) of tds_rb_vjp[_host]; budget: tape_cap, and on the device work_bytes"""
+    nb, nc = m.num_bodies, _model.TDS_RB_STATE
+    s0 = A.exact(s0, None, "s0").reshape(-1, nb, nc)
+    n, p = s0.shape[0], len(params)
+    every = int(steps) if every is None else int(every)  # (None: the final state alone)
+    n_rec = int(steps) // every if every >= 1 and steps >= 1 else 1
+    gs = A.exact(gs, (n, n_rec, nb * nc), "gs", by_count=True)
+    sel = param_spec(params)
+    th, thp = A.theta(theta, n, p)
+    s, gs0, gth = A.new((n, n_rec, nb, nc), s0), A.new(tuple(s0.shape), s0), A.new((n, p), s0)
+    _rb_check(call(n, int(steps), every, A.ptr(s0), p, sel, thp, A.ptr(gs), A.ptr(s), A.ptr(gs0), A.ptr(gth),
+                   *(int(b) for b in budget)))
+    return s, gs0, gth
 
 
 def _dynamics(A, call, m, q, qd, tau, want, out):
@@ -934,18 +1143,27 @@ def inverse_kinematics_host(m: _model.Model, q_init, links, targets, body_points
     IK_CONVERGED / IK_REACHED), residual [N] float64."""
     import numpy as np
 
-    q_init = np.ascontiguousarray(q_init, dtype=np.float64).reshape(-1, m.dof_q)
+    q_init = _HostArrays.records(q_init, m.dof_q, "q_init")
+    n, k = q_init.shape[0], np.size(links)
+    targets = np.broadcast_to(np.asarray(targets, dtype=np.float64).reshape((-1, k, 3) if k else (n, 0, 3)), (n, k, 3))
+    call = functools.partial(lib().tds_hip_inverse_kinematics_host, C.byref(m))
+    return _inverse_kinematics(_HostArrays, call, m, q_init, links, targets, body_points, q_reference, None,
+                               ik_options(method, **options))
+
+
+def _inverse_kinematics(A, call, m, q_init, links, targets, body_points, q_reference, out, options):
+    """the dict of tds_hip_inverse_kinematics[_host]'s outputs; out: a dict of buffers to write into, and one that
+    leaves iterations, status or residual out has those not computed"""
+    q_init = A.records(q_init, m.dof_q, "q_init")
     n = q_init.shape[0]
     k, links, pts, lp, pp = _ik_targets(links, body_points)
-    targets = np.asarray(targets, dtype=np.float64).reshape((-1, k, 3) if k else (n, 0, 3))
-    targets = np.ascontiguousarray(np.broadcast_to(targets, (n, k, 3)))
-    qr, qrp = _host_rows(q_reference, n, m.dof_q)
-    o = ik_options(method, **options)
+    targets = A.exact(targets, (n, k, 3), "targets")
+    q_reference, qrp = A.rows(q_reference, n, m.dof_q, "q_reference")
+    assert out is None or "q" in out, "out must hold q"
     shapes = _ik_shapes(m, n)
-    res, _ = _host_outputs(shapes, shapes, dtypes=_IK_DTYPES)
-    _check(lib().tds_hip_inverse_kinematics_host(C.byref(m), n, q_init.ctypes.data, k, lp, pp, targets.ctypes.data, qrp,
-                                                 C.byref(o), res["q"].ctypes.data, res["iterations"].ctypes.data,
-                                                 res["status"].ctypes.data, res["residual"].ctypes.data))
+    res, _ = A.outputs(shapes, [name for name in shapes if out is None or name in out], out, q_init, dtypes=_IK_DTYPES)
+    _check(call(n, A.ptr(q_init), k, lp, pp, A.ptr(targets), qrp, C.byref(options), A.ptr(res["q"]),
+                A.ptr(res.get("iterations")), A.ptr(res.get("status")), A.ptr(res.get("residual"))))
     return res
 
 
@@ -954,12 +1172,31 @@ LQR_MAX_NX, LQR_MAX_NU = 40, 16
 
 
 def _lqr_shapes(A, B):
-    """(n, T, nx, nu) from A [n, T, nx, nx] and B [n, T, nx, nu], and the shapes of the other inputs by name"""
+    """(n, T, nx, nu) from A [n, T, nx, nx] and B [n, T, nx, nu], and the shapes of a backward pass's inputs by name,
+    in the order the library takes them"""
     if len(A.shape) != 4 or len(B.shape) != 4 or A.shape[2] != A.shape[3] or tuple(B.shape[:3]) != tuple(A.shape[:3]):
         raise ValueError(f"A: expected [n, T, nx, nx] and B [n, T, nx, nu], got {tuple(A.shape)} and {tuple(B.shape)}")
     n, T, nx, nu = int(A.shape[0]), int(A.shape[1]), int(A.shape[2]), int(B.shape[3])
-    return (n, T, nx, nu), {"lx": (n, T + 1, nx), "lu": (n, T, nu), "lxx": (n, T + 1, nx, nx), "luu": (n, T, nu, nu),
-                            "lux": (n, T, nu, nx), "mu": (n,)}
+    return (n, T, nx, nu), {"A": (n, T, nx, nx), "B": (n, T, nx, nu), "lx": (n, T + 1, nx), "lu": (n, T, nu),
+                            "lxx": (n, T + 1, nx, nx), "luu": (n, T, nu, nu), "lux": (n, T, nu, nx), "mu": (n,),
+                            "dlo": (n, T, nu), "dhi": (n, T, nu)}
+
+
+def _lqr_backward(X, call, check, A, B, lx, lu, lxx, luu, lux, mu, dlo=None, dhi=None):
+    """(k, K, dv, status) of tds_hip_lqr_backward[_host]; with the bounds dlo, dhi the box form `call` then is: its two
+    inputs more, and (.., clamped, qp_iterations).  check: dlo <= dhi is verified here (on the device a host wait)"""
+    (n, T, nx, nu), shapes = _lqr_shapes(A, B)
+    arg = {"A": A, "B": B, "lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux, "mu": mu}
+    if dlo is not None:
+        arg.update(dlo=dlo, dhi=dhi)
+    arg = {key: X.exact(a, shapes[key], key, error=ValueError) for key, a in arg.items()}
+    if dlo is not None and check:
+        _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
+    out = [X.new((n, T, nu), A), X.new((n, T, nu, nx), A), X.new((n, 2), A), X.new((n,), A, "int32")]
+    if dlo is not None:
+        out += [X.new((n, T), A, "int32"), X.new((n, T), A, "int32")]
+    _check(call(n, T, nx, nu, *(X.ptr(a) for a in arg.values()), *(X.ptr(t) for t in out)))
+    return tuple(out)
 
 
 def lqr_backward_host(A, B, lx, lu, lxx, luu, lux, mu):
@@ -968,22 +1205,16 @@ def lqr_backward_host(A, B, lx, lu, lxx, luu, lux, mu):
     lxx [n, T + 1, nx, nx], luu [n, T, nu, nu], lux [n, T, nu, nx], mu [n] (or a scalar).  Returns (k [n, T, nu],
     K [n, T, nu, nx], dv [n, 2], status [n] int32): status t + 1 where the Cholesky of Q_uu + mu I failed at step t
     (that problem's gains and dv are zero), else 0."""
+    A, B, mu = _lqr_host_arrays(A, B, mu)
+    return _lqr_backward(_HostArrays, lib().tds_hip_lqr_backward_host, True, A, B, lx, lu, lxx, luu, lux, mu)
+
+
+def _lqr_host_arrays(A, B, mu):
+    """what the host forms accept beyond the device's: array-likes, and a scalar mu"""
     import numpy as np
 
     A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
-    (n, T, nx, nu), shapes = _lqr_shapes(A, B)
-    arg = {"lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux,
-           "mu": np.broadcast_to(np.asarray(mu, dtype=np.float64), (n,))}
-    for key, shape in shapes.items():
-        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
-        if arg[key].shape != shape:
-            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
-    k, K = np.zeros((n, T, nu)), np.zeros((n, T, nu, nx))
-    dv, status = np.zeros((n, 2)), np.zeros(n, dtype=np.int32)
-    _check(lib().tds_hip_lqr_backward_host(n, T, nx, nu, A.ctypes.data, B.ctypes.data,
-                                           *(arg[key].ctypes.data for key in ("lx", "lu", "lxx", "luu", "lux", "mu")),
-                                           k.ctypes.data, K.ctypes.data, dv.ctypes.data, status.ctypes.data))
-    return k, K, dv, status
+    return A, B, np.broadcast_to(np.asarray(mu, dtype=np.float64), A.shape[:1])
 
 
 def _bounds_ordered(lo, hi, names):
@@ -999,38 +1230,39 @@ def lqr_backward_box_host(A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi):
     the unconstrained solve, feedback gains on the controls it left free (include/tds_hip.h states it).  Returns
     (k, K, dv, status, clamped [n, T] int32 -- bit a set: control a clamped in the QP's final set --, qp_iterations
     [n, T] int32).  Infinite bounds give lqr_backward_host's k, K, dv, status bit for bit."""
-    import numpy as np
-
-    A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
-    (n, T, nx, nu), shapes = _lqr_shapes(A, B)
-    shapes.update({"dlo": (n, T, nu), "dhi": (n, T, nu)})
-    arg = {"lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux,
-           "mu": np.broadcast_to(np.asarray(mu, dtype=np.float64), (n,)), "dlo": dlo, "dhi": dhi}
-    for key, shape in shapes.items():
-        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
-        if arg[key].shape != shape:
-            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
-    _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
-    k, K = np.zeros((n, T, nu)), np.zeros((n, T, nu, nx))
-    dv, status = np.zeros((n, 2)), np.zeros(n, dtype=np.int32)
-    clamped, its = np.zeros((n, T), dtype=np.int32), np.zeros((n, T), dtype=np.int32)
-    _check(lib().tds_hip_lqr_backward_box_host(
-        n, T, nx, nu, A.ctypes.data, B.ctypes.data,
-        *(arg[key].ctypes.data for key in ("lx", "lu", "lxx", "luu", "lux", "mu", "dlo", "dhi")),
-        k.ctypes.data, K.ctypes.data, dv.ctypes.data, status.ctypes.data, clamped.ctypes.data, its.ctypes.data))
-    return k, K, dv, status, clamped, its
+    A, B, mu = _lqr_host_arrays(A, B, mu)
+    return _lqr_backward(_HostArrays, lib().tds_hip_lqr_backward_box_host, True, A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi)
 
 
-def _feedback_shapes(m, x0, s_nom):
-    """(rows, P, T) and the shapes of a feedback rollout's inputs by name"""
+def _feedback_rollout(X, calls, check_map, check_bounds, m, x0, s_nom, u_nom, k, K, alpha, problem_of_row, u_lo, u_hi):
+    """(s, u) of tds_hip_feedback_rollout[_host], and with the limits u_lo, u_hi of its box form: calls = (the plain
+    entry point, the box one), each taking (rows, T, P, the pointers).  check_map: the entries of problem_of_row are
+    verified here, check_bounds: u_lo <= u_hi is (on the device a host wait each)"""
     nsd, n_act, _ = trajectory_dims(m, 1)
     if len(x0.shape) != 2 or x0.shape[1] != m.input_dim:
         raise ValueError(f"x0: expected [rows, {m.input_dim}], got {list(x0.shape)}")
     if len(s_nom.shape) != 3 or s_nom.shape[1] < 2 or s_nom.shape[2] != nsd:
         raise ValueError(f"s_nom: expected [P, T + 1, {nsd}] with T >= 1, got {list(s_nom.shape)}")
     rows, P, T = int(x0.shape[0]), int(s_nom.shape[0]), int(s_nom.shape[1]) - 1
-    return (rows, P, T, nsd, n_act), {"u_nom": (P, T, n_act), "k": (P, T, n_act), "K": (P, T, n_act, nsd),
-                                      "alpha": (rows,)}
+    if (u_lo is None) != (u_hi is None):
+        raise ValueError("u_lo and u_hi are given together or not at all")
+    arg = {"x0": (x0, (rows, m.input_dim)), "s_nom": (s_nom, (P, T + 1, nsd)), "u_nom": (u_nom, (P, T, n_act)),
+           "k": (k, (P, T, n_act)), "K": (K, (P, T, n_act, nsd)), "alpha": (alpha, (rows,))}
+    if u_lo is not None:
+        arg.update(u_lo=(u_lo, (P, T, n_act)), u_hi=(u_hi, (P, T, n_act)))
+    arg = {key: X.exact(a, shape, key, error=ValueError) for key, (a, shape) in arg.items()}
+    if problem_of_row is not None:
+        problem_of_row = X.exact(problem_of_row, (rows,), "problem_of_row", "int32", error=ValueError)
+        if check_map and not (0 <= int(problem_of_row.min()) and int(problem_of_row.max()) < P):
+            raise ValueError(f"problem_of_row: entries outside [0, {P})")
+    elif rows != P:
+        raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
+    if u_lo is not None and check_bounds:
+        _bounds_ordered(arg["u_lo"], arg["u_hi"], ("u_lo", "u_hi"))
+    s, u = X.new((rows, T + 1, nsd), x0), X.new((rows, T, n_act), x0)
+    inputs = [X.ptr(a) for a in arg.values()]
+    _check(calls[u_lo is not None](rows, T, P, *inputs[:6], X.ptr(problem_of_row), *inputs[6:], X.ptr(s), X.ptr(u)))
+    return s, u
 
 
 def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, problem_of_row=None, u_lo=None,
@@ -1044,38 +1276,15 @@ def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, pr
     u [rows, T, n_act])."""
     import numpy as np
 
+    # (what the host form accepts beyond the device's: array-likes, a scalar alpha, any integers in problem_of_row,
+    # whose range the library checks)
     x0, s_nom = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(s_nom, dtype=np.float64)
-    (rows, P, T, nsd, n_act), shapes = _feedback_shapes(m, x0, s_nom)
-    arg = {"u_nom": u_nom, "k": k, "K": K, "alpha": np.broadcast_to(np.asarray(alpha, dtype=np.float64), (rows,))}
-    for key, shape in shapes.items():
-        arg[key] = np.ascontiguousarray(arg[key], dtype=np.float64)
-        if arg[key].shape != shape:
-            raise ValueError(f"{key}: expected {list(shape)}, got {list(arg[key].shape)}")
-    por = None
+    alpha = np.broadcast_to(np.asarray(alpha, dtype=np.float64), x0.shape[:1])
     if problem_of_row is not None:
-        por = np.ascontiguousarray(np.asarray(problem_of_row, dtype=np.int64).reshape(-1).astype(np.int32))
-        if por.shape != (rows,):
-            raise ValueError(f"problem_of_row: expected [{rows}], got {list(por.shape)}")
-    elif rows != P:
-        raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
-    s, u = np.zeros((rows, T + 1, nsd)), np.zeros((rows, T, n_act))
-    if (u_lo is None) != (u_hi is None):
-        raise ValueError("u_lo and u_hi are given together or not at all")
-    if u_lo is not None:
-        lim = {"u_lo": np.ascontiguousarray(u_lo, dtype=np.float64), "u_hi": np.ascontiguousarray(u_hi, dtype=np.float64)}
-        for key, a in lim.items():
-            if a.shape != (P, T, n_act):
-                raise ValueError(f"{key}: expected {[P, T, n_act]}, got {list(a.shape)}")
-        _bounds_ordered(lim["u_lo"], lim["u_hi"], ("u_lo", "u_hi"))
-        _check(lib().tds_hip_feedback_rollout_box_host(
-            C.byref(m), rows, T, P, x0.ctypes.data, s_nom.ctypes.data,
-            *(arg[key].ctypes.data for key in ("u_nom", "k", "K", "alpha")), None if por is None else por.ctypes.data,
-            lim["u_lo"].ctypes.data, lim["u_hi"].ctypes.data, s.ctypes.data, u.ctypes.data))
-        return s, u
-    _check(lib().tds_hip_feedback_rollout_host(C.byref(m), rows, T, P, x0.ctypes.data, s_nom.ctypes.data,
-                                               *(arg[key].ctypes.data for key in ("u_nom", "k", "K", "alpha")),
-                                               None if por is None else por.ctypes.data, s.ctypes.data, u.ctypes.data))
-    return s, u
+        problem_of_row = np.asarray(problem_of_row, dtype=np.int64).reshape(-1).astype(np.int32)
+    calls = [functools.partial(f, C.byref(m)) for f in (lib().tds_hip_feedback_rollout_host,
+                                                        lib().tds_hip_feedback_rollout_box_host)]
+    return _feedback_rollout(_HostArrays, calls, False, True, m, x0, s_nom, u_nom, k, K, alpha, problem_of_row, u_lo, u_hi)
 
 
 def trajectory_records(m: _model.Model, x0, s, u):
@@ -1101,13 +1310,8 @@ def trajectory_records(m: _model.Model, x0, s, u):
 
 def step_host(m: _model.Model, x):
     """forward_zero through the double instantiation of the step Jacobians' template (CPU)"""
-    import numpy as np
-
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    y = np.zeros((x.shape[0], m.output_dim), dtype=np.float64)
-    _check(lib().tds_hip_jacobian_host(C.byref(m), x.shape[0], x.ctypes.data, 0, None, 0, None, 0, y.ctypes.data,
-                                       None))
-    return y
+    call = functools.partial(lib().tds_hip_jacobian_host, C.byref(m))
+    return _jacobian(_HostArrays, call, m, x, None, None, None, True, want_jac=False)[1]
 
 
 def vjp_host(m: _model.Model, x, w, want_y: bool = False, tape_cap: int = 0, tape_len: bool = False):
@@ -1117,27 +1321,9 @@ def vjp_host(m: _model.Model, x, w, want_y: bool = False, tape_cap: int = 0, tap
     (or [N, input_dim]); with want_y also forward_zero's y [N, output_dim].  tape_cap > 0 replaces the model class's
     tape capacity, and tape_len adds the entries each environment recorded (-1: overflowed) to what is returned
     (tds_hip_vjp_host_tape)."""
-    import numpy as np
-
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    n = x.shape[0]
-    w = np.asarray(w, dtype=np.float64)
-    squeeze = w.ndim == 2
-    w3 = np.ascontiguousarray(w[:, None] if squeeze else w)
-    if w3.ndim != 3 or w3.shape[0] != n or w3.shape[2] != m.output_dim:
-        raise ValueError(f"w: expected [{n}, K, {m.output_dim}] or [{n}, {m.output_dim}], got {tuple(w.shape)}")
-    k = w3.shape[1]
-    wj = np.zeros((n, k, m.input_dim), dtype=np.float64)
-    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
-    lens = np.zeros(n, dtype=np.int32) if tape_len else None
-    _check(lib().tds_hip_vjp_host_tape(C.byref(m), n, x.ctypes.data, k, w3.ctypes.data,
-                                       y.ctypes.data if want_y else None, wj.ctypes.data, int(tape_cap),
-                                       lens.ctypes.data if tape_len else None))
-    out = (wj[:, 0] if squeeze else wj,)
-    if want_y:
-        out += (y,)
-    if tape_len:
-        out += (lens,)
+    call = functools.partial(lib().tds_hip_vjp_host_tape, C.byref(m))
+    y, wj, lens = _vjp(_HostArrays, call, m, x, w, want_y, tape=(tape_cap, tape_len))
+    out = (wj,) + ((y,) if want_y else ()) + ((lens,) if tape_len else ())
     return out if len(out) > 1 else out[0]
 
 
@@ -1202,46 +1388,15 @@ def model_variants_host(m: _model.Model, params, theta, env_variant=None, num_en
     return int(nbytes.value)
 
 
-def _theta_rows(theta, n, p):
-    """theta [p] (every environment) or [n, p] as a contiguous [n, p] float64 array"""
-    import numpy as np
-
-    t = np.asarray(theta, dtype=np.float64)
-    if t.ndim == 1:
-        t = np.broadcast_to(t, (n, t.shape[0]))
-    if t.shape != (n, p):
-        raise ValueError(f"theta: expected [{p}] or [{n}, {p}], got {tuple(np.shape(theta))}")
-    return np.ascontiguousarray(t)
-
-
 def jvp_params_host(m: _model.Model, x, theta, params, v=None, want_y: bool = False):
     """Forward mode in [x | theta] on the CPU (tds_hip_jvp_params_host; needs no GPU).
 
     x [N, input_dim], theta [p] or [N, p] (the selected parameters' values), v [N, K, input_dim + p] or
     [N, input_dim + p] (K = 1).  Returns jv = J v [N, K, output_dim] (or [N, output_dim]), with want_y also y
     [N, output_dim]; v None: y alone."""
-    import numpy as np
-
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x.shape[0], len(params)
-    sel = param_spec(params)
-    th = _theta_rows(theta, n, p)
-    y = np.zeros((n, m.output_dim), dtype=np.float64)
-    if v is None:
-        _check(lib().tds_hip_jvp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, 0, None,
-                                             y.ctypes.data, None))
-        return y
-    v = np.asarray(v, dtype=np.float64)
-    squeeze = v.ndim == 2
-    v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
-    if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != m.input_dim + p:
-        raise ValueError(f"v: expected [{n}, K, {m.input_dim + p}], got {tuple(v.shape)}")
-    k = v3.shape[1]
-    jv = np.zeros((n, k, m.output_dim), dtype=np.float64)
-    _check(lib().tds_hip_jvp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, k, v3.ctypes.data,
-                                         y.ctypes.data, jv.ctypes.data))
-    jv = jv[:, 0] if squeeze else jv
-    return (jv, y) if want_y else jv
+    call = functools.partial(lib().tds_hip_jvp_params_host, C.byref(m))
+    y, jv = _jvp_params(_HostArrays, call, m, x, theta, params, v)
+    return y if v is None else (jv, y) if want_y else jv
 
 
 def vjp_params_host(m: _model.Model, x, theta, params, w, want_y: bool = False, tape_cap: int = 0,
@@ -1250,29 +1405,9 @@ def vjp_params_host(m: _model.Model, x, theta, params, w, want_y: bool = False, 
 
     x [N, input_dim], theta [p] or [N, p], w [N, K, output_dim] or [N, output_dim].  Returns wj = w^T J
     [N, K, input_dim + p] (or [N, input_dim + p]), the x part first; want_y, tape_cap and tape_len as for vjp_host."""
-    import numpy as np
-
-    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x.shape[0], len(params)
-    sel = param_spec(params)
-    th = _theta_rows(theta, n, p)
-    w = np.asarray(w, dtype=np.float64)
-    squeeze = w.ndim == 2
-    w3 = np.ascontiguousarray(w[:, None] if squeeze else w)
-    if w3.ndim != 3 or w3.shape[0] != n or w3.shape[2] != m.output_dim:
-        raise ValueError(f"w: expected [{n}, K, {m.output_dim}] or [{n}, {m.output_dim}], got {tuple(w.shape)}")
-    k = w3.shape[1]
-    wj = np.zeros((n, k, m.input_dim + p), dtype=np.float64)
-    y = np.zeros((n, m.output_dim), dtype=np.float64) if want_y else None
-    lens = np.zeros(n, dtype=np.int32) if tape_len else None
-    _check(lib().tds_hip_vjp_params_host(C.byref(m), n, x.ctypes.data, p, sel, th.ctypes.data, k, w3.ctypes.data,
-                                         y.ctypes.data if want_y else None, wj.ctypes.data, int(tape_cap),
-                                         lens.ctypes.data if tape_len else None))
-    out = (wj[:, 0] if squeeze else wj,)
-    if want_y:
-        out += (y,)
-    if tape_len:
-        out += (lens,)
+    call = functools.partial(lib().tds_hip_vjp_params_host, C.byref(m))
+    y, wj, lens = _vjp(_HostArrays, call, m, x, w, want_y, None, params, theta, (tape_cap, tape_len))
+    out = (wj,) + ((y,) if want_y else ()) + ((lens,) if tape_len else ())
     return out if len(out) > 1 else out[0]
 
 
@@ -1290,36 +1425,8 @@ def trajectory_jvp_host(m: _model.Model, x0, v=None, steps: int = 1, every: int 
     x0 [N, input_dim], u None or [N, steps - 1, n_act], theta None (the model's values), [p] or [N, p], v
     [N, K, input_dim + p] (or [N, input_dim + p]: K = 1).  Returns (s, js): s [N, n_rec, nq + nd], js
     [N, K, n_rec, nq + nd] (or [N, n_rec, nq + nd]); v None: js None."""
-    import numpy as np
-
-    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x0.shape[0], len(params)
-    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    up = None
-    if u is not None:
-        u = np.ascontiguousarray(u, dtype=np.float64)
-        if u.shape != (n, max(int(steps) - 1, 0), n_act):
-            raise ValueError(f"u: expected [{n}, {int(steps) - 1}, {n_act}], got {tuple(u.shape)}")
-        up = u.ctypes.data
-    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
-    k, v3, js, squeeze = 0, None, None, False
-    if v is not None:
-        v = np.asarray(v, dtype=np.float64)
-        squeeze = v.ndim == 2
-        v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
-        if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != m.input_dim + p:
-            raise ValueError(f"v: expected [{n}, K, {m.input_dim + p}], got {tuple(v.shape)}")
-        k = v3.shape[1]
-        js = np.zeros((n, k, max(n_rec, 1), nsd), dtype=np.float64)
-    _check(lib().tds_hip_trajectory_jvp_host(C.byref(m), n, int(steps), int(every), x0.ctypes.data, up, p, sel,
-                                             None if th is None else th.ctypes.data, k,
-                                             None if v3 is None else v3.ctypes.data, s.ctypes.data,
-                                             None if js is None else js.ctypes.data))
-    if js is not None and squeeze:
-        js = js[:, 0]
-    return s, js
+    call = functools.partial(lib().tds_hip_trajectory_jvp_host, C.byref(m))
+    return _trajectory_jvp(_HostArrays, call, m, x0, v, steps, every, u, params, theta)
 
 
 def trajectory_vjp_host(m: _model.Model, x0, gs, steps: int, every: int = 1, u=None, params=(), theta=None,
@@ -1331,32 +1438,9 @@ def trajectory_vjp_host(m: _model.Model, x0, gs, steps: int, every: int = 1, u=N
     Returns (s, gx0, gu, gtheta): s [N, n_rec, nq + nd], gx0 [N, input_dim], gu [N, steps - 1, n_act] (zeros where u is
     None) and gtheta [N, p]; with tape_len also the entries each step recorded [N, steps] (-1: overflowed).  tape_cap
     as for vjp_host."""
-    import numpy as np
-
-    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x0.shape[0], len(params)
-    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    up = None
-    if u is not None:
-        u = np.ascontiguousarray(u, dtype=np.float64)
-        if u.shape != (n, max(int(steps) - 1, 0), n_act):
-            raise ValueError(f"u: expected [{n}, {int(steps) - 1}, {n_act}], got {tuple(u.shape)}")
-        up = u.ctypes.data
-    gs = np.ascontiguousarray(gs, dtype=np.float64)
-    if n_rec > 0 and gs.shape != (n, n_rec, nsd):
-        raise ValueError(f"gs: expected [{n}, {n_rec}, {nsd}], got {tuple(gs.shape)}")
-    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
-    gx0 = np.zeros((n, m.input_dim), dtype=np.float64)
-    gu = np.zeros((n, max(int(steps) - 1, 0), max(n_act, 0)), dtype=np.float64)
-    gth = np.zeros((n, p), dtype=np.float64)
-    lens = np.zeros((n, max(int(steps), 1)), dtype=np.int32) if tape_len else None
-    _check(lib().tds_hip_trajectory_vjp_host(C.byref(m), n, int(steps), int(every), x0.ctypes.data, up, p, sel,
-                                             None if th is None else th.ctypes.data, gs.ctypes.data, s.ctypes.data,
-                                             gx0.ctypes.data, gu.ctypes.data, gth.ctypes.data, int(tape_cap),
-                                             lens.ctypes.data if tape_len else None))
-    return (s, gx0, gu, gth, lens) if tape_len else (s, gx0, gu, gth)
+    call = functools.partial(lib().tds_hip_trajectory_vjp_host, C.byref(m))
+    out = _trajectory_vjp(_HostArrays, call, m, x0, gs, steps, every, u, params, theta, (tape_cap, tape_len))
+    return out if tape_len else out[:4]
 
 
 def policy_network_spec(m: _model.Model, layer_sizes=None, activations=None, use_bias=None):
@@ -1392,47 +1476,10 @@ def policy_trajectory_vjp_host(m: _model.Model, x0, policy, gs, steps: int, ever
     [N, n_rec, nq + nd], ga None or [N, steps, n_act]; the network as for policy_network_spec; params and theta as for
     trajectory_vjp_host.  Returns (s, u, gpolicy, gx0, gtheta), with tape_len also the entries each step recorded
     [N, steps]; gs and ga both None: (s, u), the primal alone."""
-    import numpy as np
-
-    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, m.input_dim)
-    n, p = x0.shape[0], len(params)
-    nsd, n_act, n_rec = trajectory_dims(m, steps, every)
-    nl, ls, act, ub, P = policy_network_spec(m, layer_sizes, activations, use_bias)
-    pol = np.asarray(policy, dtype=np.float64)
-    if pol.ndim == 1:
-        pol = np.broadcast_to(pol, (n, pol.shape[0]))
-    if pol.shape != (n, P):
-        raise ValueError(f"policy: expected [{P}] or [{n}, {P}], got {tuple(np.shape(policy))}")
-    pol = np.ascontiguousarray(pol)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    T = max(int(steps), 0)
-    if gs is not None:
-        gs = np.ascontiguousarray(gs, dtype=np.float64)
-        if n_rec > 0 and gs.shape != (n, n_rec, nsd):
-            raise ValueError(f"gs: expected [{n}, {n_rec}, {nsd}], got {tuple(gs.shape)}")
-    if ga is not None:
-        ga = np.ascontiguousarray(ga, dtype=np.float64)
-        if T > 0 and ga.shape != (n, T, n_act):
-            raise ValueError(f"ga: expected [{n}, {T}, {n_act}], got {tuple(ga.shape)}")
-    grad = gs is not None or ga is not None
-    s = np.zeros((n, max(n_rec, 1), nsd), dtype=np.float64)
-    u = np.zeros((n, max(T, 1), max(n_act, 1)), dtype=np.float64)
-    gpol = np.zeros((n, P), dtype=np.float64)
-    gx0 = np.zeros((n, m.input_dim), dtype=np.float64)
-    gth = np.zeros((n, max(p, 1)), dtype=np.float64)
-    lens = np.zeros((n, max(T, 1)), dtype=np.int32) if tape_len else None
-    flags = (1 if first_obs_raw else 0) | (2 if obs_raw else 0)
-    _check(lib().tds_hip_policy_trajectory_vjp_host(
-        C.byref(m), n, int(steps), int(every), flags, x0.ctypes.data, pol.ctypes.data, nl, _np_ptr(ls), _np_ptr(act),
-        _np_ptr(ub), p, sel, _np_ptr(th), _np_ptr(gs), _np_ptr(ga), s.ctypes.data, u.ctypes.data,
-        gpol.ctypes.data if grad else None, gx0.ctypes.data if grad else None, gth.ctypes.data if grad else None,
-        int(tape_cap), _np_ptr(lens)))
-    u = u[:, :T, :max(n_act, 0)]
-    if not grad:
-        return s, u
-    out = (s, u, gpol, gx0, gth[:, :p])
-    return out + (lens,) if tape_len else out
+    call = functools.partial(lib().tds_hip_policy_trajectory_vjp_host, C.byref(m))
+    out = _policy_trajectory_vjp(_HostArrays, call, m, x0, policy, gs, steps, every, ga, (layer_sizes, activations, use_bias),
+                                 params, theta, first_obs_raw, obs_raw, (tape_cap, tape_len))
+    return out[:2] if gs is None and ga is None else out if tape_len else out[:5]
 
 
 def trajectory_directions(input_dim: int, wrt, p: int = 0, device=None):
@@ -1473,35 +1520,8 @@ def rb_jvp_host(m: _model.RbModel, s0, steps: int, v=None, params=(), theta=None
     s0 [N, num_bodies, 13], v [N, K, num_bodies * 13 + p] (or [N, num_bodies * 13 + p]: K = 1), theta None (the model's
     values), [p] or [N, p].  Returns s_T [N, num_bodies, 13] (v None) or (s_T, jv), jv [N, K, num_bodies, 13] (or
     [N, num_bodies, 13])."""
-    import numpy as np
-
-    nb = m.num_bodies
-    ns = nb * _model.TDS_RB_STATE
-    s0 = np.ascontiguousarray(s0, dtype=np.float64).reshape(-1, nb, _model.TDS_RB_STATE)
-    n, p = s0.shape[0], len(params)
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    thp = None if th is None else th.ctypes.data
-    sT = np.zeros_like(s0)
-    if v is None:
-        _rb_check(lib().tds_rb_jvp_host(C.byref(m), n, int(steps), s0.ctypes.data, p, sel, thp, 0, None,
-                                        sT.ctypes.data, None))
-        return sT
-    v = np.asarray(v, dtype=np.float64)
-    squeeze = v.ndim == 2
-    v3 = np.ascontiguousarray(v[:, None] if squeeze else v)
-    if v3.ndim != 3 or v3.shape[0] != n or v3.shape[2] != ns + p:
-        raise ValueError(f"v: expected [{n}, K, {ns + p}], got {tuple(v.shape)}")
-    k = v3.shape[1]
-    jv = np.zeros((n, k, nb, _model.TDS_RB_STATE), dtype=np.float64)
-    _rb_check(lib().tds_rb_jvp_host(C.byref(m), n, int(steps), s0.ctypes.data, p, sel, thp, k, v3.ctypes.data,
-                                    sT.ctypes.data, jv.ctypes.data))
-    return sT, (jv[:, 0] if squeeze else jv)
-
-
-def _rb_every(steps, every):
-    """every None: the final state alone (every = steps)"""
-    return int(steps) if every is None else int(every)
+    sT, jv = _rb_jvp(_HostArrays, functools.partial(lib().tds_rb_jvp_host, C.byref(m)), m, s0, steps, v, params, theta)
+    return sT if v is None else (sT, jv)
 
 
 def rb_vjp_host(m: _model.RbModel, s0, steps: int, gs, params=(), theta=None, every=None, tape_cap: int = 0):
@@ -1512,26 +1532,8 @@ def rb_vjp_host(m: _model.RbModel, s0, steps: int, gs, params=(), theta=None, ev
     the records; theta None (the model's values), [p] or [N, p].  Returns (s [N, n_rec, num_bodies, 13], gs0
     [N, num_bodies, 13], gtheta [N, p]).  tape_cap: entries one step's tape may hold (0: the model's bound); a world
     that overflows gets NaN gradients and the call raises."""
-    import numpy as np
-
-    nb = m.num_bodies
-    ns = nb * _model.TDS_RB_STATE
-    s0 = np.ascontiguousarray(s0, dtype=np.float64).reshape(-1, nb, _model.TDS_RB_STATE)
-    n, p = s0.shape[0], len(params)
-    every = _rb_every(steps, every)
-    n_rec = int(steps) // every if every >= 1 and steps >= 1 else 1
-    gs = np.ascontiguousarray(gs, dtype=np.float64)
-    if gs.size != n * n_rec * ns:
-        raise ValueError(f"gs: expected [{n}, {n_rec}, {ns}], got {tuple(gs.shape)}")
-    sel = param_spec(params)
-    th = None if theta is None else _theta_rows(theta, n, p)
-    s = np.zeros((n, n_rec, nb, _model.TDS_RB_STATE))
-    gs0 = np.zeros_like(s0)
-    gth = np.zeros((n, max(p, 1)))
-    _rb_check(lib().tds_rb_vjp_host(C.byref(m), n, int(steps), every, s0.ctypes.data, p, sel,
-                                    None if th is None else th.ctypes.data, gs.ctypes.data, s.ctypes.data,
-                                    gs0.ctypes.data, gth.ctypes.data, int(tape_cap)))
-    return s, gs0, gth[:, :p]
+    call = functools.partial(lib().tds_rb_vjp_host, C.byref(m))
+    return _rb_vjp(_HostArrays, call, m, s0, steps, gs, params, theta, every, tape_cap)
 
 
 def rb_vjp_plan(m: _model.RbModel, n: int, steps: int, p: int = 0, tape_cap: int = 0, work_bytes: int = 0):
@@ -1815,62 +1817,27 @@ class HipSim:
     def jvp(self, x, v, y=None):
         """(y, jv): y = f(x) [N, output_dim] and the directional derivatives jv = J(x) v [N, K, output_dim] for
         v [N, K, input_dim] (or [N, input_dim]: K = 1, jv [N, output_dim]).  Any N; f64 handles only (async)."""
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        squeeze = v.dim() == 2
-        v3 = v.unsqueeze(1) if squeeze else v
-        assert v3.is_cuda and v3.dtype == torch.float64 and tuple(v3.shape[::2]) == (x.shape[0], self.input_dim)
-        x, v3 = x.contiguous(), v3.contiguous()
-        n, k = x.shape[0], v3.shape[1]
-        if y is None:
-            y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
-        jv = torch.empty((n, k, self.output_dim), dtype=torch.float64, device=x.device)
-        _check(lib().tds_hip_jvp(self.h, n, C.c_void_p(x.data_ptr()), k, C.c_void_p(v3.data_ptr()),
-                                 C.c_void_p(y.data_ptr()), C.c_void_p(jv.data_ptr())))
+        A = _DevArrays
+        x = A.records(x, self.input_dim, "x")
+        n = x.shape[0]
+        v3, squeeze = A.tangents(v, n, self.input_dim, "v")
+        y = A.new((n, self.output_dim), x) if y is None else y
+        jv = A.new((n, v3.shape[1], self.output_dim), x)
+        _check(lib().tds_hip_jvp(self.h, n, A.ptr(x), v3.shape[1], A.ptr(v3), A.ptr(y), A.ptr(jv)))
         return y, (jv[:, 0] if squeeze else jv)
 
     def jacobian(self, x, rows=None, cols=None, accumulate=None, y=None):
         """J = dy/dx at x [N, input_dim]: [N, n_rows, n_cols] (accumulate None) or [n_rows, n_cols] ("sum", "mean");
         rows / cols: index lists into y / x (None: dense).  With y (a [N, output_dim] tensor) forward_zero's output is
         written too.  Any N; f64 handles only."""
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        x = x.contiguous()
-        n = x.shape[0]
-        ra, nr, rp = _index_array(rows)
-        ca, nc, cp = _index_array(cols)
-        nr = nr if rows is not None else self.output_dim
-        nc = nc if cols is not None else self.input_dim
-        acc = JAC_ACCUMULATE[accumulate]
-        jac = torch.empty((n, nr, nc) if acc == 0 else (nr, nc), dtype=torch.float64, device=x.device)
-        if y is not None:
-            assert y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (n, self.output_dim)
-        _check(lib().tds_hip_jacobian(self.h, n, C.c_void_p(x.data_ptr()), nr, rp, nc, cp, acc,
-                                      C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(jac.data_ptr())))
-        return jac
+        call = functools.partial(lib().tds_hip_jacobian, self.h)
+        return _jacobian(_DevArrays, call, self.model, x, rows, cols, accumulate, y is not None, y)[0]
 
     def vjp(self, x, w, y=None):
         """(y, wj): y = f(x) [N, output_dim] and the vector-Jacobian products wj = w^T J(x) [N, K, input_dim] for
         cotangents w [N, K, output_dim] (or [N, output_dim]: K = 1, wj [N, input_dim]).  Reverse mode: one tape per
         environment, swept back once per cotangent.  Any N; f64 handles only.  The call waits for its kernels."""
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        squeeze = w.dim() == 2
-        w3 = w.unsqueeze(1) if squeeze else w
-        assert w3.is_cuda and w3.dtype == torch.float64 and w3.dim() == 3
-        assert tuple(w3.shape[::2]) == (x.shape[0], self.output_dim)
-        x, w3 = x.contiguous(), w3.contiguous()
-        n, k = x.shape[0], w3.shape[1]
-        if y is None:
-            y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
-        assert y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (n, self.output_dim)
-        wj = torch.empty((n, k, self.input_dim), dtype=torch.float64, device=x.device)
-        _check(lib().tds_hip_vjp(self.h, n, C.c_void_p(x.data_ptr()), k, C.c_void_p(w3.data_ptr()),
-                                 C.c_void_p(y.data_ptr()), C.c_void_p(wj.data_ptr())))
-        return y, (wj[:, 0] if squeeze else wj)
+        return _vjp(_DevArrays, functools.partial(lib().tds_hip_vjp, self.h), self.model, x, w, True, y)[:2]
 
     # -- parameter derivatives: [x | theta], theta the selected model scalars per environment ---------------------
     def jvp_params(self, x, theta, params, v=None):
@@ -1878,48 +1845,16 @@ class HipSim:
         [N, K, input_dim + p] over [x | theta] (or [N, input_dim + p]: K = 1, jv [N, output_dim]).  theta [p] (every
         environment) or [N, p], the values of the selection `params` (tuples or tds_param_t, see param_spec).  Any N;
         f64 handles only (async)."""
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        x = x.contiguous()
-        n, p = x.shape[0], len(params)
-        sel = param_spec(params)
-        th = _dev_theta_rows(theta, n, p)
-        y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
-        if v is None:
-            _check(lib().tds_hip_jvp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), 0,
-                                            None, C.c_void_p(y.data_ptr()), None))
-            return y
-        squeeze = v.dim() == 2
-        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
-        assert v3.is_cuda and v3.dtype == torch.float64 and tuple(v3.shape[::2]) == (n, self.input_dim + p)
-        k = v3.shape[1]
-        jv = torch.empty((n, k, self.output_dim), dtype=torch.float64, device=x.device)
-        _check(lib().tds_hip_jvp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), k,
-                                        C.c_void_p(v3.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(jv.data_ptr())))
-        return y, (jv[:, 0] if squeeze else jv)
+        call = functools.partial(lib().tds_hip_jvp_params, self.h)
+        y, jv = _jvp_params(_DevArrays, call, self.model, x, theta, params, v)
+        return y if v is None else (y, jv)
 
     def vjp_params(self, x, theta, params, w):
         """(y, wj_x, wj_theta): y = f(x; theta) and w^T J split into its x part [N, (K,) input_dim] and its theta part
         [N, (K,) p], for cotangents w [N, K, output_dim] (or [N, output_dim]: K = 1).  theta and params as for
         jvp_params.  Reverse mode; the call waits for its kernels."""
-        import torch
-
-        assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == self.input_dim
-        squeeze = w.dim() == 2
-        w3 = (w.unsqueeze(1) if squeeze else w).contiguous()
-        assert w3.is_cuda and w3.dtype == torch.float64 and w3.dim() == 3
-        assert tuple(w3.shape[::2]) == (x.shape[0], self.output_dim)
-        x = x.contiguous()
-        n, k, p = x.shape[0], w3.shape[1], len(params)
-        sel = param_spec(params)
-        th = _dev_theta_rows(theta, n, p)
-        y = torch.empty((n, self.output_dim), dtype=torch.float64, device=x.device)
-        wj = torch.empty((n, k, self.input_dim + p), dtype=torch.float64, device=x.device)
-        _check(lib().tds_hip_vjp_params(self.h, n, C.c_void_p(x.data_ptr()), p, sel, C.c_void_p(th.data_ptr()), k,
-                                        C.c_void_p(w3.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(wj.data_ptr())))
-        if squeeze:
-            wj = wj[:, 0]
+        call = functools.partial(lib().tds_hip_vjp_params, self.h)
+        y, wj, _ = _vjp(_DevArrays, call, self.model, x, w, True, None, params, theta)
         return y, wj[..., :self.input_dim], wj[..., self.input_dim:]
 
     # -- articulated trajectories: forward_zero chained, forward mode in [x0 | theta] ----------------------------------
@@ -1930,38 +1865,9 @@ class HipSim:
         actions every step) or [N, steps - 1, n_act], the actions of steps 1 ..; not differentiated.  params and theta
         as for jvp_params; theta None: the model's values.  The resident state is not touched.  f64 handles only
         (async)."""
-        import torch
-
-        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
-        x0 = x0.contiguous()
-        n, p = x0.shape[0], len(params)
-        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
-        sel = param_spec(params)
-        th = None if theta is None else _dev_theta_rows(theta, n, p)
-        thp = None if th is None else C.c_void_p(th.data_ptr())
-        up = None
-        if u is not None:
-            assert u.is_cuda and u.dtype == torch.float64
-            assert tuple(u.shape) == (n, max(int(steps) - 1, 0), n_act), (tuple(u.shape), n, int(steps) - 1, n_act)
-            u = u.contiguous()
-            up = C.c_void_p(u.data_ptr())
-        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=x0.device)
-        x0p = C.c_void_p(x0.data_ptr())
-        if v is None:
-            _check(lib().tds_hip_trajectory_jvp(self.h, n, int(steps), int(every), x0p, up, p, sel, thp, 0, None,
-                                                C.c_void_p(s.data_ptr()), None))
-            return s, None
-        squeeze = v.dim() == 2
-        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
-        assert v3.is_cuda and v3.dtype == torch.float64 and v3.dim() == 3 and tuple(v3.shape[::2]) == (n, self.input_dim + p)
-        k = v3.shape[1]
-        js = torch.empty((n, k, max(n_rec, 1), nsd), dtype=torch.float64, device=x0.device)
-        if k == 0:
-            return self.trajectory_jvp(x0, None, steps, every, u, params, theta)[0], js
-        _check(lib().tds_hip_trajectory_jvp(self.h, n, int(steps), int(every), x0p, up, p, sel, thp, k,
-                                            C.c_void_p(v3.data_ptr()), C.c_void_p(s.data_ptr()),
-                                            C.c_void_p(js.data_ptr())))
-        return s, (js[:, 0] if squeeze else js)
+        # (k = 0 directions: v and js have no extent, their pointers are NULL, and the call is the primal one)
+        call = functools.partial(lib().tds_hip_trajectory_jvp, self.h)
+        return _trajectory_jvp(_DevArrays, call, self.model, x0, v, steps, every, u, params, theta)
 
     def trajectory_vjp(self, x0, gs, steps: int, every: int = 1, u=None, params=(), theta=None):
         """(s, gx0, gu, gtheta): the states s of trajectory_jvp's trajectory and the gradients of <gs, s> for the
@@ -1969,35 +1875,8 @@ class HipSim:
         steps 1 .. (zeros where u is None: x0's action slots then feed every step, and gx0 holds their gradient) and
         gtheta [N, p] in theta.  Reverse mode: one primal pass, then the steps' tapes recorded several at a time
         (option traj_vjp_lanes) and swept back in turn; the call waits for its kernels.  f64 handles only."""
-        import torch
-
-        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
-        x0 = x0.contiguous()
-        n, p = x0.shape[0], len(params)
-        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
-        sel = param_spec(params)
-        th = None if theta is None else _dev_theta_rows(theta, n, p)
-        up = None
-        if u is not None:
-            assert u.is_cuda and u.dtype == torch.float64
-            assert tuple(u.shape) == (n, max(int(steps) - 1, 0), n_act), (tuple(u.shape), n, int(steps) - 1, n_act)
-            u = u.contiguous()
-            up = C.c_void_p(u.data_ptr())
-        gs = gs.contiguous()
-        assert gs.is_cuda and gs.dtype == torch.float64
-        assert n_rec < 1 or tuple(gs.shape) == (n, n_rec, nsd), (tuple(gs.shape), n, n_rec, nsd)
-        dev = x0.device
-        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=dev)
-        gx0 = torch.empty((n, self.input_dim), dtype=torch.float64, device=dev)
-        gu = torch.zeros((n, max(int(steps) - 1, 0), max(n_act, 0)), dtype=torch.float64, device=dev)
-        gth = torch.empty((n, p), dtype=torch.float64, device=dev)
-        # (pointers of empty tensors may be NULL: every output gets a buffer of at least one element)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else s.data_ptr())  # noqa: E731
-        _check(lib().tds_hip_trajectory_vjp(self.h, n, int(steps), int(every), C.c_void_p(x0.data_ptr()), up, p, sel,
-                                            None if th is None else C.c_void_p(th.data_ptr()),
-                                            C.c_void_p(gs.data_ptr()), C.c_void_p(s.data_ptr()),
-                                            C.c_void_p(gx0.data_ptr()), ptr(gu), ptr(gth)))
-        return s, gx0, gu, gth
+        call = functools.partial(lib().tds_hip_trajectory_vjp, self.h)
+        return _trajectory_vjp(_DevArrays, call, self.model, x0, gs, steps, every, u, params, theta)[:4]
 
     # -- closed loop: the policy network between the steps, gradients through dynamics and policy -----------------
     def policy_trajectory_vjp(self, x0, policy, gs, steps: int, every: int = 1, ga=None, layer_sizes=None,
@@ -2011,44 +1890,9 @@ class HipSim:
         the primal alone, the gradients come back as None).  obs_raw: the policy sees obs[0], obs[1] as they are at
         every step (fixed-base models), first_obs_raw: at step 0 only.  The call waits for its kernels where a
         cotangent is given.  f64 handles only."""
-        import torch
-
-        assert x0.is_cuda and x0.dtype == torch.float64 and x0.dim() == 2 and x0.shape[1] == self.input_dim
-        x0 = x0.contiguous()
-        n, p = x0.shape[0], len(params)
-        nsd, n_act, n_rec = trajectory_dims(self.model, steps, every)
-        nl, ls, act, ub, P = policy_network_spec(self.model, layer_sizes, activations, use_bias)
-        assert policy.is_cuda and policy.dtype == torch.float64
-        if policy.dim() == 1:
-            policy = policy.unsqueeze(0).expand(n, -1)
-        assert tuple(policy.shape) == (n, P), (tuple(policy.shape), n, P)
-        policy = policy.contiguous()
-        sel = param_spec(params)
-        th = None if theta is None else _dev_theta_rows(theta, n, p)
-        T = max(int(steps), 0)
-        dev = x0.device
-        if gs is not None:
-            gs = gs.contiguous()
-            assert gs.is_cuda and gs.dtype == torch.float64
-            assert n_rec < 1 or tuple(gs.shape) == (n, n_rec, nsd), (tuple(gs.shape), n, n_rec, nsd)
-        if ga is not None:
-            ga = ga.contiguous()
-            assert ga.is_cuda and ga.dtype == torch.float64
-            assert T < 1 or tuple(ga.shape) == (n, T, n_act), (tuple(ga.shape), n, T, n_act)
-        grad = gs is not None or ga is not None
-        s = torch.empty((n, max(n_rec, 1), nsd), dtype=torch.float64, device=dev)
-        u = torch.empty((n, max(T, 1), max(n_act, 1)), dtype=torch.float64, device=dev)
-        gpol = torch.empty((n, P), dtype=torch.float64, device=dev) if grad else None
-        gx0 = torch.empty((n, self.input_dim), dtype=torch.float64, device=dev) if grad else None
-        gth = torch.empty((n, max(p, 1)), dtype=torch.float64, device=dev) if grad else None
-        # (pointers of empty tensors may be NULL: a model without actions is refused by the library, not here)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() if t.numel() else s.data_ptr())  # noqa: E731
-        flags = (1 if first_obs_raw else 0) | (2 if obs_raw else 0)
-        _check(lib().tds_hip_policy_trajectory_vjp(
-            self.h, n, int(steps), int(every), flags, ptr(x0), ptr(policy), nl, _np_ptr(ls), _np_ptr(act), _np_ptr(ub),
-            p, sel, ptr(th), ptr(gs), ptr(ga), ptr(s), ptr(u), ptr(gpol), ptr(gx0), ptr(gth)))
-        u = u[:, :T, :max(n_act, 0)]
-        return s, u, gpol, gx0, (gth[:, :p] if grad else None)
+        call = functools.partial(lib().tds_hip_policy_trajectory_vjp, self.h)
+        return _policy_trajectory_vjp(_DevArrays, call, self.model, x0, policy, gs, steps, every, ga,
+                                      (layer_sizes, activations, use_bias), params, theta, first_obs_raw, obs_raw)[:5]
 
     def policy_trajectory(self, x0, policy, steps: int, every: int = 1, layer_sizes=None, activations=None,
                           use_bias=None, params=(), theta=None, first_obs_raw: bool = False, obs_raw: bool = False):
@@ -2124,7 +1968,7 @@ class HipSim:
         CONTACT_OUTPUTS (shapes: contact_shapes(model, N)) as a dict of tensors on the handle's device.  out: a dict of
         tensors to write into.  Any N; f64 handles only; only the wanted outputs are computed (async)."""
         want = _contact_want(want)
-        x = _dev_records(x, self.input_dim, "x")
+        x = _DevArrays.records(x, self.input_dim, "x")
         n = x.shape[0]
         res, o = _dev_outputs(contact_shapes(self.model, n), want, out, x.device, struct=ContactOut)
         _check(lib().tds_hip_contacts(self.h, n, C.c_void_p(x.data_ptr()), C.byref(o)))
@@ -2164,81 +2008,24 @@ class HipSim:
         device: q [N, dof_q] float64, iterations [N] and status [N] int32 (IK_FAILED / IK_CONVERGED / IK_REACHED),
         residual [N] float64.  out: a dict of tensors to write into; one that names q but leaves out iterations,
         status or residual has those not computed.  Any N; f64 handles only (async)."""
-        import torch
-
-        q_init = _dev_records(q_init, self.model.dof_q, "q_init")
-        n = q_init.shape[0]
-        k, links, pts, lp, pp = _ik_targets(links, body_points)
-        assert targets.is_cuda and targets.dtype == torch.float64 and tuple(targets.shape) == (n, k, 3), "targets"
-        targets = targets.contiguous()
-        q_reference, qrp = _DevArrays.rows(q_reference, n, self.model.dof_q, "q_reference")
-        o = ik_options(method, **options)
-        assert out is None or "q" in out, "out must hold q"
-        shapes = _ik_shapes(self.model, n)
-        res, _ = _dev_outputs(shapes, [name for name in shapes if out is None or name in out], out,
-                              q_init.device, dtypes=_IK_DTYPES)
-        ptr = {name: C.c_void_p(t.data_ptr()) for name, t in res.items()}
-        _check(lib().tds_hip_inverse_kinematics(self.h, n, C.c_void_p(q_init.data_ptr()), k, lp, pp,
-                                                C.c_void_p(targets.data_ptr()), qrp, C.byref(o), ptr["q"],
-                                                ptr.get("iterations"), ptr.get("status"), ptr.get("residual")))
-        return res
+        call = functools.partial(lib().tds_hip_inverse_kinematics, self.h)
+        return _inverse_kinematics(_DevArrays, call, self.model, q_init, links, targets, body_points, q_reference, out,
+                                   ik_options(method, **options))
 
     # -- batched iLQR (csrc/tds_lqr.hip) ----------------------------------------------------------------------
     def lqr_backward(self, A, B, lx, lu, lxx, luu, lux, mu):
         """The backward pass of n time-varying LQ problems as one launch (tds_hip_lqr_backward; arguments and results
         as hip_backend.lqr_backward_host, CUDA float64 tensors; mu [n]).  The handle's model is not read.  Async."""
-        import torch
-
-        (n, T, nx, nu), shapes = _lqr_shapes(A, B)
-        arg = {"A": A, "B": B, "lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux, "mu": mu}
-        shapes.update({"A": (n, T, nx, nx), "B": (n, T, nx, nu)})
-        for key, shape in shapes.items():
-            t = arg[key]
-            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
-                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
-            arg[key] = t.contiguous()
-        dev = A.device
-        k = torch.empty((n, T, nu), dtype=torch.float64, device=dev)
-        K = torch.empty((n, T, nu, nx), dtype=torch.float64, device=dev)
-        dv = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        _check(lib().tds_hip_lqr_backward(self.h, n, T, nx, nu,
-                                          *(C.c_void_p(arg[key].data_ptr())
-                                            for key in ("A", "B", "lx", "lu", "lxx", "luu", "lux", "mu")),
-                                          C.c_void_p(k.data_ptr()), C.c_void_p(K.data_ptr()), C.c_void_p(dv.data_ptr()),
-                                          C.c_void_p(status.data_ptr())))
-        return k, K, dv, status
+        call = functools.partial(lib().tds_hip_lqr_backward, self.h)
+        return _lqr_backward(_DevArrays, call, False, A, B, lx, lu, lxx, luu, lux, mu)
 
     def lqr_backward_box(self, A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi, check: bool = True):
         """The backward pass under control limits as one launch (tds_hip_lqr_backward_box; arguments and results as
         hip_backend.lqr_backward_box_host, CUDA tensors).  check: dlo <= dhi without NaN is verified before the launch
         (the one host wait of the call); a caller that built the bounds itself passes False and the call is
         asynchronous.  The handle's model is not read."""
-        import torch
-
-        (n, T, nx, nu), shapes = _lqr_shapes(A, B)
-        arg = {"A": A, "B": B, "lx": lx, "lu": lu, "lxx": lxx, "luu": luu, "lux": lux, "mu": mu, "dlo": dlo, "dhi": dhi}
-        shapes.update({"A": (n, T, nx, nx), "B": (n, T, nx, nu), "dlo": (n, T, nu), "dhi": (n, T, nu)})
-        for key, shape in shapes.items():
-            t = arg[key]
-            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
-                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
-            arg[key] = t.contiguous()
-        if check:
-            _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
-        dev = A.device
-        k = torch.empty((n, T, nu), dtype=torch.float64, device=dev)
-        K = torch.empty((n, T, nu, nx), dtype=torch.float64, device=dev)
-        dv = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        clamped = torch.empty((n, T), dtype=torch.int32, device=dev)
-        its = torch.empty((n, T), dtype=torch.int32, device=dev)
-        _check(lib().tds_hip_lqr_backward_box(
-            self.h, n, T, nx, nu,
-            *(C.c_void_p(arg[key].data_ptr())
-              for key in ("A", "B", "lx", "lu", "lxx", "luu", "lux", "mu", "dlo", "dhi")),
-            *(C.c_void_p(t.data_ptr()) for t in (k, K, dv, status, clamped, its))))
-        return k, K, dv, status, clamped, its
+        call = functools.partial(lib().tds_hip_lqr_backward_box, self.h)
+        return _lqr_backward(_DevArrays, call, check, A, B, lx, lu, lxx, luu, lux, mu, dlo, dhi)
 
     def feedback_rollout(self, x0, s_nom, u_nom, k, K, alpha, problem_of_row=None, check: bool = True, u_lo=None,
                          u_hi=None):
@@ -2249,47 +2036,11 @@ class HipSim:
         False and the call is asynchronous.  u_lo, u_hi [P, T, n_act] (both or neither): u_t is clamped to them
         (tds_hip_feedback_rollout_box; u_lo <= u_hi without NaN is verified under check); None is the call without
         limits."""
-        import torch
-
-        (rows, P, T, nsd, n_act), shapes = _feedback_shapes(self.model, x0, s_nom)
-        arg = {"x0": x0, "s_nom": s_nom, "u_nom": u_nom, "k": k, "K": K, "alpha": alpha}
-        shapes.update({"x0": (rows, self.input_dim), "s_nom": (P, T + 1, nsd)})
-        if (u_lo is None) != (u_hi is None):
-            raise ValueError("u_lo and u_hi are given together or not at all")
-        if u_lo is not None:
-            arg.update({"u_lo": u_lo, "u_hi": u_hi})
-            shapes.update({"u_lo": (P, T, n_act), "u_hi": (P, T, n_act)})
-        for key, shape in shapes.items():
-            t = arg[key]
-            if not (t.is_cuda and t.dtype == torch.float64) or tuple(t.shape) != shape:
-                raise ValueError(f"{key}: expected a CUDA float64 tensor {list(shape)}, got {list(t.shape)} {t.dtype}")
-            arg[key] = t.contiguous()
-        if problem_of_row is not None:
-            if not (problem_of_row.is_cuda and problem_of_row.dtype == torch.int32) or \
-                    tuple(problem_of_row.shape) != (rows,):
-                raise ValueError(f"problem_of_row: expected a CUDA int32 tensor [{rows}]")
-            problem_of_row = problem_of_row.contiguous()
-            if check and not (0 <= int(problem_of_row.min()) and int(problem_of_row.max()) < P):
-                raise ValueError(f"problem_of_row: entries outside [0, {P})")
-        elif rows != P:
-            raise ValueError(f"problem_of_row is None: x0 needs one row per problem ({P}), got {rows}")
-        s = torch.empty((rows, T + 1, nsd), dtype=torch.float64, device=x0.device)
-        u = torch.empty((rows, T, n_act), dtype=torch.float64, device=x0.device)
-        if u_lo is not None:
-            if check:
-                _bounds_ordered(arg["u_lo"], arg["u_hi"], ("u_lo", "u_hi"))
-            _check(lib().tds_hip_feedback_rollout_box(
-                self.h, rows, T, *(C.c_void_p(arg[key].data_ptr()) for key in ("x0", "s_nom", "u_nom", "k", "K", "alpha")),
-                C.c_void_p(problem_of_row.data_ptr()) if problem_of_row is not None else None,
-                C.c_void_p(arg["u_lo"].data_ptr()), C.c_void_p(arg["u_hi"].data_ptr()), C.c_void_p(s.data_ptr()),
-                C.c_void_p(u.data_ptr())))
-            return s, u
-        _check(lib().tds_hip_feedback_rollout(self.h, rows, T,
-                                              *(C.c_void_p(arg[key].data_ptr())
-                                                for key in ("x0", "s_nom", "u_nom", "k", "K", "alpha")),
-                                              C.c_void_p(problem_of_row.data_ptr()) if problem_of_row is not None
-                                              else None, C.c_void_p(s.data_ptr()), C.c_void_p(u.data_ptr())))
-        return s, u
+        # (P is an argument of the host entry points alone)
+        calls = [lambda rows, T, P, *ptrs, f=f: f(self.h, rows, T, *ptrs)
+                 for f in (lib().tds_hip_feedback_rollout, lib().tds_hip_feedback_rollout_box)]
+        return _feedback_rollout(_DevArrays, calls, check, check, self.model, x0, s_nom, u_nom, k, K, alpha, problem_of_row,
+                                 u_lo, u_hi)
 
     def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
         """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
@@ -2644,36 +2395,8 @@ class RigidBodySim:
         [N, num_bodies, 13]); v None: jv None.  params: a selection of ("mass", body), ("gravity", comp), ("friction",),
         ("restitution",) (hip_backend.param_spec); theta None (the model's values), [p] or [N, p].  The resident state
         is not touched.  f64 handles only (async on the handle's stream)."""
-        import torch
-
-        nb = self.model.num_bodies
-        ns = nb * _model.TDS_RB_STATE
-        assert s0.is_cuda and s0.dtype == torch.float64
-        s0 = s0.reshape(-1, nb, _model.TDS_RB_STATE).contiguous()
-        n, p = s0.shape[0], len(params)
-        sel = param_spec(params)
-        th = None
-        if theta is not None:
-            assert theta.is_cuda and theta.dtype == torch.float64
-            th = (theta.unsqueeze(0).expand(n, p) if theta.dim() == 1 else theta).contiguous()
-            assert tuple(th.shape) == (n, p), (tuple(th.shape), n, p)
-        thp = None if th is None else C.c_void_p(th.data_ptr())
-        sT = torch.empty_like(s0)
-        if v is None:
-            _rb_check(lib().tds_rb_jvp(self.h, n, int(steps), C.c_void_p(s0.data_ptr()), p, sel, thp, 0, None,
-                                       C.c_void_p(sT.data_ptr()), None))
-            return sT, None
-        squeeze = v.dim() == 2
-        v3 = (v.unsqueeze(1) if squeeze else v).contiguous()
-        assert v3.is_cuda and v3.dtype == torch.float64 and v3.dim() == 3 and tuple(v3.shape[::2]) == (n, ns + p)
-        k = v3.shape[1]
-        jv = torch.empty((n, k, nb, _model.TDS_RB_STATE), dtype=torch.float64, device=s0.device)
-        if k > 0:
-            _rb_check(lib().tds_rb_jvp(self.h, n, int(steps), C.c_void_p(s0.data_ptr()), p, sel, thp, k,
-                                       C.c_void_p(v3.data_ptr()), C.c_void_p(sT.data_ptr()), C.c_void_p(jv.data_ptr())))
-        else:
-            sT = self.jvp(s0, None, steps, params, theta)[0]
-        return sT, (jv[:, 0] if squeeze else jv)
+        # (k = 0 directions: v and jv have no extent, their pointers are NULL, and the call is the primal one)
+        return _rb_jvp(_DevArrays, functools.partial(lib().tds_rb_jvp, self.h), self.model, s0, steps, v, params, theta)
 
     def vjp(self, s0, gs, steps: int, params=(), theta=None, every=None, tape_cap: int = 0, work_bytes: int = 0):
         """(s, gs0, gtheta): `steps` World::steps from s0 [N, num_bodies, 13] (any N), the state after every `every`-th
@@ -2684,31 +2407,8 @@ class RigidBodySim:
         the work buffer (0: 8 GiB): it decides windows and passes, never the results (hip_backend.rb_vjp_plan).  A world
         that overflows its tape gets NaN gradients and the call raises.  The resident state is not touched.  f64
         handles only; the call waits for its launches."""
-        import torch
-
-        nb = self.model.num_bodies
-        ns = nb * _model.TDS_RB_STATE
-        assert s0.is_cuda and s0.dtype == torch.float64
-        s0 = s0.reshape(-1, nb, _model.TDS_RB_STATE).contiguous()
-        n, p = s0.shape[0], len(params)
-        every = _rb_every(steps, every)
-        n_rec = int(steps) // every if every >= 1 and steps >= 1 else 1
-        assert gs.is_cuda and gs.dtype == torch.float64 and gs.numel() == n * n_rec * ns, (tuple(gs.shape), n, n_rec, ns)
-        gs = gs.contiguous()
-        sel = param_spec(params)
-        th = None
-        if theta is not None:
-            assert theta.is_cuda and theta.dtype == torch.float64
-            th = (theta.unsqueeze(0).expand(n, p) if theta.dim() == 1 else theta).contiguous()
-            assert tuple(th.shape) == (n, p), (tuple(th.shape), n, p)
-        s = torch.empty((n, n_rec, nb, _model.TDS_RB_STATE), dtype=torch.float64, device=s0.device)
-        gs0 = torch.empty_like(s0)
-        gth = torch.empty((n, p), dtype=torch.float64, device=s0.device)
-        _rb_check(lib().tds_rb_vjp(self.h, n, int(steps), every, C.c_void_p(s0.data_ptr()), p, sel,
-                                   None if th is None else C.c_void_p(th.data_ptr()), C.c_void_p(gs.data_ptr()),
-                                   C.c_void_p(s.data_ptr()), C.c_void_p(gs0.data_ptr()),
-                                   C.c_void_p(gth.data_ptr()) if p else None, int(tape_cap), int(work_bytes)))
-        return s, gs0, gth
+        call = functools.partial(lib().tds_rb_vjp, self.h)
+        return _rb_vjp(_DevArrays, call, self.model, s0, steps, gs, params, theta, every, tape_cap, work_bytes)
 
     def jacobian(self, s0, steps: int, wrt, params=(), theta=None):
         """dense d s_T / d [s0 entries wrt | theta]: [N, num_bodies * 13, len(wrt) + p] from unit directions.  wrt: a
