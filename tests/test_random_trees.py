@@ -24,18 +24,32 @@ def _rot(rng):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def random_tree_model(seed, floating=False, spherical=False):
+SHAPE_KINDS = {"sphere": 0.6, "capsule": 0.3, "box": 0.1}   # kind -> its share of the shapes drawn
+
+
+def random_tree_model(seed, floating=False, spherical=False, links=None, p_fixed=0.1, contact_points=24,
+                      shapes=tuple(SHAPE_KINDS)):
     """floating: the tree hangs off a floating base (random inertia, own collision shapes); links may attach
-    to the base directly (parent -1) anywhere in the list, as in the reference's ant_org.urdf"""
+    to the base directly (parent -1) anywhere in the list, as in the reference's ant_org.urdf.
+    The knobs aim a tree at a size (the defaults draw the models the tests of this file have always seen,
+    tests/test_tree_derivs_cpu.py holds their digests): links (lo, hi): the range of the link count, both ends
+    included; p_fixed: the probability that a joint behind the root chain is fixed; contact_points: the budget of
+    contact points (sphere 1, capsule 2, box 8); shapes: the shape kinds drawn, with SHAPE_KINDS' shares among them."""
     rng = np.random.default_rng(seed)
+    lo, hi = (3, 22) if links is None else (max(links[0], 3), max(links[1], 3))   # (a fixed base draws its root chain too)
+    lo_f, hi_f = (1, 20) if links is None else links
+    kinds = [k for k in SHAPE_KINDS if k in shapes]
+    kind_p = [SHAPE_KINDS[k] for k in kinds]
+    if len(kinds) < len(SHAPE_KINDS):
+        kind_p = [p / sum(kind_p) for p in kind_p]
     m = tds_amd.Model()
     m.abi_version = tds_amd.TDS_HIP_ABI_VERSION
     m.step_mode = tds_amd.TDS_STEP_TAU
-    nl = int(rng.integers(3, 23))
+    nl = int(rng.integers(lo, hi + 1))
     n_virtual = int(rng.integers(0, 6)) if rng.random() < 0.6 else 0     # massless root chain length
     n_virtual = min(n_virtual, nl - 2)
     if floating:
-        nl, n_virtual = int(rng.integers(1, 21)), 0
+        nl, n_virtual = int(rng.integers(lo_f, hi_f + 1)), 0
     if spherical:       # (a spherical joint takes three lanes and four coordinates)
         nl = int(rng.integers(2, 12))
         n_virtual = min(n_virtual, 3, nl - 1)
@@ -57,7 +71,7 @@ def random_tree_model(seed, floating=False, spherical=False):
         if i < n_virtual:
             jt = virt[i]
         else:
-            jt = int(rng.integers(0, 8)) if (rng.random() < 0.9 or i == n_virtual) else M.JOINT_FIXED
+            jt = int(rng.integers(0, 8)) if (rng.random() < 1.0 - p_fixed or i == n_virtual) else M.JOINT_FIXED
             if spherical and (rng.random() < 0.4 or i == n_virtual) and nq_used + 4 <= 30:
                 jt = M.JOINT_SPHERICAL
         l.joint_type = jt
@@ -125,9 +139,9 @@ def random_tree_model(seed, floating=False, spherical=False):
     for i in range(-1 if floating else n_virtual, nl):
         if rng.random() < 0.6 and ng < tds_amd.TDS_MAX_GEOMS:
             g = m.geoms[ng]
-            kind = rng.choice(["sphere", "capsule", "box"], p=[0.6, 0.3, 0.1])
+            kind = rng.choice(kinds, p=kind_p)
             need = {"sphere": 1, "capsule": 2, "box": 8}[kind]
-            if ncp + need > 24:
+            if ncp + need > contact_points:
                 continue
             ncp += need
             g.link = i
