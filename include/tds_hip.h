@@ -1076,6 +1076,53 @@ int tds_hip_feedback_rollout_box_host(const tds_model_t *model, int rows, int T,
                                       const double *alpha, const int32_t *problem_of_row, const double *u_lo,
                                       const double *u_hi, double *s_out, double *u_out);
 
+/* Batched system identification: one damped Gauss-Newton (Levenberg-Marquardt) step of n least-squares problems
+   (csrc/tds_lm.hip).  Problem i owns the contiguous rows row_start[i] .. row_start[i+1]-1 of `rows` trajectories; a row
+   has m = n_rec (nq + nd) residual entries; the rows of a problem share its p parameters.  All arrays row-major, f64
+   where not said: row_start [n+1] (int32, non-decreasing from 0 to rows), s and s_obs [rows][m] (the simulated and the
+   observed states), w [rows][m] or NULL (every weight 1), js [rows][p][m] (tds_hip_trajectory_jvp's js [n][k][n_rec][nsd]
+   with k = p unit directions on theta, as it comes), dlo <= dhi [n][p] (bounds on the STEP; both NULL: none; +-inf where
+   a parameter has none), lambda [n][n_lambda] (> 0: the damping of each candidate).
+     Sums, over the entries of the problem's rows: an entry with w == 0 is skipped (its s_obs may be NaN: a missing
+   measurement); otherwise a = w (s - s_obs), c_i = w js_i, and
+       cost = sum a^2 / 2        g_i = sum c_i a        H_ij = sum c_i c_j
+   each ONE sequential sum in the order (row ascending, entry ascending), products not contracted.
+     Damping and the step, for each candidate l:
+       D_i = min(max(H_ii, 1e-6), 1e32)                     (Ceres's min_lm_diagonal, max_lm_diagonal)
+       A = H + lambda_l diag(D)
+       delta_l = argmin  delta^T A delta / 2 + g^T delta   over dlo <= delta <= dhi
+   by the projected-Newton box QP of tds_hip_lqr_backward_box (its rules 1-7 and constants, with H = A, q = g) from
+   delta = clamp(0, dlo, dhi); with infinite bounds delta_l is the plain damped Gauss-Newton step -A^-1 g (zero where
+   |g|_2 < 1e-8: rule 4).  pred_l = -(g^T delta_l + delta_l^T H delta_l / 2) with the undamped H.
+     Outputs: cost [n], g [n][p], H [n][p][p] (symmetric), delta [n][n_lambda][p], pred [n][n_lambda], and int32
+   [n][n_lambda] each: clamped (bit a set: parameter a in the QP's final clamped set), qp_iterations, status:
+       0  the candidate is valid
+       1  a pivot of that candidate's factorisation was not positive: delta_l = 0, pred_l = 0 (clamped, qp_iterations 0)
+       2  the problem's cost or a diagonal entry of its H is not finite -- a counted entry that is not finite (the NaN
+          records of an inertia that is not positive definite) always makes one so, as does an entry whose square
+          overflows --: every candidate of that problem; cost = +inf, and g, H, delta, pred, clamped, qp_iterations zero
+   The other problems are not affected, bit for bit as if run alone.  A problem without rows is legal (H = g = 0,
+   delta = 0).  p = 0 is the cost-only mode: js, bounds, lambda and every output but cost may be NULL and only cost is
+   written (+inf where it is not finite), whatever n_lambda.
+     n >= 1, rows >= 0, m >= 1, 0 <= p <= TDS_LM_MAX_P, 0 <= n_lambda <= TDS_LM_MAX_LAMBDA: beyond the two bounds
+   TDS_ERR_UNSUPPORTED.  A row_start that is not non-decreasing from 0 to rows, dlo > dhi, a NaN bound, a lambda that is
+   not positive and finite: the caller's promise on the device (row_start is clipped to [0, rows], so that nothing
+   outside the arrays is read), TDS_ERR_INVALID_ARG in the host checker.  Every sum and solve is the same sequence of
+   operations on the device and in the host checker (the unit is built without FP contraction).  The handle supplies
+   device, stream and error text; its model is not read.  ONE launch on the handle's stream, one wavefront per problem,
+   no host wait. */
+#define TDS_LM_MAX_P 16
+#define TDS_LM_MAX_LAMBDA 8
+int tds_hip_lm_step(tds_hip_sim_t *sim, int n, int rows, int m, int p, int n_lambda, const void *row_start_dev,
+                    const void *s_dev, const void *s_obs_dev, const void *w_dev, const void *js_dev, const void *dlo_dev,
+                    const void *dhi_dev, const void *lambda_dev, void *cost_dev, void *g_dev, void *H_dev,
+                    void *delta_dev, void *pred_dev, void *clamped_dev, void *qp_iterations_dev, void *status_dev);
+/* The same statement with plain loops on the CPU (host arrays, needs no GPU): the checker. */
+int tds_hip_lm_step_host(int n, int rows, int m, int p, int n_lambda, const int32_t *row_start, const double *s,
+                         const double *s_obs, const double *w, const double *js, const double *dlo, const double *dhi,
+                         const double *lambda, double *cost, double *g, double *H, double *delta, double *pred,
+                         int32_t *clamped, int32_t *qp_iterations, int32_t *status);
+
 /* Duration of the most recent stepping CALL (all of its launches: one for a plain step, two for the split
    auto-reset step, 2 n + 1 for a per-step-launch rollout, the whole graph for tds_hip_step_many) measured with HIP
    events on the handle's stream, in milliseconds (enabled by tds_hip_set_timing(sim, 1); synchronises). */

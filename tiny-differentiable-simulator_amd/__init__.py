@@ -12,3 +12,4 @@ from .vec_env import VectorizedAntEnv, VectorizedLaikagoEnv, VectorizedEnv  # no
 from .autograd import step_fn, param_step_fn, rb_rollout_fn, trajectory_fn, policy_trajectory_fn, contact_fn  # noqa: F401,E402
 from .autograd import dynamics_fn, inverse_dynamics_fn  # noqa: F401,E402
 from .ilqr import ilqr, QuadraticCost  # noqa: F401,E402
+from .sysid import sysid, sysid_starts  # noqa: F401,E402

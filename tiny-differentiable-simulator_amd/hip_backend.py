@@ -191,6 +191,9 @@ def lib():
             getattr(L, f"tds_hip_lqr_backward{box}_host").argtypes = lq_tail
             getattr(L, f"tds_hip_feedback_rollout{box}").argtypes = [C.c_void_p, C.c_int, C.c_int] + fb_tail
             getattr(L, f"tds_hip_feedback_rollout{box}_host").argtypes = [P, C.c_int, C.c_int, C.c_int] + fb_tail
+        lm_tail = [C.c_int] * 5 + [C.c_void_p] * 16
+        L.tds_hip_lm_step.argtypes = [C.c_void_p] + lm_tail
+        L.tds_hip_lm_step_host.argtypes = lm_tail
         _lib = L
     return _lib
 
@@ -430,7 +433,7 @@ EXPORTED_SYMBOLS = [
     "tds_hip_ik_default_options", "tds_hip_inverse_kinematics", "tds_hip_inverse_kinematics_host",
     "tds_hip_lqr_backward", "tds_hip_lqr_backward_host", "tds_hip_feedback_rollout", "tds_hip_feedback_rollout_host",
     "tds_hip_lqr_backward_box", "tds_hip_lqr_backward_box_host", "tds_hip_feedback_rollout_box",
-    "tds_hip_feedback_rollout_box_host",
+    "tds_hip_feedback_rollout_box_host", "tds_hip_lm_step", "tds_hip_lm_step_host",
     "tds_hip_contacts", "tds_hip_contacts_host", "tds_hip_contact_layout",
     "tds_hip_contacts_jvp", "tds_hip_contacts_jvp_host", "tds_hip_contacts_jvp_tangents",
     "tds_hip_dynamics_jvp", "tds_hip_inverse_dynamics_jvp", "tds_hip_dynamics_jvp_host",
@@ -1287,6 +1290,68 @@ def feedback_rollout_host(m: _model.Model, x0, s_nom, u_nom, k, K, alpha=1.0, pr
     return _feedback_rollout(_HostArrays, calls, False, True, m, x0, s_nom, u_nom, k, K, alpha, problem_of_row, u_lo, u_hi)
 
 
+# -- batched system identification: the Levenberg-Marquardt step (csrc/tds_lm.hip) -----------------------------------
+LM_MAX_P, LM_MAX_LAMBDA = 16, 8
+LM_OUTPUTS = ("cost", "g", "H", "delta", "pred", "clamped", "qp_iterations", "status")
+
+
+def _lm_step(X, call, check, row_start, s, s_obs, js, lam, w, dlo, dhi):
+    """the outputs of tds_hip_lm_step[_host] by name (LM_OUTPUTS; js None, the cost-only mode: cost alone).  check:
+    row_start, dlo <= dhi and lam > 0 are verified here (on the device a host wait each)"""
+    if len(s.shape) < 2:
+        raise ValueError(f"s: expected [rows, m] (or [rows, n_rec, nsd]), got {list(s.shape)}")
+    rows, m = int(s.shape[0]), _entries(s.shape[1:])
+    row_start = X.exact(row_start, None, "row_start", "int32", error=ValueError)
+    n = _entries(row_start.shape) - 1
+    if len(row_start.shape) != 1 or n < 1:
+        raise ValueError(f"row_start: expected [n + 1] with n >= 1, got {list(row_start.shape)}")
+    p = 0 if js is None else int(js.shape[1]) if len(js.shape) >= 3 and js.shape[0] == rows else -1
+    if p < 0:
+        raise ValueError(f"js: expected [{rows}, p, m] (or [{rows}, p, n_rec, nsd]), got {list(js.shape)}")
+    L = 0 if p == 0 or lam is None else int(lam.shape[-1])
+    if (dlo is None) != (dhi is None):
+        raise ValueError("dlo and dhi are given together or not at all")
+    arg = {"s": (s, (rows, m)), "s_obs": (s_obs, (rows, m)), "w": (w, (rows, m)), "js": (js, (rows, p, m)),
+           "dlo": (dlo, (n, p)), "dhi": (dhi, (n, p)), "lam": (lam, (n, L))}
+    arg = {key: None if a is None or (p == 0 and key in ("js", "dlo", "dhi", "lam")) else
+           X.exact(a, shape, key, by_count=key in ("s", "s_obs", "w", "js"), error=ValueError)
+           for key, (a, shape) in arg.items()}
+    if p > 0 and arg["lam"] is None:
+        raise ValueError(f"lam: expected [{n}, n_lambda]")
+    if check:
+        if not (int(row_start[0]) == 0 and int(row_start[-1]) == rows and bool((row_start[1:] >= row_start[:-1]).all())):
+            raise ValueError(f"row_start: not non-decreasing from 0 to rows = {rows}")
+        if arg["dlo"] is not None:
+            _bounds_ordered(arg["dlo"], arg["dhi"], ("dlo", "dhi"))
+        if arg["lam"] is not None and not bool(((arg["lam"] > 0) & (arg["lam"] < float("inf"))).all()):
+            raise ValueError("lam: a lambda that is not positive and finite")
+    shapes = {"cost": (n,), "g": (n, p), "H": (n, p, p), "delta": (n, L, p), "pred": (n, L), "clamped": (n, L),
+              "qp_iterations": (n, L), "status": (n, L)}
+    out = {k: X.new(shapes[k], row_start, "int32" if k in LM_OUTPUTS[5:] else "float64")
+           for k in (LM_OUTPUTS if p > 0 else LM_OUTPUTS[:1])}
+    _check(call(n, rows, m, p, L, X.ptr(row_start), *(X.ptr(a) for a in arg.values()),
+                *(X.ptr(out.get(k)) for k in LM_OUTPUTS)))
+    return out
+
+
+def lm_step_host(row_start, s, s_obs, js, lam=None, w=None, dlo=None, dhi=None):
+    """One Levenberg-Marquardt step of n least-squares problems on the CPU (tds_hip_lm_step_host; the checker of
+    HipSim.lm_step, needs no GPU; include/tds_hip.h states it).  Problem i owns the rows row_start[i] ..
+    row_start[i + 1] - 1 (row_start [n + 1] ints); s, s_obs [rows, m] (or [rows, n_rec, nsd]: trajectory_jvp_host's s),
+    w the same shape or None (weights 1; an entry of weight 0 is skipped, whatever its observation), js [rows, p, m]
+    (trajectory_jvp_host's js for the p unit directions on theta, as it comes), lam [n, n_lambda] > 0, dlo <= dhi [n, p]
+    or both None: the bounds on the step.  Returns a dict: cost [n], g [n, p], H [n, p, p], delta [n, n_lambda, p],
+    pred [n, n_lambda], and int32 [n, n_lambda]: clamped, qp_iterations, status (0 valid, 1 that candidate's system not
+    positive definite, 2 the problem's data not finite).  js None is the cost-only mode: {"cost": [n]}."""
+    import numpy as np
+
+    # (what the host form accepts beyond the device's: array-likes; the library itself verifies the arguments)
+    row_start = np.asarray(row_start, dtype=np.int64).astype(np.int32)
+    f64 = lambda a: None if a is None else np.asarray(a, dtype=np.float64)  # noqa: E731
+    return _lm_step(_HostArrays, lib().tds_hip_lm_step_host, False, row_start, f64(s), s_obs, f64(js), f64(lam), w,
+                    dlo, dhi)
+
+
 def trajectory_records(m: _model.Model, x0, s, u):
     """The [N T, input_dim] records of a trajectory, problem-major (what jacobian / jacobian_host linearise): record
     (n, t) = [s[n, t] | u[n, t] | the rest of x0[n]].  x0 [N, input_dim], s [N, T + 1, nsd] (or [N, T, nsd]),
@@ -2041,6 +2106,16 @@ class HipSim:
                  for f in (lib().tds_hip_feedback_rollout, lib().tds_hip_feedback_rollout_box)]
         return _feedback_rollout(_DevArrays, calls, check, check, self.model, x0, s_nom, u_nom, k, K, alpha, problem_of_row,
                                  u_lo, u_hi)
+
+    # -- batched system identification (csrc/tds_lm.hip) --------------------------------------------------------
+    def lm_step(self, row_start, s, s_obs, js, lam=None, w=None, dlo=None, dhi=None, check: bool = True):
+        """One Levenberg-Marquardt step of n least-squares problems as one launch, a wavefront per problem
+        (tds_hip_lm_step; arguments and results as hip_backend.lm_step_host, CUDA float64 tensors; row_start a CUDA
+        int32 tensor [n + 1]).  Any n, independent of num_envs; the handle's model is not read.  check: row_start,
+        dlo <= dhi without NaN and lam > 0 are verified before the launch (the host waits of the call); a caller that
+        built them itself passes False and the call is asynchronous."""
+        call = functools.partial(lib().tds_hip_lm_step, self.h)
+        return _lm_step(_DevArrays, call, check, row_start, s, s_obs, js, lam, w, dlo, dhi)
 
     def trajectory_jacobian(self, x0, steps: int, wrt, params=(), theta=None, every: int = 1, u=None):
         """dense d s / d [x0 entries wrt | theta]: [N, n_rec (nq + nd), len(wrt) + p] from unit directions (wrt: indices
